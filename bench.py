@@ -16,10 +16,13 @@ of the packed constants from rank 0 (outside the timed region).
 
 `--lmk-only` times BASELINE configs[1] instead (B = 128 by default, 68 landmarks + pose, no mesh).
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline`, `cpu_baseline` and `extra`
-(the other BASELINE configs and the reference-API variants of the headline step, each timed briefly on the same box:
-configs[1] B = 128 landmarks only, fp32 NCHW ingest through forward_test, the reference's packed [B,3,53215] output,
-one stream, ResNet-50 B = 512 = configs[4]).
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run does only what that line needs: set-up, warm-up, the
+timed steps.  `--full` adds `roofline`, `cpu_baseline` and `extra` (the other BASELINE configs and the reference-API variants
+of the headline step, each timed briefly on the same box: configs[1] B = 128 landmarks only, fp32 NCHW ingest through
+forward_test, the reference's packed [B,3,53215] output, one stream, ResNet-50 B = 512 = configs[4]).
+
+`--dump-outputs DIR` writes what the last timed step returned (params, landmarks, pose, a fixed sample of the mesh) as
+DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import ctypes
@@ -361,6 +364,23 @@ def _recon_rocprof():
 RECON_ROCPROF = _recon_rocprof()
 
 
+def dump_outputs(out_dir, param, lmk, mesh, pose):
+    """`--dump-outputs`: what a caller of the timed step receives -- params [B,62], landmarks [B,3,68], pose angles and translation
+    [B,3] and the mesh [B,3,53215] -- as float32 .npy files.  The mesh is a fixed sample, every face at 2048 seeded vertex indices
+    (25 MB at B = 1024); above 1024 faces every array keeps 1024 seeded faces, so that the files stay under 64 MB at any batch."""
+    os.makedirs(out_dir, exist_ok=True)
+    B = param.shape[0]
+    faces = torch.from_numpy(np.sort(np.random.default_rng(1).choice(B, 1024, replace=False))) if B > 1024 else None
+    arrays = dict(param=param, lmk=lmk, pose_angles=pose[0], pose_t3d=pose[1])
+    if mesh is not None:
+        verts = np.sort(np.random.default_rng(0).choice(mesh.shape[2], min(2048, mesh.shape[2]), replace=False))
+        arrays['mesh_sample'] = mesh[:, :, torch.from_numpy(verts).to(mesh.device)]
+    for name, t in arrays.items():
+        if faces is not None:
+            t = t.index_select(0, faces.to(t.device))
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 def time_steps(fn, steps, warmup, sync):
     for _ in range(warmup):
         fn()
@@ -389,6 +409,9 @@ def main():
     ap.add_argument('--prewarm', type=float, default=0.3, help='seconds of untimed steps BEFORE the W warm-up steps: the clocks of an idle GPU ramp for '
                     '~0.2 s, and a 20-step / 24 ms window taken right after W = 5 steps reads ~5 %% low (reported as `prewarm_s`)')
     ap.add_argument('--dry-run', action='store_true', help='multi-process plumbing only (gloo on host memory, no GPU): what the CPU tests drive')
+    ap.add_argument('--full', action='store_true', help='also measure the roofline, the sustained clocks, the `extra` configs and the CPU '
+                    'baseline (--no-extras / --no-cpu-baseline still drop theirs); a plain run times the headline step only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed step to DIR/<name>.npy (float32)')
     args = ap.parse_args()
     if args.overlap is None:
         args.overlap = 2
@@ -459,7 +482,7 @@ def main():
     # the process owns no stream but the default one: every further stream costs all of them (~5 % on these per-launch times with the two
     # replica streams alive), and the roofline is about the kernels, not about the schedule of batches.
     iso_profile = None
-    if rank == 0 and args.arch != 'resnet50':
+    if args.full and rank == 0 and args.arch != 'resnet50':
         from synergynet_amd import abi as _abi
         _lib = _abi.lib()
         t_w = time.perf_counter()
@@ -492,12 +515,12 @@ def main():
 
         def step():
             lo, mo = outs[ring._k % 2]
-            ring.submit(crops, rois, dense=not args.lmk_only, lmk_out=lo, mesh_out=mo)
+            return ring.submit(crops, rois, dense=not args.lmk_only, lmk_out=lo, mesh_out=mo)[:4]
     else:
         pipe = OverlappedPipeline(model, overlap=bool(args.overlap), rec_priority=args.rec_priority)
 
         def step():
-            pipe.submit(crops, rois, lmk_out=lmk, mesh_out=mesh, dense=not args.lmk_only)
+            return pipe.submit(crops, rois, lmk_out=lmk, mesh_out=mesh, dense=not args.lmk_only)
 
     t_pre, n_pre = time.perf_counter(), 0
     while time.perf_counter() - t_pre < args.prewarm:       # clock ramp of an idle GPU: untimed, before the contract's W warm-up steps
@@ -517,11 +540,13 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier()
     el = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last)
     sustained = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # sustained clocks: the same step for ~2 s, right here -- before any extra creates further HIP streams (they cost every stream)
         try:
             n2 = max(args.steps, int(2.0 / max(el / args.steps, 1e-4)))
@@ -545,7 +570,7 @@ def main():
     roof = None
     from synergynet_amd import abi
     lib = abi.lib()
-    if rank == 0 and args.arch == 'resnet50':
+    if args.full and rank == 0 and args.arch == 'resnet50':
         fl = lib.syn_resnet50_flops_per_face() * B
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
@@ -563,7 +588,7 @@ def main():
                     mfma_issue_tflops=round(3 * ach, 1), mfma_peak_fp16=PEAK_F16_MFMA_TFLOPS,
                     frac_of_fp32_mfma_peak=round(ach / PEAK_F32_MFMA_TFLOPS, 4),
                     flops_per_launch=fl, ms_per_launch=round(bb_ms, 4))
-    elif rank == 0:
+    elif args.full and rank == 0:
         feats, avg_ms, flops = iso_profile
         n = len(feats)
         fam = [i for i, f in enumerate(feats) if 2 <= f <= 17 or f >= 100]  # fused inverted-residual block launches (>= 100: a chain, 100 * first + last)
@@ -629,7 +654,7 @@ def main():
 
     # --- the other BASELINE configs and the reference-API variants of the headline step, briefly, on this box
     extra = None
-    if rank == 0 and world == 1 and not args.no_extras and args.arch == 'mobilenet_v2' and not args.lmk_only:
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.arch == 'mobilenet_v2' and not args.lmk_only:
         extra = {}
         sync = torch.cuda.synchronize
 
@@ -815,7 +840,7 @@ def main():
             out['distributed'] = dist_info
         if extra:
             out['extra'] = extra
-        if not args.no_cpu_baseline and world == 1 and args.arch == 'mobilenet_v2':
+        if args.full and not args.no_cpu_baseline and world == 1 and args.arch == 'mobilenet_v2':
             out['cpu_baseline'] = cpu_baseline(sd, pack)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + '\n').encode())

@@ -18,6 +18,8 @@ synthetic inputs:
   * FaceBoxes.models.faceboxes.FaceBoxesNet, utils.prior_box.PriorBox, utils.box_utils.decode, glued like
     FaceBoxes.__call__                              -> faceboxes_golden.npz (main_faceboxes)
   * benchmark_aflw2000.calc_nme / ana on seeded synthetic ground truth -> evaluate_golden.npz (main_evaluate)
+  * SynergyNet on fresh seeds + mobilenet_v2() state_dict keys -> reference_fresh_golden.npz (main_fresh_reference)
+  * the reference's C++ rasteriser on random meshes -> rasterize_ref_golden.npz (main_rasterize_ref)
 
 The assets themselves (9 MB of weights, 32 MB of basis) are NOT stored: they are
 regenerated bit-identically from the seeds in synergynet_amd/synth.py.  The dense
@@ -427,8 +429,64 @@ def main_write_obj():
     print('wrote', path, out['bytes_plain'].size, 'bytes of OBJ')
 
 
+FRESH_OFFSET, FRESH_STRIDE = 3, 13      # fresh-seed dense-mesh subset: vertices 3, 16, 29, ...
+
+
+def main_fresh_reference():
+    """The reference run live on seeds no other fixture uses (crops 555, parameters 556, tests/test_oracle_golden.py) plus the
+    state_dict keys of its own mobilenet_v2() (tests/test_host_cpu.py) -> reference_fresh_golden.npz.  The dense meshes are
+    stored as every FRESH_STRIDE-th vertex from FRESH_OFFSET (other vertices than reference_outputs.npz's subset) plus float64
+    per-row sums and sums of squares over all vertices."""
+    pack, sd = synth.make_3dmm(SEED_3DMM), synth.make_backbone_state(SEED_W)
+    ref, model = ref_loader.build_reference_model(pack, sd)
+    x = synth.normalize_crops(synth.make_crops(2, seed=555))
+    params = synth.make_params(3, seed=556, scale=1.5)
+    with torch.no_grad():
+        fwd = model.forward_test(torch.from_numpy(x)).numpy()
+        dense = model.reconstruct_vertex_62(torch.from_numpy(params), dense=True).numpy()
+    sys.path.insert(0, ref_loader.REF_ROOT)
+    try:
+        import importlib
+        m = importlib.import_module('backbone_nets.mobilenetv2_backbone')
+        keys = sorted(k for k in m.mobilenet_v2().state_dict() if not k.endswith('num_batches_tracked'))
+    finally:
+        sys.path.remove(ref_loader.REF_ROOT)
+    path = os.path.join(HERE, 'reference_fresh_golden.npz')
+    d64 = dense.astype(np.float64)
+    np.savez_compressed(path, seeds=np.array([SEED_W, SEED_3DMM]), forward_test=fwd, vert_offset=np.array(FRESH_OFFSET),
+                        vert_stride=np.array(FRESH_STRIDE), dense_sub=dense[:, :, FRESH_OFFSET::FRESH_STRIDE].copy(),
+                        dense_rowsum=d64.sum(axis=2), dense_rowsumsq=(d64 ** 2).sum(axis=2), mobilenet_v2_keys=np.array(keys))
+    print('wrote', path, os.path.getsize(path) // 1024, 'KB')
+
+
+def main_rasterize_ref():
+    """The reference's own C++ rasteriser (oracle/_ref/libsim3dr_ref.so, compiled from where it lies by oracle/Makefile) on random
+    meshes with degenerate and duplicate triangles and equal depths -> rasterize_ref_golden.npz: inputs and the reference's
+    normals and images, for tests/test_render_cpu.py's bit-identity test."""
+    from oracle import sim3dr as osim
+    osim.build()
+    assert osim.ref_available(), 'oracle/_ref not built'
+    rng = np.random.default_rng(5)
+    out = {}
+    for c, (nv, nt, hw) in enumerate(((300, 700, 64), (50, 400, 33), (4000, 9000, 128))):
+        v = rng.uniform(-10, hw + 10, (nv, 3)).astype(np.float32)
+        t = rng.integers(0, nv, (nt, 3)).astype(np.int32)
+        t[::7, 1] = t[::7, 0]                                       # degenerate (zero-area) triangles
+        t[5] = t[4]                                                 # duplicate triangle: first one wins ties
+        v[::11, 2] = v[0, 2]                                        # equal depths
+        col = rng.uniform(0, 1, (nv, 3)).astype(np.float32)
+        bg = rng.integers(0, 256, (hw, hw, 3), dtype=np.uint8)
+        out.update({f'c{c}_vertices': v, f'c{c}_triangles': t, f'c{c}_colors': col, f'c{c}_bg': bg,
+                    f'c{c}_normal': osim.get_normal(v, t, 'ref')})
+        for rev in (False, True):
+            out[f'c{c}_image_rev{int(rev)}'] = osim.rasterize(v, t, col, bg=bg.copy(), reverse=rev, impl='ref')
+    path = os.path.join(HERE, 'rasterize_ref_golden.npz')
+    np.savez_compressed(path, n_cases=np.array(3), **out)
+    print('wrote', path, os.path.getsize(path) // 1024, 'KB')
+
+
 if __name__ == '__main__':
-    if len(sys.argv) > 1:                      # python make_golden.py main_pose_mat main_faceboxes_real ...: only those fixtures
+    if len(sys.argv) > 1:                     # python make_golden.py main_pose_mat main_faceboxes_real ...: only those fixtures
         for name in sys.argv[1:]:
             globals()[name]()
         sys.exit(0)
@@ -440,3 +498,5 @@ if __name__ == '__main__':
     main_faceboxes_real()
     main_evaluate()
     main_write_obj()
+    main_fresh_reference()
+    main_rasterize_ref()

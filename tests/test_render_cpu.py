@@ -49,23 +49,16 @@ def test_restatement_matches_reference_golden_full_size(rgold):
     assert (overlap != img).any(2).mean() > 0.2                    # the two faces really cover the frame
 
 
-@pytest.mark.skipif(not osim.ref_available(), reason='oracle/_ref not built (no /root/reference on this machine)')
 def test_restatement_is_bit_identical_to_the_reference_cpp():
-    rng = np.random.default_rng(5)
-    for nv, nt, hw in ((300, 700, 64), (50, 400, 33), (4000, 9000, 128)):
-        v = rng.uniform(-10, hw + 10, (nv, 3)).astype(np.float32)
-        t = rng.integers(0, nv, (nt, 3)).astype(np.int32)
-        t[::7, 1] = t[::7, 0]                                       # degenerate (zero-area) triangles
-        t[5] = t[4]                                                 # duplicate triangle: first one wins ties
-        v[::11, 2] = v[0, 2]                                        # equal depths
-        a, b = osim.get_normal(v, t, 'oracle'), osim.get_normal(v, t, 'ref')
-        assert np.array_equal(a, b, equal_nan=True)
-        col = rng.uniform(0, 1, (nv, 3)).astype(np.float32)
-        bg = rng.integers(0, 256, (hw, hw, 3), dtype=np.uint8)
+    """Random meshes with degenerate and duplicate triangles and equal depths: normals and images equal, bit for bit, to what the
+    reference's own C++ computed on them (rasterize_ref_golden.npz, make_golden.py main_rasterize_ref)."""
+    g = np.load(os.path.join(HERE, 'golden', 'rasterize_ref_golden.npz'))
+    for c in range(int(g['n_cases'])):
+        v, t, col, bg = (g[f'c{c}_{k}'] for k in ('vertices', 'triangles', 'colors', 'bg'))
+        assert np.array_equal(osim.get_normal(v, t, 'oracle'), g[f'c{c}_normal'], equal_nan=True)
         for rev in (False, True):
             ia = osim.rasterize(v, t, col, bg=bg.copy(), reverse=rev, impl='oracle')
-            ib = osim.rasterize(v, t, col, bg=bg.copy(), reverse=rev, impl='ref')
-            assert np.array_equal(ia, ib)
+            assert np.array_equal(ia, g[f'c{c}_image_rev{int(rev)}'])
 
 
 def test_isolated_vertices_get_nan_normals_like_the_reference():

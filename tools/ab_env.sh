@@ -9,7 +9,7 @@ for v in "" "$@" ""; do
   unset SYNERGY_HIP_LIB; envs=""
   case "$v" in "") ;; *=*) envs="$v";; *) export SYNERGY_HIP_LIB=$R/synergynet_amd/libsynergy_hip_$v.so;; esac
   echo "== ${v:-default}" >> $out
-  env $envs python $R/bench.py --steps 100 --no-cpu-baseline --no-extras $extra 2>/dev/null | python -c "
+  env $envs python $R/bench.py --full --steps 100 --no-cpu-baseline --no-extras $extra 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; out=$R/gpurun_out/ab_perlaunch.txt; : > $out
 for tag in "" "$@" ""; do
   if [ -n "$tag" ]; then export SYNERGY_HIP_LIB=$R/synergynet_amd/libsynergy_hip_$tag.so; else unset SYNERGY_HIP_LIB; fi
   echo "== ${tag:-default}" >> $out
-  python $R/bench.py --steps 100 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+  python $R/bench.py --full --steps 100 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -6,7 +6,7 @@ import subprocess
 import sys
 
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = subprocess.run([sys.executable, os.path.join(R, 'bench.py'), '--no-cpu-baseline', '--no-extras'] + sys.argv[1:], capture_output=True, text=True)
+out = subprocess.run([sys.executable, os.path.join(R, 'bench.py'), '--full', '--no-cpu-baseline', '--no-extras'] + sys.argv[1:], capture_output=True, text=True)
 try:
     d = json.loads(out.stdout.strip().splitlines()[-1])
     r = d['roofline']

@@ -5,7 +5,7 @@
 #   wait counters, and the per-stage s_memtime tables of the fused blocks.
 tag=$1
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/round_$tag; mkdir -p $O
-python $R/bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-300 $O/bench.json
+python $R/bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-300 $O/bench.json
 SYN_BENCH_FORCE_DIST=1 NCCL_DEBUG=INFO python $R/bench.py --no-cpu-baseline --no-extras > $O/bench_force_dist.json 2> $O/bench_force_dist.log; echo "force-dist rc=$?"
 python $R/tools/stage_profile.py 1024 > $O/stage_profile_b1024.txt 2>&1; echo "stage rc=$?"
 cd /tmp && export TMPDIR=/tmp
