@@ -244,6 +244,43 @@ int syn_rasterize(syn_handle *h, const float *vertices, const float *colors, int
 int syn_add_weighted(syn_handle *h, const uint8_t *a, float alpha, const uint8_t *b, float beta, uint8_t *out,
                      size_t n, void *stream);
 
+/* ---- textured meshes: what the reference's texture demos do with a mesh (uv_texture_realFaces.py:45-51,96-116, artistic.py:44-49,111-117) ----
+ * syn_load_uv_map: the UV assets, once per handle (HOST int32 arrays).
+ *   coord_u, coord_v [nver]: pixel row / column of every vertex in the UV texture image, (uv[:,1]*255.0).astype(int32) and
+ *     (uv[:,0]*255.0).astype(int32) of 3dmm_data/BFM_UV.npy -- the caller evaluates them in the asset's own dtype (:48-49);
+ *   keep_ind [n_keep]: the kept vertex subset (keptInd.npy), indices into the nver vertices;
+ *   tri_kept [ntri_kept,3]: 0-based topology of the KEPT vertex list (deletedTri.npy is 1-based [3,ntri]: pass its transpose - 1).
+ * The kept topology goes into a second topology slot with its own adjacency, next to the one syn_load_triangles holds, so a
+ * caller that alternates full-mesh and textured renders re-uploads neither.  Index ranges are validated like syn_load_triangles. */
+int syn_load_uv_map(syn_handle *h, const int32_t *coord_u, const int32_t *coord_v, int nver, const int32_t *keep_ind, int n_keep,
+                    const int32_t *tri_kept, int ntri_kept);
+
+/* Which topology syn_mesh_shade, syn_mesh_shade_textured and syn_rasterize work on from now on: 0 = syn_load_triangles' (the
+ * default, and what every syn_load_triangles call selects), 1 = the kept topology of syn_load_uv_map (vertex count n_keep).
+ * SYN_ERR_NOT_LOADED when that slot is empty. */
+int syn_select_topology(syn_handle *h, int slot);
+
+/* np.flip(img, axis=0)[coord_u, coord_v, :] (uv_texture_realFaces.py:109-110) for T texture images in one launch.
+ * uv_tex: device uint8 [T,tex_h,tex_w,channels] (channels <= 4); kept != 0: one colour per kept vertex (n = n_keep, vertex keep_ind[k]),
+ * else per vertex (n = nver); out: device float32 [T,n,channels], out[t,k,:] = uv_tex[t, tex_h-1-coord_u[v], coord_v[v], :] as
+ * 0..255 (normalize = 0, what the coloured OBJ takes, :113) or divided by 255.0f (one IEEE division, :115).
+ * SYN_ERR_INVALID when the texture is smaller than the table needs. */
+int syn_uv_colors(syn_handle *h, const uint8_t *uv_tex, int T, int tex_h, int tex_w, int channels, int kept, int normalize, float *out,
+                  void *stream);
+
+/* vertices[:, keep_ind] (uv_texture_realFaces.py:98) for F meshes: vertices device [F,3,nver] (planar = 1) or the pitched
+ * [F,3,p][:, :, :nver] (planar = p >= nver) read in place; out device [F,3,n_keep] packed. */
+int syn_gather_vertices(syn_handle *h, const float *vertices, int F, int planar, float *out, void *stream);
+
+/* syn_mesh_shade with `texture *= light` (Sim3DR/lighting.py:68-70) in the lighting kernel's epilogue, on the selected topology.
+ * vertices, planar, cfg16, normal as syn_mesh_shade; light: device [F,nver,3] or NULL; colors: device [F,nver,3], what syn_rasterize draws.
+ * shared = 0: tex device [F,nver,3], colors[f] = tex[f] * light[f] (colors may be tex itself).
+ * shared = 1: tex device [nver,3], ONE array multiplied in place face after face as the reference does when utils/render.py:39-42
+ *   hands the same array to every call: colors[f] = ((tex * light[0]) * light[1]) ... * light[f] in float32, left to right, and tex
+ *   holds the last product afterwards. */
+int syn_mesh_shade_textured(syn_handle *h, const float *vertices, int F, int planar, const float *cfg16, float *normal, float *light,
+                            float *tex, int shared, float *colors, void *stream);
+
 /* ---- FaceBoxes face detector: the boxes get_all_outputs crops (synergy3DMM.py:169-171) ----
  * syn_detector_flat_count / syn_load_detector: FaceBoxesNet's state_dict (FaceBoxes/models/faceboxes.py:64-114) flattened in
  * forward order -- conv1, conv2, inception{1,2,3}.{branch1x1, branch1x1_2, branch3x3_reduce, branch3x3, branch3x3_reduce_2,

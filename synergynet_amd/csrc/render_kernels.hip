@@ -3,6 +3,8 @@
 //   RenderPipeline      (Sim3DR/lighting.py:37-71)                   ambient + diffuse + specular vertex colours
 //   Sim3DR.rasterize    (Sim3DR/lib/rasterize_kernel.cpp:219-287)  z-buffer rasteriser, barycentric colours
 //   cv2.addWeighted     (utils/render.py:45)                         alpha overlay
+//   textured meshes     (uv_texture_realFaces.py:45-51,96-116, lighting.py:68-70): UV colour lookup, kept-vertex gather,
+//                       texture * light in the lighting epilogue
 // The reference walks the 105 840 triangles one at a time on the host.  Here every stage is data parallel and still
 // reproduces the sequential result BIT FOR BIT (tests/test_gpu_render.py):
 //   * arithmetic is plain IEEE single precision in the reference's operation order -- FMA contraction is switched off for
@@ -103,11 +105,10 @@ __global__ __launch_bounds__(1024) void minmax_kernel(const float *__restrict__ 
 // ---- Phong vertex colours (lighting.py:37-71 with norm_vertices :9-14), one thread per (face, vertex) ----
 // cfg: [0] intensity_ambient [1..3] color_ambient [4] intensity_directional [5..7] color_directional
 //      [8] intensity_specular [9] specular_exp(int) [10..12] light_pos [13..15] view_pos
-__global__ __launch_bounds__(256) void lighting_kernel(const float *__restrict__ vertices, const float *__restrict__ normal,
-                                                       const unsigned *__restrict__ mm, const float *__restrict__ cfg,
-                                                       float *__restrict__ light, int nver, int planar) {
-    const int i = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
-    if (i >= nver) return;
+namespace {
+__device__ __forceinline__ void phong_vertex(const float *__restrict__ vertices, const float *__restrict__ normal,
+                                             const unsigned *__restrict__ mm, const float *__restrict__ cfg, int nver, int planar,
+                                             int f, int i, float out[3]) {
     auto unkey = [](unsigned k) { const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; return __builtin_bit_cast(float, u); };
     const unsigned *m = mm + f * 6;
     const float *v = vertices + (size_t)f * face_stride(planar, nver);
@@ -151,8 +152,84 @@ __global__ __launch_bounds__(256) void lighting_kernel(const float *__restrict__
             for (int c = 0; c < 3; ++c) l[c] += (cfg[8] * cfg[5 + c]) * sc2;
         }
     }
+    for (int c = 0; c < 3; ++c) out[c] = (l[c] != l[c]) ? l[c] : fminf(fmaxf(l[c], 0.0f), 1.0f);
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void lighting_kernel(const float *__restrict__ vertices, const float *__restrict__ normal,
+                                                       const unsigned *__restrict__ mm, const float *__restrict__ cfg,
+                                                       float *__restrict__ light, int nver, int planar) {
+    const int i = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    if (i >= nver) return;
+    float l[3];
+    phong_vertex(vertices, normal, mm, cfg, nver, planar, f, i, l);
     float *o = light + ((size_t)f * nver + i) * 3;
-    for (int c = 0; c < 3; ++c) o[c] = (l[c] != l[c]) ? l[c] : fminf(fmaxf(l[c], 0.0f), 1.0f);
+    for (int c = 0; c < 3; ++c) o[c] = l[c];
+}
+
+// ---- textured vertex colours (lighting.py:68-70: `texture *= light`), the product in the lighting epilogue ----
+// Per-face textures [F,nver,3]: colours[f] = tex[f] * light[f], one thread per (face, vertex).  colours may alias tex.
+__global__ __launch_bounds__(256) void lighting_tex_kernel(const float *__restrict__ vertices, const float *__restrict__ normal,
+                                                           const unsigned *__restrict__ mm, const float *__restrict__ cfg,
+                                                           float *light, const float *tex, float *colors, int nver, int planar) {
+    const int i = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    if (i >= nver) return;
+    float l[3];
+    phong_vertex(vertices, normal, mm, cfg, nver, planar, f, i, l);
+    const size_t o = ((size_t)f * nver + i) * 3;
+    for (int c = 0; c < 3; ++c) {
+        const float t = tex[o + c];
+        if (light) light[o + c] = l[c];
+        colors[o + c] = t * l[c];
+    }
+}
+
+// One shared texture [nver,3]: the reference multiplies the caller's array in place once per face (utils/render.py:39-42 hands
+// the same array to every call), so face f is drawn with ((tex * l0) * l1) ... * lf.  One thread per vertex walks the faces in
+// order; the last product goes back into tex.
+__global__ __launch_bounds__(256) void lighting_tex_shared_kernel(const float *__restrict__ vertices, const float *__restrict__ normal,
+                                                                  const unsigned *__restrict__ mm, const float *__restrict__ cfg,
+                                                                  float *light, float *tex, float *colors, int F, int nver,
+                                                                  int planar) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nver) return;
+    float t[3];
+    for (int c = 0; c < 3; ++c) t[c] = tex[(size_t)i * 3 + c];
+    for (int f = 0; f < F; ++f) {
+        float l[3];
+        phong_vertex(vertices, normal, mm, cfg, nver, planar, f, i, l);
+        const size_t o = ((size_t)f * nver + i) * 3;
+        for (int c = 0; c < 3; ++c) {
+            t[c] = t[c] * l[c];
+            if (light) light[o + c] = l[c];
+            colors[o + c] = t[c];
+        }
+    }
+    for (int c = 0; c < 3; ++c) tex[(size_t)i * 3 + c] = t[c];
+}
+
+// ---- UV colour lookup (uv_texture_realFaces.py:48-49,109-115): np.flip(img, 0)[coord_u, coord_v, :] per (texture, vertex) ----
+// uv_tex uint8 [T,th,tw,ch]; keep == nullptr: every vertex, else vertex keep[k]; out float32 [T,n,ch], raw 0..255 or / 255.0f.
+__global__ __launch_bounds__(256) void uv_colors_kernel(const unsigned char *__restrict__ uv_tex, const int *__restrict__ coord_u,
+                                                        const int *__restrict__ coord_v, const int *__restrict__ keep,
+                                                        float *__restrict__ out, int n, int th, int tw, int ch, int normalize) {
+    const int k = blockIdx.x * 256 + threadIdx.x, t = blockIdx.y;
+    if (k >= n) return;
+    const int v = keep ? keep[k] : k;
+    const unsigned char *src = uv_tex + (((size_t)t * th + (th - 1 - coord_u[v])) * tw + coord_v[v]) * ch;
+    float *o = out + ((size_t)t * n + k) * ch;
+    for (int q = 0; q < ch; ++q) {
+        const float x = (float)src[q];
+        o[q] = normalize ? x / 255.0f : x;
+    }
+}
+
+// ---- kept-vertex gather (vertices[:, keep_ind], uv_texture_realFaces.py:98): [F,3,pitch][:, :, :nver] -> [F,3,n_keep] ----
+__global__ __launch_bounds__(256) void gather_vertices_kernel(const float *__restrict__ vertices, const int *__restrict__ keep,
+                                                              float *__restrict__ out, int n_keep, int pitch) {
+    const int k = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;           // row = face * 3 + coordinate
+    if (k >= n_keep) return;
+    out[(size_t)row * n_keep + k] = vertices[(size_t)row * pitch + keep[k]];
 }
 
 namespace {
@@ -251,6 +328,23 @@ void launch_mesh_normals(const float *vertices, const int *tri, const int *adj_o
 void launch_mesh_lighting(const float *vertices, const float *normal, const unsigned *mm, const float *cfg, float *light, int F,
                           int nver, int planar, hipStream_t s) {
     lighting_kernel<<<dim3((nver + 255) / 256, F), 256, 0, s>>>(vertices, normal, mm, cfg, light, nver, planar);
+}
+
+void launch_mesh_lighting_tex(const float *vertices, const float *normal, const unsigned *mm, const float *cfg, float *light,
+                              float *tex, int shared, float *colors, int F, int nver, int planar, hipStream_t s) {
+    if (shared)
+        lighting_tex_shared_kernel<<<(nver + 255) / 256, 256, 0, s>>>(vertices, normal, mm, cfg, light, tex, colors, F, nver, planar);
+    else
+        lighting_tex_kernel<<<dim3((nver + 255) / 256, F), 256, 0, s>>>(vertices, normal, mm, cfg, light, tex, colors, nver, planar);
+}
+
+void launch_uv_colors(const unsigned char *uv_tex, const int *coord_u, const int *coord_v, const int *keep, float *out, int T, int n,
+                      int th, int tw, int ch, int normalize, hipStream_t s) {
+    uv_colors_kernel<<<dim3((n + 255) / 256, T), 256, 0, s>>>(uv_tex, coord_u, coord_v, keep, out, n, th, tw, ch, normalize);
+}
+
+void launch_gather_vertices(const float *vertices, const int *keep, float *out, int F, int n_keep, int pitch, hipStream_t s) {
+    gather_vertices_kernel<<<dim3((n_keep + 255) / 256, 3 * F), 256, 0, s>>>(vertices, keep, out, n_keep, pitch);
 }
 
 void launch_rasterize(const float *vertices, const int *tri, const float *colors, unsigned long long *zkey, unsigned char *image,

@@ -267,6 +267,14 @@ void launch_mesh_normals(const float *vertices, const int *tri, const int *adj_o
                          int ntri, int planar, hipStream_t s);
 void launch_mesh_lighting(const float *vertices, const float *normal, const unsigned *mm, const float *cfg /*16 floats, device*/,
                           float *light /*[F,nver,3]*/, int F, int nver, int planar, hipStream_t s);
+// textured meshes: light computed as above, colours = tex * light (shared != 0: one [nver,3] texture multiplied in place face after
+// face, lighting.py:69 through utils/render.py:39-42); light may be NULL
+void launch_mesh_lighting_tex(const float *vertices, const float *normal, const unsigned *mm, const float *cfg, float *light,
+                              float *tex, int shared, float *colors /*[F,nver,3]*/, int F, int nver, int planar, hipStream_t s);
+void launch_uv_colors(const unsigned char *uv_tex /*[T,th,tw,ch]*/, const int *coord_u, const int *coord_v, const int *keep /*nullable*/,
+                      float *out /*[T,n,ch]*/, int T, int n, int th, int tw, int ch, int normalize, hipStream_t s);
+void launch_gather_vertices(const float *vertices /*[F*3] rows `pitch` apart*/, const int *keep, float *out /*[F,3,n_keep]*/, int F,
+                            int n_keep, int pitch, hipStream_t s);
 void launch_rasterize(const float *vertices, const int *tri, const float *colors /*[F,nver,c]*/, unsigned long long *zkey /*[h*w]*/,
                       unsigned char *image /*[h,w,c] in place*/, int F, int nver, int ntri, int h, int w, int c, int planar,
                       int reverse, hipStream_t s);

@@ -309,6 +309,13 @@ struct syn_handle {
     // mesh topology + render scratch (syn_load_triangles / syn_mesh_* / syn_rasterize)
     int *d_tri = nullptr, *d_adj_off = nullptr, *d_adj_tri = nullptr;
     int ntri = 0, tri_nver = 0;
+    // textured meshes (syn_load_uv_map): UV pixel tables over all vertices, the kept-vertex list and a second topology slot
+    // for the kept mesh with its own adjacency; topo_slot = which of the two syn_mesh_shade* / syn_rasterize read
+    int *d_uv = nullptr;           // coord_u [uv_nver] | coord_v [uv_nver] | keep_ind [n_keep]
+    int uv_nver = 0, n_keep = 0, uv_max[4] = {0, 0, 0, 0};      // max coord_u, coord_v over all vertices | over the kept ones
+    int *k_tri = nullptr, *k_adj_off = nullptr, *k_adj_tri = nullptr;
+    int k_ntri = 0;
+    int topo_slot = 0;
     void *rws = nullptr;           // render scratch: tri normals | min/max keys | z keys
     size_t rws_bytes = 0;
     // FaceBoxes detector: packed weights + per-frame scratch (syn_load_detector / syn_detect)
@@ -940,6 +947,10 @@ int syn_destroy(syn_handle *h) {
     if (h->d_tri) (void)hipFree(h->d_tri);
     if (h->d_adj_off) (void)hipFree(h->d_adj_off);
     if (h->d_adj_tri) (void)hipFree(h->d_adj_tri);
+    if (h->d_uv) (void)hipFree(h->d_uv);
+    if (h->k_tri) (void)hipFree(h->k_tri);
+    if (h->k_adj_off) (void)hipFree(h->k_adj_off);
+    if (h->k_adj_tri) (void)hipFree(h->k_adj_tri);
     if (h->rws) (void)hipFree(h->rws);
     if (h->d_det) (void)hipFree(h->d_det);
     if (h->dws) (void)hipFree(h->dws);
@@ -2352,54 +2363,154 @@ int ensure_rws(syn_handle *h, size_t bytes) {
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 }  // namespace
 
-int syn_load_triangles(syn_handle *h, const int32_t *tri, int ntri, int nver) {
-    if (!h || !tri || ntri <= 0 || nver <= 0) return fail(SYN_ERR_INVALID, "syn_load_triangles: bad argument");
-    if (ntri >= (1 << 24)) return fail(SYN_ERR_INVALID, "syn_load_triangles: ntri=%d exceeds the 24-bit z-key field", ntri);
-    for (int i = 0; i < 3 * ntri; ++i)
-        if (tri[i] < 0 || tri[i] >= nver) return fail(SYN_ERR_INVALID, "syn_load_triangles: tri[%d]=%d out of range", i, tri[i]);
-    // CSR of incident triangles per vertex in ascending triangle order, corner order inside a triangle: exactly the order
-    // in which the reference's sequential loop adds triangle normals to a vertex (rasterize_kernel.cpp:187-198)
+namespace {
+// Uploads a topology ([ntri,3], indices already validated) with the CSR of incident triangles per vertex in ascending triangle
+// order, corner order inside a triangle: exactly the order in which the reference's sequential loop adds triangle normals to
+// a vertex (rasterize_kernel.cpp:187-198)
+int upload_topology(syn_handle *h, const int32_t *tri, int ntri, int nver, int **d_tri, int **d_adj_off, int **d_adj_tri) {
     std::vector<int> off(nver + 1, 0), adj(3 * (size_t)ntri);
     for (int i = 0; i < 3 * ntri; ++i) off[tri[i] + 1]++;
     for (int v = 0; v < nver; ++v) off[v + 1] += off[v];
     std::vector<int> cur(off.begin(), off.end() - 1);
     for (int t = 0; t < ntri; ++t)
         for (int j = 0; j < 3; ++j) adj[cur[tri[3 * t + j]]++] = t;
+    if (*d_tri) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(*d_tri); (void)hipFree(*d_adj_off); (void)hipFree(*d_adj_tri); *d_tri = *d_adj_off = *d_adj_tri = nullptr; }
+    HIP_TRY(hipMalloc((void **)d_tri, sizeof(int) * 3 * (size_t)ntri));
+    HIP_TRY(hipMalloc((void **)d_adj_off, sizeof(int) * (nver + 1)));
+    HIP_TRY(hipMalloc((void **)d_adj_tri, sizeof(int) * 3 * (size_t)ntri));
+    HIP_TRY(hipMemcpy(*d_tri, tri, sizeof(int) * 3 * (size_t)ntri, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(*d_adj_off, off.data(), sizeof(int) * (nver + 1), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(*d_adj_tri, adj.data(), sizeof(int) * 3 * (size_t)ntri, hipMemcpyHostToDevice));
+    return SYN_OK;
+}
+struct Topo { const int *tri, *adj_off, *adj_tri; int ntri, nver; };
+// the topology syn_mesh_shade* / syn_rasterize work on (syn_select_topology); tri == nullptr: not loaded
+Topo current_topo(const syn_handle *h) {
+    if (h->topo_slot == 1) return Topo{h->k_tri, h->k_adj_off, h->k_adj_tri, h->k_ntri, h->n_keep};
+    return Topo{h->d_tri, h->d_adj_off, h->d_adj_tri, h->ntri, h->tri_nver};
+}
+}  // namespace
+
+int syn_load_triangles(syn_handle *h, const int32_t *tri, int ntri, int nver) {
+    if (!h || !tri || ntri <= 0 || nver <= 0) return fail(SYN_ERR_INVALID, "syn_load_triangles: bad argument");
+    if (ntri >= (1 << 24)) return fail(SYN_ERR_INVALID, "syn_load_triangles: ntri=%d exceeds the 24-bit z-key field", ntri);
+    for (int i = 0; i < 3 * ntri; ++i)
+        if (tri[i] < 0 || tri[i] >= nver) return fail(SYN_ERR_INVALID, "syn_load_triangles: tri[%d]=%d out of range", i, tri[i]);
     DeviceGuard g(h->device);
-    if (h->d_tri) { (void)hipFree(h->d_tri); (void)hipFree(h->d_adj_off); (void)hipFree(h->d_adj_tri); h->d_tri = h->d_adj_off = h->d_adj_tri = nullptr; }
-    HIP_TRY(hipMalloc((void **)&h->d_tri, sizeof(int) * 3 * (size_t)ntri));
-    HIP_TRY(hipMalloc((void **)&h->d_adj_off, sizeof(int) * (nver + 1)));
-    HIP_TRY(hipMalloc((void **)&h->d_adj_tri, sizeof(int) * 3 * (size_t)ntri));
-    HIP_TRY(hipMemcpy(h->d_tri, tri, sizeof(int) * 3 * (size_t)ntri, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_adj_off, off.data(), sizeof(int) * (nver + 1), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->d_adj_tri, adj.data(), sizeof(int) * 3 * (size_t)ntri, hipMemcpyHostToDevice));
+    int rc = upload_topology(h, tri, ntri, nver, &h->d_tri, &h->d_adj_off, &h->d_adj_tri);
+    if (rc) { h->ntri = h->tri_nver = 0; return rc; }
     h->ntri = ntri; h->tri_nver = nver;
+    h->topo_slot = 0;
     return SYN_OK;
 }
 
-int syn_mesh_shade(syn_handle *h, const float *vertices, int F, int planar, const float *cfg16, float *normal, float *light,
-                   void *stream) {
-    if (!h || !vertices || !normal) return fail(SYN_ERR_INVALID, "syn_mesh_shade: NULL argument");
-    if (F <= 0) return fail(SYN_ERR_INVALID, "syn_mesh_shade: F=%d", F);
-    if (light && !cfg16) return fail(SYN_ERR_INVALID, "syn_mesh_shade: light requested without a lighting configuration");
-    if (!h->d_tri) return fail(SYN_ERR_NOT_LOADED, "syn_mesh_shade: triangles not loaded");
-    if (planar < 0 || (planar > 1 && planar < h->tri_nver)) return fail(SYN_ERR_INVALID, "syn_mesh_shade: planar=%d (0, 1 or a row pitch >= %d)", planar, h->tri_nver);
-    if (planar == 1) planar = h->tri_nver;
+int syn_load_uv_map(syn_handle *h, const int32_t *coord_u, const int32_t *coord_v, int nver, const int32_t *keep_ind, int n_keep,
+                    const int32_t *tri_kept, int ntri_kept) {
+    if (!h || !coord_u || !coord_v || !keep_ind || !tri_kept || nver <= 0 || n_keep <= 0 || ntri_kept <= 0)
+        return fail(SYN_ERR_INVALID, "syn_load_uv_map: bad argument");
+    if (ntri_kept >= (1 << 24)) return fail(SYN_ERR_INVALID, "syn_load_uv_map: ntri_kept=%d exceeds the 24-bit z-key field", ntri_kept);
+    int mx[4] = {0, 0, 0, 0};
+    for (int i = 0; i < nver; ++i) {
+        if (coord_u[i] < 0 || coord_v[i] < 0) return fail(SYN_ERR_INVALID, "syn_load_uv_map: negative UV pixel (%d, %d) at vertex %d", coord_u[i], coord_v[i], i);
+        mx[0] = std::max(mx[0], (int)coord_u[i]); mx[1] = std::max(mx[1], (int)coord_v[i]);
+    }
+    for (int k = 0; k < n_keep; ++k) {
+        if (keep_ind[k] < 0 || keep_ind[k] >= nver) return fail(SYN_ERR_INVALID, "syn_load_uv_map: keep_ind[%d]=%d out of range", k, keep_ind[k]);
+        mx[2] = std::max(mx[2], (int)coord_u[keep_ind[k]]); mx[3] = std::max(mx[3], (int)coord_v[keep_ind[k]]);
+    }
+    for (int i = 0; i < 3 * ntri_kept; ++i)
+        if (tri_kept[i] < 0 || tri_kept[i] >= n_keep) return fail(SYN_ERR_INVALID, "syn_load_uv_map: tri_kept[%d]=%d out of range", i, tri_kept[i]);
     DeviceGuard g(h->device);
-    const size_t tn = align256(sizeof(float) * 3 * (size_t)h->ntri * F), mmb = align256(sizeof(unsigned) * 6 * F + 64);
+    if (h->d_uv) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(h->d_uv); h->d_uv = nullptr; }
+    h->uv_nver = h->n_keep = h->k_ntri = 0;
+    if (h->topo_slot == 1) h->topo_slot = 0;
+    HIP_TRY(hipMalloc((void **)&h->d_uv, sizeof(int) * (2 * (size_t)nver + n_keep)));
+    HIP_TRY(hipMemcpy(h->d_uv, coord_u, sizeof(int) * nver, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_uv + nver, coord_v, sizeof(int) * nver, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_uv + 2 * (size_t)nver, keep_ind, sizeof(int) * n_keep, hipMemcpyHostToDevice));
+    int rc = upload_topology(h, tri_kept, ntri_kept, n_keep, &h->k_tri, &h->k_adj_off, &h->k_adj_tri);
+    if (rc) return rc;
+    h->uv_nver = nver; h->n_keep = n_keep; h->k_ntri = ntri_kept;
+    for (int i = 0; i < 4; ++i) h->uv_max[i] = mx[i];
+    return SYN_OK;
+}
+
+int syn_select_topology(syn_handle *h, int slot) {
+    if (!h || (slot != 0 && slot != 1)) return fail(SYN_ERR_INVALID, "syn_select_topology: slot must be 0 (syn_load_triangles) or 1 (syn_load_uv_map)");
+    if (slot == 1 && !h->k_ntri) return fail(SYN_ERR_NOT_LOADED, "syn_select_topology: UV map not loaded");
+    if (slot == 0 && !h->d_tri) return fail(SYN_ERR_NOT_LOADED, "syn_select_topology: triangles not loaded");
+    h->topo_slot = slot;
+    return SYN_OK;
+}
+
+int syn_uv_colors(syn_handle *h, const uint8_t *uv_tex, int T, int tex_h, int tex_w, int channels, int kept, int normalize, float *out,
+                  void *stream) {
+    if (!h || !uv_tex || !out) return fail(SYN_ERR_INVALID, "syn_uv_colors: NULL argument");
+    if (T <= 0 || tex_h <= 0 || tex_w <= 0 || channels <= 0 || channels > 4)
+        return fail(SYN_ERR_INVALID, "syn_uv_colors: T=%d tex_h=%d tex_w=%d channels=%d", T, tex_h, tex_w, channels);
+    if (!h->d_uv || !h->uv_nver) return fail(SYN_ERR_NOT_LOADED, "syn_uv_colors: UV map not loaded");
+    const int mu = h->uv_max[kept ? 2 : 0], mv = h->uv_max[kept ? 3 : 1];
+    if (tex_h <= mu || tex_w <= mv)
+        return fail(SYN_ERR_INVALID, "syn_uv_colors: a %d x %d texture is smaller than the UV table needs (%d x %d)", tex_h, tex_w, mu + 1, mv + 1);
+    DeviceGuard g(h->device);
+    syn::launch_uv_colors(uv_tex, h->d_uv, h->d_uv + h->uv_nver, kept ? h->d_uv + 2 * (size_t)h->uv_nver : nullptr, out, T,
+                          kept ? h->n_keep : h->uv_nver, tex_h, tex_w, channels, normalize, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+int syn_gather_vertices(syn_handle *h, const float *vertices, int F, int planar, float *out, void *stream) {
+    if (!h || !vertices || !out) return fail(SYN_ERR_INVALID, "syn_gather_vertices: NULL argument");
+    if (F <= 0) return fail(SYN_ERR_INVALID, "syn_gather_vertices: F=%d", F);
+    if (!h->d_uv || !h->n_keep) return fail(SYN_ERR_NOT_LOADED, "syn_gather_vertices: UV map not loaded");
+    if (planar < 1 || (planar > 1 && planar < h->uv_nver))
+        return fail(SYN_ERR_INVALID, "syn_gather_vertices: planar=%d (1 or a row pitch >= %d)", planar, h->uv_nver);
+    if (planar == 1) planar = h->uv_nver;
+    DeviceGuard g(h->device);
+    syn::launch_gather_vertices(vertices, h->d_uv + 2 * (size_t)h->uv_nver, out, F, h->n_keep, planar, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+namespace {
+int mesh_shade_impl(const char *who, syn_handle *h, const float *vertices, int F, int planar, const float *cfg16, float *normal,
+                    float *light, float *tex, int shared, float *colors, void *stream) {
+    const Topo T = current_topo(h);
+    if (!T.tri) return fail(SYN_ERR_NOT_LOADED, "%s: triangles not loaded", who);
+    if (planar < 0 || (planar > 1 && planar < T.nver)) return fail(SYN_ERR_INVALID, "%s: planar=%d (0, 1 or a row pitch >= %d)", who, planar, T.nver);
+    if (planar == 1) planar = T.nver;
+    DeviceGuard g(h->device);
+    const size_t tn = align256(sizeof(float) * 3 * (size_t)T.ntri * F), mmb = align256(sizeof(unsigned) * 6 * F + 64);
     int rc = ensure_rws(h, tn + mmb);
     if (rc) return rc;
     float *tri_normal = (float *)h->rws;
     unsigned *mm = (unsigned *)((char *)h->rws + tn);
     float *d_cfg = (float *)(mm + 6 * F);            // 16 floats right behind the keys (inside the 64-byte tail)
     hipStream_t s = (hipStream_t)stream;
-    syn::launch_mesh_normals(vertices, h->d_tri, h->d_adj_off, h->d_adj_tri, tri_normal, normal, mm, F, h->tri_nver, h->ntri, planar, s);
-    if (light) {
+    syn::launch_mesh_normals(vertices, T.tri, T.adj_off, T.adj_tri, tri_normal, normal, mm, F, T.nver, T.ntri, planar, s);
+    if (light || colors) {
         HIP_TRY(hipMemcpyAsync(d_cfg, cfg16, 16 * sizeof(float), hipMemcpyHostToDevice, s));
-        syn::launch_mesh_lighting(vertices, normal, mm, d_cfg, light, F, h->tri_nver, planar, s);
+        if (colors) syn::launch_mesh_lighting_tex(vertices, normal, mm, d_cfg, light, tex, shared, colors, F, T.nver, planar, s);
+        else syn::launch_mesh_lighting(vertices, normal, mm, d_cfg, light, F, T.nver, planar, s);
     }
     HIP_TRY(hipGetLastError());
     return SYN_OK;
+}
+}  // namespace
+
+int syn_mesh_shade(syn_handle *h, const float *vertices, int F, int planar, const float *cfg16, float *normal, float *light,
+                   void *stream) {
+    if (!h || !vertices || !normal) return fail(SYN_ERR_INVALID, "syn_mesh_shade: NULL argument");
+    if (F <= 0) return fail(SYN_ERR_INVALID, "syn_mesh_shade: F=%d", F);
+    if (light && !cfg16) return fail(SYN_ERR_INVALID, "syn_mesh_shade: light requested without a lighting configuration");
+    return mesh_shade_impl("syn_mesh_shade", h, vertices, F, planar, cfg16, normal, light, nullptr, 0, nullptr, stream);
+}
+
+int syn_mesh_shade_textured(syn_handle *h, const float *vertices, int F, int planar, const float *cfg16, float *normal, float *light,
+                            float *tex, int shared, float *colors, void *stream) {
+    if (!h || !vertices || !normal || !cfg16 || !tex || !colors) return fail(SYN_ERR_INVALID, "syn_mesh_shade_textured: NULL argument");
+    if (F <= 0) return fail(SYN_ERR_INVALID, "syn_mesh_shade_textured: F=%d", F);
+    return mesh_shade_impl("syn_mesh_shade_textured", h, vertices, F, planar, cfg16, normal, light, tex, shared != 0, colors, stream);
 }
 
 int syn_rasterize(syn_handle *h, const float *vertices, const float *colors, int F, int planar, int channels, uint8_t *image,
@@ -2407,13 +2518,14 @@ int syn_rasterize(syn_handle *h, const float *vertices, const float *colors, int
     if (!h || !vertices || !colors || !image) return fail(SYN_ERR_INVALID, "syn_rasterize: NULL argument");
     if (F <= 0 || F > 254 || H <= 0 || W <= 0 || channels <= 0 || channels > 4)
         return fail(SYN_ERR_INVALID, "syn_rasterize: F=%d H=%d W=%d channels=%d", F, H, W, channels);
-    if (!h->d_tri) return fail(SYN_ERR_NOT_LOADED, "syn_rasterize: triangles not loaded");
-    if (planar < 0 || (planar > 1 && planar < h->tri_nver)) return fail(SYN_ERR_INVALID, "syn_rasterize: planar=%d (0, 1 or a row pitch >= %d)", planar, h->tri_nver);
-    if (planar == 1) planar = h->tri_nver;
+    const Topo T = current_topo(h);
+    if (!T.tri) return fail(SYN_ERR_NOT_LOADED, "syn_rasterize: triangles not loaded");
+    if (planar < 0 || (planar > 1 && planar < T.nver)) return fail(SYN_ERR_INVALID, "syn_rasterize: planar=%d (0, 1 or a row pitch >= %d)", planar, T.nver);
+    if (planar == 1) planar = T.nver;
     DeviceGuard g(h->device);
     int rc = ensure_rws(h, sizeof(unsigned long long) * (size_t)H * W);
     if (rc) return rc;
-    syn::launch_rasterize(vertices, h->d_tri, colors, (unsigned long long *)h->rws, image, F, h->tri_nver, h->ntri, H, W, channels,
+    syn::launch_rasterize(vertices, T.tri, colors, (unsigned long long *)h->rws, image, F, T.nver, T.ntri, H, W, channels,
                           planar, reverse, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return SYN_OK;

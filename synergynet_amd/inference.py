@@ -55,6 +55,22 @@ def write_obj(obj_name, vertices, triangles):
                 f.write(('f {} {} {}\n' * t.shape[1]).format(*rev))
 
 
+def write_obj_with_colors(obj_name, vertices, triangles, colors):
+    """Coloured OBJ export of the reference's texture demos (uv_texture_realFaces.py:21-33): `vertices` [3, N] and `colors`
+    [N, 3] as lines `v x y z c2 c1 c0` -- coordinates with four decimals, the colour reversed and printed as `{}` prints the
+    array's scalars (float32 0..255 in the demo: `163.0`) -- then `triangles` [3, M] as `f i0 i1 i2`, rows as given (unlike
+    write_obj, which reverses them), and `.obj` appended to a name that lacks it.  Byte-identical to the reference's file
+    (tests/test_texture_cpu.py)."""
+    if obj_name.split('.')[-1] != 'obj':
+        obj_name = obj_name + '.obj'
+    v, t, col = np.asarray(vertices), np.asarray(triangles), np.asarray(colors)
+    with open(obj_name, 'w') as f:
+        for i in range(v.shape[1]):
+            f.write('v {:.4f} {:.4f} {:.4f} {} {} {}\n'.format(v[0, i], v[1, i], v[2, i], col[i, 2], col[i, 1], col[i, 0]))
+        if t.shape[1]:
+            f.write(('f {} {} {}\n' * t.shape[1]).format(*t[:3].T.ravel()))
+
+
 def _lanczos4_taps(n_dst: int, n_src: int):
     """Per destination index: first source tap (may be out of range, clamp later) and 8 fixed-point weights.
     OpenCV's resize evaluates the source position in double, rounds it to float32 and takes floor / fraction of THAT

@@ -5,6 +5,9 @@ w_base, w_norm, w_base_norm, u_base, w_shp_base, w_exp_base, std_size, dim;
 reference utils/params.py:13-35) and the same 'Missing data' error (:36-37).  The pack
 can also be built from an in-memory dict (synthetic assets: the real 3dmm_data/ files are
 Google-Drive downloads that are absent from the reference checkout).
+
+The three UV assets of the reference's texture demos (uv_texture_realFaces.py:47-51: BFM_UV.npy, keptInd.npy,
+deletedTri.npy) are optional attributes `uv_vert`, `keep_ind`, `tri_deletion`: None when the pack or directory lacks them.
 """
 from __future__ import annotations
 
@@ -13,6 +16,7 @@ import pickle
 
 import numpy as np
 
+_UV_FILES = dict(uv_vert='BFM_UV.npy', keep_ind='keptInd.npy', tri_deletion='deletedTri.npy')
 _FILES = ('keypoints_sim.npy', 'w_shp_sim.npy', 'w_exp_sim.npy', 'param_whitening.pkl', 'u_shp.npy', 'u_exp.npy')
 
 
@@ -45,6 +49,9 @@ class ParamsPack:
                 if os.path.isfile(tri_fp):
                     import scipy.io as sio
                     pack['tri'] = sio.loadmat(tri_fp)['tri']
+                for name, fn in _UV_FILES.items():
+                    if os.path.isfile(os.path.join(d, fn)):
+                        pack[name] = _load(os.path.join(d, fn))
             self.keypoints = np.asarray(pack['keypoints'])
             self.w_shp = np.asarray(pack['w_shp'])
             self.w_exp = np.asarray(pack['w_exp'])
@@ -63,5 +70,15 @@ class ParamsPack:
             self.std_size = 120
             self.dim = self.w_shp.shape[0] // 3
             self.tri = pack.get('tri')                                         # 1-based [3,n_tri] (synergy3DMM.py:73)
+            # texture demos (uv_texture_realFaces.py:47-51): [n_vert,2] UVs, [n_keep] kept vertices, 1-based [3,ntri_k] topology
+            # of the KEPT vertex list (the demo passes connectivity=tri_deletion-1)
+            self.uv_vert, self.keep_ind, self.tri_deletion = (None if pack.get(k) is None else np.asarray(pack[k]) for k in _UV_FILES)
         except Exception:
             raise RuntimeError('Missing data')
+
+
+def uv_pixel_coords(uv_vert):
+    """uv_texture_realFaces.py:48-49: row and column of every vertex in the UV texture image, in the asset's own dtype
+    (a float32 asset multiplies in float32, a float64 one in float64) and truncated toward zero by the int32 cast."""
+    uv = np.asarray(uv_vert)
+    return (uv[:, 1] * 255.0).astype(np.int32), (uv[:, 0] * 255.0).astype(np.int32)

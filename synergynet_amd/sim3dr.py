@@ -4,11 +4,16 @@ Same names, argument meaning and return types as the reference:
   get_normal(vertices, triangles)                          Sim3DR/Sim3DR.py:8-11
   rasterize(vertices, triangles, colors, bg=..., ...)      Sim3DR/Sim3DR.py:14-29
   RenderPipeline(**cfg)(vertices, triangles, bg, texture)  Sim3DR/lighting.py:23-71
-  render(img, ver_lst, alpha=0.6, tex=None)                utils/render.py:31-50 (returns the blended image; no files)
+  render(img, ver_lst, alpha=0.6, tex=None, connectivity=None)   utils/render.py:31-50 (returns the blended image; no files)
 numpy in, numpy out, like the reference -- but every stage runs in HIP kernels through the C ABI
 (syn_load_triangles / syn_mesh_shade / syn_rasterize / syn_add_weighted, csrc/render_kernels.hip) on the most recently
 constructed SynergyNet's handle; there is no CPU fallback.  `render_batch` is the device-resident entry: meshes as the
 [F,3,N] tensor `reconstruct(..., dense=True)` returns, no transposes, no host copies.
+
+Textured meshes (the reference's uv_texture_realFaces.py / artistic.py): `uv_vertex_colors` looks one colour per vertex up in
+a UV texture image, `render_batch(..., uv_tex= | tex=)` gathers the kept vertex subset, multiplies texture and light in the
+lighting kernel and draws the kept topology -- syn_load_uv_map / syn_uv_colors / syn_gather_vertices / syn_mesh_shade_textured,
+all on the device.  The handle keeps two topology slots (full mesh, kept mesh); `model._topology_uploads` counts the uploads.
 """
 from __future__ import annotations
 
@@ -38,12 +43,50 @@ def _triangles(m, triangles):
     return t, key
 
 
+def _count_upload(m, slot):
+    """`model._topology_uploads` = [uploads of the syn_load_triangles slot, uploads of the kept slot of syn_load_uv_map]."""
+    if not hasattr(m, '_topology_uploads'):
+        m._topology_uploads = [0, 0]
+    m._topology_uploads[slot] += 1
+
+
+def _select(m, slot):
+    """Point syn_mesh_shade* / syn_rasterize at a topology slot (0: syn_load_triangles, 1: the kept mesh); a host-side switch."""
+    abi.check(m._lib.syn_select_topology(m._h, slot))
+
+
 def _ensure_topology(m, triangles, nver):
     t, key = _triangles(m, triangles)
     if getattr(m, '_tri_key', None) != (key, nver):
         abi.check(m._lib.syn_load_triangles(m._h, t.ctypes.data_as(C.c_void_p), t.shape[0], nver))
         m._tri_key = (key, nver)
+        _count_upload(m, 0)
+    _select(m, 0)
     return t
+
+
+def _ensure_uv_map(m):
+    """Upload the model's UV assets (param_pack.uv_vert / keep_ind / tri_deletion) once: pixel tables, kept vertices and the
+    kept topology in the handle's second slot.  Returns (n_vert, n_keep)."""
+    pp = getattr(m, 'param_pack', None)
+    if pp is None or getattr(pp, 'uv_vert', None) is None or pp.keep_ind is None or pp.tri_deletion is None:
+        raise RuntimeError('Missing data: the model has no UV assets (BFM_UV.npy, keptInd.npy, deletedTri.npy)')
+    objs = (pp.uv_vert, pp.keep_ind, pp.tri_deletion)
+    held = getattr(m, '_uv_key', None)
+    if held is None or any(a is not b for a, b in zip(held[0], objs)):
+        from .params import uv_pixel_coords
+        cu, cv = (np.ascontiguousarray(a, dtype=np.int32) for a in uv_pixel_coords(pp.uv_vert))
+        keep = np.asarray(pp.keep_ind).reshape(-1)
+        td = np.asarray(pp.tri_deletion)
+        if td.ndim != 2 or td.shape[0] != 3:
+            raise ValueError('tri_deletion must be [3,ntri] (1-based), as deletedTri.npy holds it')
+        keep = np.ascontiguousarray(keep, dtype=np.int32)
+        tri = np.ascontiguousarray(td.T.astype(np.int64) - 1, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        abi.check(m._lib.syn_load_uv_map(m._h, ptr(cu), ptr(cv), cu.size, ptr(keep), keep.size, ptr(tri), tri.shape[0]))
+        m._uv_key = (objs, cu.size, keep.size)
+        _count_upload(m, 1)
+    return m._uv_key[1], m._uv_key[2]
 
 
 def _cfg16(pipe):
@@ -75,6 +118,74 @@ def _shade(m, verts_t, planar, cfg=None):
         abi.check(m._lib.syn_mesh_shade(m._h, verts_t.data_ptr(), F, int(planar), cfg, normal.data_ptr(),
                                         light.data_ptr() if light is not None else None, m._stream()))
     return normal, light
+
+
+def _shade_textured(m, verts_t, planar, cfg, tex_t, shared, want_light=False):
+    """Normals + Phong light with `texture *= light` (lighting.py:68-70) in the kernel's epilogue, on the selected topology.
+    tex_t: float32 device tensor, [n,3] when shared (multiplied in place face after face, like the reference's caller array) or
+    [F,n,3].  Returns (normal, light or None, colours [F,n,3])."""
+    F = verts_t.shape[0]
+    n = verts_t.shape[2] if planar else verts_t.shape[1]
+    if tex_t.dtype != torch.float32 or not tex_t.is_contiguous() or tuple(tex_t.shape) != ((n, 3) if shared else (F, n, 3)):
+        raise ValueError(f'tex must be a contiguous float32 [{n},3] or [{F},{n},3] array (one colour per vertex of the mesh), got '
+                         f'{tuple(tex_t.shape)} {tex_t.dtype}')
+    normal = torch.empty((F, n, 3), dtype=torch.float32, device=m.device)
+    light = torch.empty_like(normal) if want_light else None
+    colors = torch.empty_like(normal)
+    with torch.cuda.device(m.device):
+        abi.check(m._lib.syn_mesh_shade_textured(m._h, verts_t.data_ptr(), F, int(planar), cfg, normal.data_ptr(),
+                                                 light.data_ptr() if light is not None else None, tex_t.data_ptr(), int(shared),
+                                                 colors.data_ptr(), m._stream()))
+    return normal, light, colors
+
+
+def _tex_arg(m, tex, F, n):
+    """A caller's texture as (device tensor, shared?, host array to update afterwards or None).  numpy arrays are the
+    reference's calling convention ([n,3] float32, multiplied in place); device tensors stay on the device."""
+    if isinstance(tex, torch.Tensor):
+        t, back = tex, None
+        if t.device != m.device:
+            raise ValueError(f'tex tensor must live on {m.device}')
+    else:
+        if not isinstance(tex, np.ndarray) or tex.dtype != np.float32:
+            raise TypeError('tex must be a float32 numpy array or device tensor (the reference multiplies it in place)')
+        t, back = torch.from_numpy(np.ascontiguousarray(tex)).to(m.device), tex
+    if t.dim() not in (2, 3) or tuple(t.shape[-2:]) != (n, 3) or (t.dim() == 3 and t.shape[0] != F):
+        raise ValueError(f'tex must be [{n},3] or [{F},{n},3] (one colour per vertex of the mesh), got {tuple(t.shape)}')
+    return t, t.dim() == 2, back
+
+
+def uv_vertex_colors(model, uv_tex, kept=True, normalize=False):
+    """One colour per vertex from a UV texture image (uv_texture_realFaces.py:48-49,109-115): uv_tex uint8 [H,W,ch] or
+    [T,H,W,ch] (array or device tensor, rows as cv2.imread delivers them -- the flip of :109 is part of the lookup).  Returns a
+    float32 device tensor [n,ch] / [T,n,ch], n = the kept vertices (kept=True: `colors_uv[keep_ind]`) or all of them; values
+    0..255 (what write_obj_with_colors takes) or / 255 with normalize=True (what render takes as `tex`)."""
+    _ensure_uv_map(model)
+    t = uv_tex if isinstance(uv_tex, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(uv_tex))
+    if t.dtype != torch.uint8 or t.dim() not in (3, 4):
+        raise TypeError('uv_tex must be uint8 [H,W,ch] or [T,H,W,ch]')
+    t = t.to(model.device).contiguous()
+    t4 = t if t.dim() == 4 else t[None]
+    T, th, tw, ch = t4.shape
+    n = model._uv_key[2] if kept else model._uv_key[1]
+    out = torch.empty((T, n, ch), dtype=torch.float32, device=model.device)
+    with torch.cuda.device(model.device):
+        abi.check(model._lib.syn_uv_colors(model._h, t4.data_ptr(), T, th, tw, ch, int(bool(kept)), int(bool(normalize)),
+                                           out.data_ptr(), model._stream()))
+    return out if t.dim() == 4 else out[0]
+
+
+def gather_kept(model, meshes):
+    """meshes[:, :, keep_ind] on the device (uv_texture_realFaces.py:98): [F,3,N] float32, packed or the pitched view
+    reconstruct() returns (read in place) -> packed [F,3,n_keep]."""
+    n_vert, n_keep = _ensure_uv_map(model)
+    if meshes.shape[2] != n_vert:
+        raise ValueError(f'meshes have {meshes.shape[2]} vertices, the UV map {n_vert}')
+    planar = _planar_arg(meshes)
+    out = torch.empty((meshes.shape[0], 3, n_keep), dtype=torch.float32, device=model.device)
+    with torch.cuda.device(model.device):
+        abi.check(model._lib.syn_gather_vertices(model._h, meshes.data_ptr(), meshes.shape[0], planar, out.data_ptr(), model._stream()))
+    return out
 
 
 def get_normal(vertices, triangles):
@@ -111,7 +222,7 @@ def rasterize(vertices, triangles, colors, bg=None, height=None, width=None, cha
 
 
 class RenderPipeline:
-    """Sim3DR/lighting.py:23-71 (texture=None path; a texture multiplies the vertex colours on the host side like :69)."""
+    """Sim3DR/lighting.py:23-71; a texture is multiplied with the light in the lighting kernel and, like :69, in place."""
 
     def __init__(self, **kwargs):
         conv = lambda o: np.array(o, dtype=np.float32)[None, :] if isinstance(o, (tuple, list)) else o
@@ -136,56 +247,110 @@ class RenderPipeline:
         return light[0].cpu().numpy()
 
     def __call__(self, vertices, triangles, bg, texture=None):
-        light = self.light(vertices, triangles)
         if texture is None:
-            return rasterize(vertices, triangles, light, bg=bg)
-        texture *= light
-        return rasterize(vertices, triangles, texture, bg=bg)
+            return rasterize(vertices, triangles, self.light(vertices, triangles), bg=bg)
+        m = _model()
+        if bg.dtype != np.uint8:
+            raise TypeError('bg must be uint8 (the reference binding takes unsigned char, rasterize.pyx:97)')
+        v = np.ascontiguousarray(vertices, dtype=np.float32)
+        _ensure_topology(m, triangles, v.shape[0])
+        vt = torch.from_numpy(v).to(m.device)[None]
+        tex_t, shared, back = _tex_arg(m, texture, 1, v.shape[0])
+        if not shared:
+            raise ValueError('texture must be [nver,3]')
+        height, width, channel = bg.shape
+        img = torch.from_numpy(np.ascontiguousarray(bg)).to(m.device)
+        _, _, colors = _shade_textured(m, vt, False, _cfg16(self), tex_t, True)
+        with torch.cuda.device(m.device):
+            abi.check(m._lib.syn_rasterize(m._h, vt.data_ptr(), colors.data_ptr(), 1, 0, channel, img.data_ptr(), height, width, 0,
+                                           m._stream()))
+        if back is not None:
+            back[...] = tex_t.cpu().numpy()              # `texture *= light` (lighting.py:69): the caller's array holds the product
+        bg[...] = img.cpu().numpy()
+        return bg
 
 
-def render_batch(model, img, meshes, alpha=0.6, cfg=None):
-    """Device-resident utils/render.py:31-50: img uint8 [H,W,3] (tensor or array), meshes [F,3,N] float32 device tensor in
-    image coordinates (reconstruct(..., roi=..., dense=True)); the topology is the model's `triangles`.
-    Returns (solid overlay, blended result) as uint8 device tensors."""
-    pipe = RenderPipeline(**(cfg or RENDER_CFG))
-    F, _, n = meshes.shape
-    if getattr(model, '_tri_obj', None) is not model.triangles or getattr(model, '_tri_key', (None, None))[1] != n:
-        t = np.asarray(model.triangles)                  # the class attribute is [3,ntri] (synergy3DMM.py:105), Sim3DR wants [ntri,3]
-        _ensure_topology(model, np.ascontiguousarray(t.T if t.shape[0] == 3 else t), n)
-        model._tri_obj = model.triangles                 # same object next time: skip the host-side comparison
+def _draw_and_blend(model, img, meshes, colors, planar, alpha):
     img_t = (img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))).to(model.device)
     H, W, ch = img_t.shape
+    F = meshes.shape[0]
     overlap = img_t.clone()
     res = torch.empty_like(img_t)
-    planar = _planar_arg(meshes)       # the pitched rows reconstruct() writes are read in place: no packed copy on the device path
     with torch.cuda.device(model.device):
-        normal, light = _shade(model, meshes, planar=planar, cfg=_cfg16(pipe))
         for f0 in range(0, F, 254):                      # the z-key has an 8-bit face field; later faces overwrite earlier ones
             f1 = min(F, f0 + 254)
-            abi.check(model._lib.syn_rasterize(model._h, meshes[f0:f1].data_ptr(), light[f0:f1].data_ptr(), f1 - f0, planar, ch,
+            abi.check(model._lib.syn_rasterize(model._h, meshes[f0:f1].data_ptr(), colors[f0:f1].data_ptr(), f1 - f0, planar, ch,
                                                overlap.data_ptr(), H, W, 0, model._stream()))
         abi.check(model._lib.syn_add_weighted(model._h, img_t.data_ptr(), C.c_float(1 - alpha), overlap.data_ptr(), C.c_float(alpha),
                                               res.data_ptr(), img_t.numel(), model._stream()))
     return overlap, res
 
 
+def _render_textured(model, img, meshes, tex, alpha, pipe):
+    """The meshes (vertex count = that of the selected topology) drawn with tex * light; tex as _tex_arg takes it."""
+    F, _, n = meshes.shape
+    tex_t, shared, back = _tex_arg(model, tex, F, n)
+    planar = _planar_arg(meshes)
+    _, _, colors = _shade_textured(model, meshes, planar, _cfg16(pipe), tex_t, shared)
+    out = _draw_and_blend(model, img, meshes, colors, planar, alpha)
+    if back is not None and shared:
+        back[...] = tex_t.cpu().numpy()                  # the reference leaves the caller's array multiplied (lighting.py:69)
+    return out
+
+
+def render_batch(model, img, meshes, alpha=0.6, cfg=None, uv_tex=None, tex=None):
+    """Device-resident utils/render.py:31-50: img uint8 [H,W,3] (tensor or array), meshes [F,3,N] float32 device tensor in
+    image coordinates (reconstruct(..., roi=..., dense=True)); the topology is the model's `triangles`.
+    Returns (solid overlay, blended result) as uint8 device tensors.
+
+    Textured (the texture demos, uv_texture_realFaces.py:96-116): with `uv_tex` (uint8 UV texture image [H,W,3], or [F,H,W,3]
+    for one per face) or `tex` (float32 colours in [0,1] per KEPT vertex, [n_keep,3] shared or [F,n_keep,3]) the full meshes
+    are gathered to the model's kept vertex subset, lit, multiplied with the texture and drawn with the kept topology
+    (param_pack.keep_ind / tri_deletion) -- gather, lookup, shade, raster and blend on the device.  A shared `tex` is
+    multiplied in place face after face like the reference's (lighting.py:69)."""
+    pipe = RenderPipeline(**(cfg or RENDER_CFG))
+    if uv_tex is not None or tex is not None:
+        if uv_tex is not None and tex is not None:
+            raise ValueError('give uv_tex or tex, not both')
+        kept = gather_kept(model, meshes)
+        if uv_tex is not None:
+            tex = uv_vertex_colors(model, uv_tex, kept=True, normalize=True)
+            if tex.shape[-1] != 3:
+                raise ValueError('uv_tex must have 3 channels to be rendered')
+        _select(model, 1)
+        return _render_textured(model, img, kept, tex, alpha, pipe)
+    F, _, n = meshes.shape
+    if getattr(model, '_tri_obj', None) is not model.triangles or getattr(model, '_tri_key', (None, None))[1] != n:
+        t = np.asarray(model.triangles)                  # the class attribute is [3,ntri] (synergy3DMM.py:105), Sim3DR wants [ntri,3]
+        _ensure_topology(model, np.ascontiguousarray(t.T if t.shape[0] == 3 else t), n)
+        model._tri_obj = model.triangles                 # same object next time: skip the host-side comparison
+    _select(model, 0)
+    planar = _planar_arg(meshes)       # the pitched rows reconstruct() writes are read in place: no packed copy on the device path
+    with torch.cuda.device(model.device):
+        _, light = _shade(model, meshes, planar=planar, cfg=_cfg16(pipe))
+    return _draw_and_blend(model, img, meshes, light, planar, alpha)
+
+
 def render(img, ver_lst, alpha=0.6, wfp=None, tex=None, connectivity=None):
     """utils/render.py:31-50: img uint8 [H,W,3], ver_lst = the mesh list of get_all_outputs ((3,N) arrays).  Returns the
-    blended image; `wfp` (file output through cv2.imwrite in the reference) is not supported here."""
+    blended image; `wfp` (file output through cv2.imwrite in the reference) is not supported here.
+    tex [N,3] float32 in [0,1]: one colour per vertex of the meshes AS PASSED (the texture demos pass the kept subset and
+    connectivity=tri_deletion-1, uv_texture_realFaces.py:115-116); it is multiplied with the light of every face in turn, in
+    place, so the caller's array is left mutated like the reference's (lighting.py:69)."""
     if wfp is not None:
         raise NotImplementedError('file output is outside this library (the reference uses cv2.imwrite)')
-    if tex is not None:
-        raise NotImplementedError('textured rendering: use RenderPipeline.__call__(..., texture=...)')
     m = _model()
+    meshes = torch.from_numpy(np.stack([np.asarray(v, dtype=np.float32) for v in ver_lst])).to(m.device)
+    saved = m.triangles
     if connectivity is not None:
         tri = np.ascontiguousarray(np.asarray(connectivity).T, dtype=np.int32)
-        meshes = torch.from_numpy(np.stack([np.asarray(v, dtype=np.float32) for v in ver_lst])).to(m.device)
         _ensure_topology(m, tri, meshes.shape[2])
-        saved = m.triangles
         m.triangles = torch.from_numpy(tri.T.astype(np.int64))
-        try:
+    try:
+        if tex is None:
             return render_batch(m, img, meshes, alpha)[1].cpu().numpy()
-        finally:
-            m.triangles = saved
-    meshes = torch.from_numpy(np.stack([np.asarray(v, dtype=np.float32) for v in ver_lst])).to(m.device)
-    return render_batch(m, img, meshes, alpha)[1].cpu().numpy()
+        t = np.asarray(m.triangles)
+        _ensure_topology(m, np.ascontiguousarray(t.T if t.shape[0] == 3 else t), meshes.shape[2])
+        return _render_textured(m, img, meshes, tex, alpha, RenderPipeline(**RENDER_CFG))[1].cpu().numpy()
+    finally:
+        m.triangles = saved

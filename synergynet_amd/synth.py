@@ -273,6 +273,31 @@ def make_face_meshes(n_faces: int, rows: int = 231, cols: int = 231, n_vert: int
     return np.ascontiguousarray(out, dtype=np.float32)
 
 
+def make_uv_assets(n_vert: int | None = None, rows: int = 231, cols: int = 231, seed: int = 31) -> dict:
+    """Seeded stand-ins for the reference's texture assets (uv_texture_realFaces.py:47-51) on the grid of make_grid_topology:
+    uv_vert [n_vert,2] float32 in [0,1) (3dmm_data/BFM_UV.npy: the grid position of a vertex plus jitter), keep_ind [n_keep] int64
+    (keptInd.npy) and tri_deletion [3,ntri_k] int32, 1-based, indexing the KEPT vertex list (deletedTri.npy).  The keep set drops
+    the first rows and the last columns of the grid -- so the min/max box of norm_vertices (lighting.py:9-14) changes -- and
+    scattered vertices inside; the kept topology is the grid's triangles whose corners all survive, re-indexed, and a vertex no
+    such triangle uses is dropped too."""
+    n = rows * cols if n_vert is None else n_vert
+    rng = np.random.default_rng(seed)
+    idx = np.arange(n)
+    r, c = idx // cols, idx % cols
+    uv = np.stack([(c + rng.uniform(0.05, 0.95, n)) / cols, (r + rng.uniform(0.05, 0.95, n)) / rows], 1)
+    uv_vert = np.minimum(uv, np.nextafter(np.float32(1), np.float32(0))).astype(np.float32)
+    keep = (r >= max(1, rows // 8)) & (c < cols - max(1, cols // 10)) & (rng.uniform(0, 1, n) > 0.01)
+    tri = make_grid_topology(rows, cols, n_vert=None if n_vert is None else n_vert)
+    tri = tri[keep[tri].all(1)]
+    used = np.zeros(n, bool)
+    used[tri.reshape(-1)] = True
+    keep_ind = np.flatnonzero(used)
+    new_id = np.full(n, -1, np.int64)
+    new_id[keep_ind] = np.arange(keep_ind.size)
+    tri_deletion = np.ascontiguousarray(new_id[tri].T + 1, dtype=np.int32)
+    return dict(uv_vert=uv_vert, keep_ind=keep_ind.astype(np.int64), tri_deletion=tri_deletion)
+
+
 # ---- FaceBoxes detector (SURVEY 8f row 4): layer table shared by the oracle, the packer and the tests ----
 def faceboxes_convs():
     """(state_dict prefix, cin, cout, k, stride, pad, kind) for every convolution of FaceBoxesNet in forward order
