@@ -281,6 +281,43 @@ int syn_gather_vertices(syn_handle *h, const float *vertices, int F, int planar,
 int syn_mesh_shade_textured(syn_handle *h, const float *vertices, int F, int planar, const float *cfg16, float *normal, float *light,
                             float *tex, int shared, float *colors, void *stream);
 
+/* ---- visibility buffers: Sim3DR.rasterize_triangles and the way from a photograph to a UV texture image ----
+ * All four work on the topology syn_select_topology selected, take `planar` as syn_mesh_shade does, enqueue on `stream` and
+ * synchronise nothing.
+ *
+ * syn_rasterize_triangles: Sim3DR.rasterize_triangles (Sim3DR/lib/rasterize.pyx:74-86 -> rasterize_kernel.cpp:290-348) for F meshes,
+ * each into its OWN planes: per pixel the triangle that wins the depth test (the deepest; the earliest index among equal depths,
+ * +0 and -0 being equal), its depth and its barycentric weights (order 1-u-v, v, u).
+ * depth_buffer [F,H,W] float32, triangle_buffer [F,H,W] int32, barycentric_weight [F,H,W,3] float32: device, IN-OUT.  The caller
+ * initialises them (the usual values are -1e8, -1 and 0), exactly as the reference's binding leaves that to its caller: a
+ * triangle competes for a pixel only where its depth is greater than the caller's depth_buffer (NaN never is), and pixels no
+ * triangle wins keep the caller's values in all three.  Any F (no face field in the key; the key planes come from the render
+ * scratch, which grows on demand); F*H*W >= 2^31 is SYN_ERR_INVALID. */
+int syn_rasterize_triangles(syn_handle *h, const float *vertices, int F, int planar, float *depth_buffer, int32_t *triangle_buffer,
+                            float *barycentric_weight, int H, int W, void *stream);
+
+/* Per-vertex visibility, the rule of the 3DDFA lineage: a vertex is visible when it is a corner of a triangle that won at least
+ * one pixel.  triangle_buffer: device [F,H,W] int32 as syn_rasterize_triangles leaves it (values outside [0, ntri) mark nothing);
+ * visible: device [F,nver] uint8, zeroed by the call, 1 where visible. */
+int syn_vertex_visibility(syn_handle *h, const int32_t *triangle_buffer, int F, int H, int W, uint8_t *visible, void *stream);
+
+/* One colour per vertex from a frame: bilinear sample of image (device uint8 [H,W,channels], channels <= 4) at the vertex' (x, y),
+ * in the operation order of the reference's bilinear code (rasterize_kernel.cpp:428-447): x clamped to [0,W-1], y to [0,H-1],
+ * xd = x - floor(x), yd likewise, ul*(1-xd)*(1-yd) + ur*xd*(1-yd) + dl*(1-xd)*yd + dr*xd*yd, left to right in float32.
+ * out: device float32 [F,nver,channels], 0..255 (normalize = 0) or divided by 255.0f (one IEEE division).  A vertex whose x or y is
+ * not finite gets colour 0. */
+int syn_sample_vertex_colors(syn_handle *h, const float *vertices, int F, int planar, const uint8_t *image, int H, int W, int channels,
+                             int normalize, float *out, void *stream);
+
+/* The inverse of syn_uv_colors over ALL vertices of the UV table (needs syn_load_uv_map, SYN_ERR_NOT_LOADED otherwise): for every face
+ * tex[f, tex_h-1-coord_u[v], coord_v[v], :] = uint8(clip(rint(colors[f,v,:]), 0, 255)) and mask[f, ...] = 255 for every vertex v with
+ * visible[f,v] != 0 (visible == NULL: every vertex).  Where several vertices share a texel the highest vertex index wins (numpy's
+ * in-order assignment); texels no vertex lands on are 0 in both.  Every texel of tex and mask is written.
+ * colors: device float32 [F,nver,channels] in 0..255; visible: device uint8 [F,nver] or NULL; tex: device uint8 [F,tex_h,tex_w,channels];
+ * mask: device uint8 [F,tex_h,tex_w].  SYN_ERR_INVALID when the texture is smaller than the table needs. */
+int syn_uv_scatter(syn_handle *h, const float *colors, const uint8_t *visible, int F, int channels, uint8_t *tex, uint8_t *mask, int tex_h,
+                   int tex_w, void *stream);
+
 /* ---- FaceBoxes face detector: the boxes get_all_outputs crops (synergy3DMM.py:169-171) ----
  * syn_detector_flat_count / syn_load_detector: FaceBoxesNet's state_dict (FaceBoxes/models/faceboxes.py:64-114) flattened in
  * forward order -- conv1, conv2, inception{1,2,3}.{branch1x1, branch1x1_2, branch3x3_reduce, branch3x3, branch3x3_reduce_2,

@@ -5,6 +5,8 @@
 //   cv2.addWeighted     (utils/render.py:45)                         alpha overlay
 //   textured meshes     (uv_texture_realFaces.py:45-51,96-116, lighting.py:68-70): UV colour lookup, kept-vertex gather,
 //                       texture * light in the lighting epilogue
+//   Sim3DR.rasterize_triangles (Sim3DR/lib/rasterize_kernel.cpp:290-348)  per-pixel winning triangle, weights, depth; on top of it
+//                       vertex visibility, per-vertex colours sampled from a frame and the scatter into a UV texture image
 // The reference walks the 105 840 triangles one at a time on the host.  Here every stage is data parallel and still
 // reproduces the sequential result BIT FOR BIT (tests/test_gpu_render.py):
 //   * arithmetic is plain IEEE single precision in the reference's operation order -- FMA contraction is switched off for
@@ -315,6 +317,128 @@ __global__ __launch_bounds__(256) void add_weighted_kernel(const unsigned char *
     out[i] = (unsigned char)fminf(fmaxf(rintf(v), 0.0f), 255.0f);
 }
 
+// ---- Sim3DR.rasterize_triangles (rasterize_kernel.cpp:290-348): per pixel the winning triangle, its weights and its depth ----
+// Every face has its own key plane [F,h,w] of [order-preserving depth bits | ~triangle index] (no face field: any F).
+// Pass 1, one thread per (face, triangle).  The box is THIS function's (ceil of the minimum, floor of the maximum, :316-320), not
+// _rasterize's.  A candidate competes only above the caller's depth buffer (:337; NaN never does).  +0 and -0 are equal to the
+// reference's `>`, so the key is taken from +0 for both and the earlier triangle wins; pass 2 recomputes the stored depth.
+__global__ __launch_bounds__(256) void tri_depth_kernel(const float *__restrict__ vertices, const int *__restrict__ tri,
+                                                        const float *__restrict__ depth0, unsigned long long *__restrict__ zkey,
+                                                        int nver, int ntri, int h, int w, int planar) {
+    const int i = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    if (i >= ntri) return;
+    const float *v = vertices + (size_t)f * face_stride(planar, nver);
+    const int t0 = tri[3 * i], t1 = tri[3 * i + 1], t2 = tri[3 * i + 2];
+    const float p0x = vtx(v, planar, nver, t0, 0), p0y = vtx(v, planar, nver, t0, 1), d0 = vtx(v, planar, nver, t0, 2);
+    const float p1x = vtx(v, planar, nver, t1, 0), p1y = vtx(v, planar, nver, t1, 1), d1 = vtx(v, planar, nver, t1, 2);
+    const float p2x = vtx(v, planar, nver, t2, 0), p2y = vtx(v, planar, nver, t2, 1), d2 = vtx(v, planar, nver, t2, 2);
+    const int x_min = max((int)ceilf(fminf(p0x, fminf(p1x, p2x))), 0), x_max = min((int)floorf(fmaxf(p0x, fmaxf(p1x, p2x))), w - 1);
+    const int y_min = max((int)ceilf(fminf(p0y, fminf(p1y, p2y))), 0), y_max = min((int)floorf(fmaxf(p0y, fmaxf(p1y, p2y))), h - 1);
+    if (x_max < x_min || y_max < y_min) return;
+    const size_t plane = (size_t)f * h * w;
+    const unsigned long long lo = (unsigned long long)(0xffffffu - (unsigned)i);
+    for (int y = y_min; y <= y_max; ++y)
+        for (int x = x_min; x <= x_max; ++x) {
+            const Bary b = bary((float)x, (float)y, p0x, p0y, p1x, p1y, p2x, p2y);
+            if (!b.in) continue;
+            const float depth = b.w0 * d0 + b.w1 * d1 + b.w2 * d2;
+            const size_t px = plane + (size_t)y * w + x;
+            if (!(depth > depth0[px])) continue;
+            atomicMax(&zkey[px], ((unsigned long long)depth_key(depth == 0.0f ? 0.0f : depth) << 24) | lo);
+        }
+}
+
+// Pass 2, one thread per (face, pixel): where a triangle won, its depth, index and weights (1-u-v, v, u) re-derived with the same
+// expressions; elsewhere the caller's three buffers stay as they are (:337-343).
+__global__ __launch_bounds__(256) void tri_resolve_kernel(const float *__restrict__ vertices, const int *__restrict__ tri,
+                                                          const unsigned long long *__restrict__ zkey, float *__restrict__ depth,
+                                                          int *__restrict__ tri_buf, float *__restrict__ weight, int nver, int h,
+                                                          int w, int planar) {
+    const int px = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    if (px >= h * w) return;
+    const size_t o = (size_t)f * h * w + px;
+    const unsigned long long k = zkey[o];
+    if (k == 0ull) return;
+    int i = (int)(0xffffffu - (unsigned)(k & 0xffffffull));
+    asm volatile("" : "+v"(i));                              // the opaque copy of raster_shade_kernel (hipcc 7.2 mask loss)
+    const int y = px / w, x = px % w;
+    const float *v = vertices + (size_t)f * face_stride(planar, nver);
+    const int t0 = tri[3 * i], t1 = tri[3 * i + 1], t2 = tri[3 * i + 2];
+    const Bary b = bary((float)x, (float)y, vtx(v, planar, nver, t0, 0), vtx(v, planar, nver, t0, 1), vtx(v, planar, nver, t1, 0),
+                        vtx(v, planar, nver, t1, 1), vtx(v, planar, nver, t2, 0), vtx(v, planar, nver, t2, 1));
+    depth[o] = b.w0 * vtx(v, planar, nver, t0, 2) + b.w1 * vtx(v, planar, nver, t1, 2) + b.w2 * vtx(v, planar, nver, t2, 2);
+    tri_buf[o] = i;
+    float *wo = weight + o * 3;
+    wo[0] = b.w0; wo[1] = b.w1; wo[2] = b.w2;
+}
+
+// ---- per-vertex visibility (the 3DDFA lineage's rule): a vertex is visible when it is a corner of a triangle that won a pixel ----
+// one thread per (face, pixel); every writer stores the same byte, so the race between them is benign.  visible [F,nver] zeroed.
+__global__ __launch_bounds__(256) void vertex_visible_kernel(const int *__restrict__ tri_buf, const int *__restrict__ tri,
+                                                             unsigned char *__restrict__ visible, int nver, int ntri, int hw) {
+    const int px = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    if (px >= hw) return;
+    const int i = tri_buf[(size_t)f * hw + px];
+    if (i < 0 || i >= ntri) return;                          // -1 (nothing drawn) or a caller's value that is no triangle
+    unsigned char *vis = visible + (size_t)f * nver;
+    for (int c = 0; c < 3; ++c) vis[tri[3 * i + c]] = 1;
+}
+
+// ---- per-vertex colours from a frame: bilinear sample at the vertex' (x, y) in the operation order of the reference's only
+// bilinear code (rasterize_kernel.cpp:428-447), one thread per (face, vertex); a vertex with a non-finite x or y gets 0 ----
+__global__ __launch_bounds__(256) void sample_vertex_colors_kernel(const float *__restrict__ vertices,
+                                                                   const unsigned char *__restrict__ image, float *__restrict__ out,
+                                                                   int nver, int h, int w, int ch, int planar, int normalize) {
+    const int i = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    if (i >= nver) return;
+    const float *v = vertices + (size_t)f * face_stride(planar, nver);
+    float x = vtx(v, planar, nver, i, 0), y = vtx(v, planar, nver, i, 1);
+    float *o = out + ((size_t)f * nver + i) * ch;
+    if (!(fabsf(x) <= 3.402823466e38f) || !(fabsf(y) <= 3.402823466e38f)) {
+        for (int q = 0; q < ch; ++q) o[q] = 0.0f;
+        return;
+    }
+    x = fmaxf(fminf(x, (float)(w - 1)), 0.0f);
+    y = fmaxf(fminf(y, (float)(h - 1)), 0.0f);
+    const float fx = floorf(x), fy = floorf(y);
+    const float xd = x - fx, yd = y - fy;
+    const int x0 = (int)fx, x1 = (int)ceilf(x), y0 = (int)fy, y1 = (int)ceilf(y);
+    for (int q = 0; q < ch; ++q) {
+        const float ul = (float)image[((size_t)y0 * w + x0) * ch + q], ur = (float)image[((size_t)y0 * w + x1) * ch + q];
+        const float dl = (float)image[((size_t)y1 * w + x0) * ch + q], dr = (float)image[((size_t)y1 * w + x1) * ch + q];
+        const float c = ul * (1 - xd) * (1 - yd) + ur * xd * (1 - yd) + dl * (1 - xd) * yd + dr * xd * yd;
+        o[q] = normalize ? c / 255.0f : c;
+    }
+}
+
+// ---- UV scatter, the inverse of uv_colors_kernel: tex[th-1-coord_u[v], coord_v[v], :] = uint8(clip(rint(colour[v]), 0, 255)) ----
+// Several vertices share a texel; numpy's in-order assignment leaves the HIGHEST vertex index there.  Pass 1 (one thread per
+// (face, vertex)) takes the maximum of v + 1 per texel into owner [F,th,tw] (zeroed); pass 2 (one thread per (face, texel))
+// writes the owner's colour and mask 255, or zeros where no vertex landed.
+__global__ __launch_bounds__(256) void uv_owner_kernel(const int *__restrict__ coord_u, const int *__restrict__ coord_v,
+                                                       const unsigned char *__restrict__ visible, unsigned *__restrict__ owner,
+                                                       int nver, int th, int tw) {
+    const int v = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    if (v >= nver) return;
+    if (visible && !visible[(size_t)f * nver + v]) return;
+    atomicMax(&owner[((size_t)f * th + (th - 1 - coord_u[v])) * tw + coord_v[v]], (unsigned)v + 1u);
+}
+
+__global__ __launch_bounds__(256) void uv_scatter_kernel(const float *__restrict__ colors, const unsigned *__restrict__ owner,
+                                                         unsigned char *__restrict__ tex, unsigned char *__restrict__ mask,
+                                                         int nver, int texels, int ch) {
+    const int t = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    if (t >= texels) return;
+    const size_t o = (size_t)f * texels + t;
+    const unsigned own = owner[o];
+    const float *col = colors + ((size_t)f * nver + (own ? own - 1 : 0)) * ch;
+    for (int q = 0; q < ch; ++q) {
+        const float c = own ? col[q] : 0.0f;
+        tex[o * ch + q] = (unsigned char)fminf(fmaxf(rintf(c), 0.0f), 255.0f);
+    }
+    mask[o] = own ? 255 : 0;
+}
+
 void launch_mesh_normals(const float *vertices, const int *tri, const int *adj_off, const int *adj_tri, float *tri_normal,
                          float *normal, unsigned *mm, int F, int nver, int ntri, int planar, hipStream_t s) {
     // per-face extrema start at +inf / -inf in key space
@@ -352,6 +476,31 @@ void launch_rasterize(const float *vertices, const int *tri, const float *colors
     (void)hipMemsetAsync(zkey, 0, sizeof(unsigned long long) * (size_t)h * w, s);
     raster_depth_kernel<<<dim3((ntri + 255) / 256, F), 256, 0, s>>>(vertices, tri, zkey, nver, ntri, h, w, planar);
     raster_shade_kernel<<<(h * w + 255) / 256, 256, 0, s>>>(vertices, tri, colors, zkey, image, nver, h, w, c, planar, reverse);
+}
+
+void launch_rasterize_triangles(const float *vertices, const int *tri, unsigned long long *zkey, float *depth, int *tri_buf,
+                                float *weight, int F, int nver, int ntri, int h, int w, int planar, hipStream_t s) {
+    (void)hipMemsetAsync(zkey, 0, sizeof(unsigned long long) * (size_t)F * h * w, s);
+    tri_depth_kernel<<<dim3((ntri + 255) / 256, F), 256, 0, s>>>(vertices, tri, depth, zkey, nver, ntri, h, w, planar);
+    tri_resolve_kernel<<<dim3((h * w + 255) / 256, F), 256, 0, s>>>(vertices, tri, zkey, depth, tri_buf, weight, nver, h, w, planar);
+}
+
+void launch_vertex_visibility(const int *tri_buf, const int *tri, unsigned char *visible, int F, int nver, int ntri, int h, int w,
+                              hipStream_t s) {
+    (void)hipMemsetAsync(visible, 0, (size_t)F * nver, s);
+    vertex_visible_kernel<<<dim3((h * w + 255) / 256, F), 256, 0, s>>>(tri_buf, tri, visible, nver, ntri, h * w);
+}
+
+void launch_sample_vertex_colors(const float *vertices, const unsigned char *image, float *out, int F, int nver, int h, int w, int ch,
+                                 int planar, int normalize, hipStream_t s) {
+    sample_vertex_colors_kernel<<<dim3((nver + 255) / 256, F), 256, 0, s>>>(vertices, image, out, nver, h, w, ch, planar, normalize);
+}
+
+void launch_uv_scatter(const float *colors, const unsigned char *visible, const int *coord_u, const int *coord_v, unsigned *owner,
+                       unsigned char *tex, unsigned char *mask, int F, int nver, int th, int tw, int ch, hipStream_t s) {
+    (void)hipMemsetAsync(owner, 0, sizeof(unsigned) * (size_t)F * th * tw, s);
+    uv_owner_kernel<<<dim3((nver + 255) / 256, F), 256, 0, s>>>(coord_u, coord_v, visible, owner, nver, th, tw);
+    uv_scatter_kernel<<<dim3((th * tw + 255) / 256, F), 256, 0, s>>>(colors, owner, tex, mask, nver, th * tw, ch);
 }
 
 void launch_add_weighted(const unsigned char *a, float alpha, const unsigned char *b, float beta, unsigned char *out, size_t n,

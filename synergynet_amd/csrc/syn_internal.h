@@ -280,6 +280,19 @@ void launch_rasterize(const float *vertices, const int *tri, const float *colors
                       int reverse, hipStream_t s);
 void launch_add_weighted(const unsigned char *a, float alpha, const unsigned char *b, float beta, unsigned char *out, size_t n,
                          hipStream_t s);
+// visibility buffers: Sim3DR.rasterize_triangles for F meshes, each into its own [h,w] planes (depth / tri_buf / weight in-out: pixels
+// no triangle wins keep the caller's values), vertex visibility from the triangle planes, per-vertex colours sampled from a frame,
+// and the UV scatter (inverse of launch_uv_colors; highest vertex index wins a shared texel)
+void launch_rasterize_triangles(const float *vertices, const int *tri, unsigned long long *zkey /*[F,h,w] scratch*/, float *depth /*[F,h,w]*/,
+                                int *tri_buf /*[F,h,w]*/, float *weight /*[F,h,w,3]*/, int F, int nver, int ntri, int h, int w, int planar,
+                                hipStream_t s);
+void launch_vertex_visibility(const int *tri_buf /*[F,h,w]*/, const int *tri, unsigned char *visible /*[F,nver], zeroed here*/, int F,
+                              int nver, int ntri, int h, int w, hipStream_t s);
+void launch_sample_vertex_colors(const float *vertices, const unsigned char *image /*[h,w,ch]*/, float *out /*[F,nver,ch]*/, int F, int nver,
+                                 int h, int w, int ch, int planar, int normalize, hipStream_t s);
+void launch_uv_scatter(const float *colors /*[F,nver,ch]*/, const unsigned char *visible /*nullable [F,nver]*/, const int *coord_u,
+                       const int *coord_v, unsigned *owner /*[F,th,tw] scratch*/, unsigned char *tex /*[F,th,tw,ch]*/,
+                       unsigned char *mask /*[F,th,tw]*/, int F, int nver, int th, int tw, int ch, hipStream_t s);
 
 // ---- AFLW2000-3D landmark error (eval_kernels.hip) ----
 void launch_nme(const float *fit, const float *gt, const float *roi, float *nme, int N, hipStream_t s);

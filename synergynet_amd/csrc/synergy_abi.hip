@@ -2531,6 +2531,72 @@ int syn_rasterize(syn_handle *h, const float *vertices, const float *colors, int
     return SYN_OK;
 }
 
+int syn_rasterize_triangles(syn_handle *h, const float *vertices, int F, int planar, float *depth_buffer, int32_t *triangle_buffer,
+                            float *barycentric_weight, int H, int W, void *stream) {
+    if (!h || !vertices || !depth_buffer || !triangle_buffer || !barycentric_weight)
+        return fail(SYN_ERR_INVALID, "syn_rasterize_triangles: NULL argument");
+    if (F <= 0 || H <= 0 || W <= 0 || (long long)F * H * W >= (1ll << 31))
+        return fail(SYN_ERR_INVALID, "syn_rasterize_triangles: F=%d H=%d W=%d (F*H*W must stay below 2^31)", F, H, W);
+    const Topo T = current_topo(h);
+    if (!T.tri) return fail(SYN_ERR_NOT_LOADED, "syn_rasterize_triangles: triangles not loaded");
+    if (planar < 0 || (planar > 1 && planar < T.nver))
+        return fail(SYN_ERR_INVALID, "syn_rasterize_triangles: planar=%d (0, 1 or a row pitch >= %d)", planar, T.nver);
+    if (planar == 1) planar = T.nver;
+    DeviceGuard g(h->device);
+    int rc = ensure_rws(h, sizeof(unsigned long long) * (size_t)F * H * W);
+    if (rc) return rc;
+    syn::launch_rasterize_triangles(vertices, T.tri, (unsigned long long *)h->rws, depth_buffer, triangle_buffer, barycentric_weight, F,
+                                    T.nver, T.ntri, H, W, planar, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+int syn_vertex_visibility(syn_handle *h, const int32_t *triangle_buffer, int F, int H, int W, uint8_t *visible, void *stream) {
+    if (!h || !triangle_buffer || !visible) return fail(SYN_ERR_INVALID, "syn_vertex_visibility: NULL argument");
+    if (F <= 0 || H <= 0 || W <= 0 || (long long)F * H * W >= (1ll << 31))
+        return fail(SYN_ERR_INVALID, "syn_vertex_visibility: F=%d H=%d W=%d (F*H*W must stay below 2^31)", F, H, W);
+    const Topo T = current_topo(h);
+    if (!T.tri) return fail(SYN_ERR_NOT_LOADED, "syn_vertex_visibility: triangles not loaded");
+    DeviceGuard g(h->device);
+    syn::launch_vertex_visibility(triangle_buffer, T.tri, visible, F, T.nver, T.ntri, H, W, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+int syn_sample_vertex_colors(syn_handle *h, const float *vertices, int F, int planar, const uint8_t *image, int H, int W, int channels,
+                             int normalize, float *out, void *stream) {
+    if (!h || !vertices || !image || !out) return fail(SYN_ERR_INVALID, "syn_sample_vertex_colors: NULL argument");
+    if (F <= 0 || H <= 0 || W <= 0 || channels <= 0 || channels > 4 || (long long)H * W >= (1ll << 29))
+        return fail(SYN_ERR_INVALID, "syn_sample_vertex_colors: F=%d H=%d W=%d channels=%d", F, H, W, channels);
+    const Topo T = current_topo(h);
+    if (!T.tri) return fail(SYN_ERR_NOT_LOADED, "syn_sample_vertex_colors: triangles not loaded");
+    if (planar < 0 || (planar > 1 && planar < T.nver))
+        return fail(SYN_ERR_INVALID, "syn_sample_vertex_colors: planar=%d (0, 1 or a row pitch >= %d)", planar, T.nver);
+    if (planar == 1) planar = T.nver;
+    DeviceGuard g(h->device);
+    syn::launch_sample_vertex_colors(vertices, image, out, F, T.nver, H, W, channels, planar, normalize != 0, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+int syn_uv_scatter(syn_handle *h, const float *colors, const uint8_t *visible, int F, int channels, uint8_t *tex, uint8_t *mask, int tex_h,
+                   int tex_w, void *stream) {
+    if (!h || !colors || !tex || !mask) return fail(SYN_ERR_INVALID, "syn_uv_scatter: NULL argument");
+    if (F <= 0 || tex_h <= 0 || tex_w <= 0 || channels <= 0 || channels > 4 || (long long)F * tex_h * tex_w >= (1ll << 29))
+        return fail(SYN_ERR_INVALID, "syn_uv_scatter: F=%d tex_h=%d tex_w=%d channels=%d", F, tex_h, tex_w, channels);
+    if (!h->d_uv || !h->uv_nver) return fail(SYN_ERR_NOT_LOADED, "syn_uv_scatter: UV map not loaded");
+    if (tex_h <= h->uv_max[0] || tex_w <= h->uv_max[1])
+        return fail(SYN_ERR_INVALID, "syn_uv_scatter: a %d x %d texture is smaller than the UV table needs (%d x %d)", tex_h, tex_w,
+                    h->uv_max[0] + 1, h->uv_max[1] + 1);
+    DeviceGuard g(h->device);
+    int rc = ensure_rws(h, sizeof(unsigned) * (size_t)F * tex_h * tex_w);
+    if (rc) return rc;
+    syn::launch_uv_scatter(colors, visible, h->d_uv, h->d_uv + h->uv_nver, (unsigned *)h->rws, tex, mask, F, h->uv_nver, tex_h, tex_w,
+                           channels, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 int syn_add_weighted(syn_handle *h, const uint8_t *a, float alpha, const uint8_t *b, float beta, uint8_t *out, size_t n,
                      void *stream) {
     if (!h || !a || !b || !out) return fail(SYN_ERR_INVALID, "syn_add_weighted: NULL argument");

@@ -14,6 +14,13 @@ Textured meshes (the reference's uv_texture_realFaces.py / artistic.py): `uv_ver
 a UV texture image, `render_batch(..., uv_tex= | tex=)` gathers the kept vertex subset, multiplies texture and light in the
 lighting kernel and draws the kept topology -- syn_load_uv_map / syn_uv_colors / syn_gather_vertices / syn_mesh_shade_textured,
 all on the device.  The handle keeps two topology slots (full mesh, kept mesh); `model._topology_uploads` counts the uploads.
+
+Visibility buffers: `rasterize_triangles` is the third entry point of the reference's binding (Sim3DR/lib/rasterize.pyx:74-86: per
+pixel the winning triangle, its barycentric weights and its depth, written into the caller's arrays).  `visibility_batch` is its
+device-resident form plus the per-vertex visibility that follows from it, `vertex_colors_from_image` samples one colour per vertex
+from a frame, and `texture_from_image` chains them into a UV texture image (and its mask of filled texels) -- what
+`render_batch(uv_tex=)` and `uv_vertex_colors` consume.  syn_rasterize_triangles / syn_vertex_visibility /
+syn_sample_vertex_colors / syn_uv_scatter.
 """
 from __future__ import annotations
 
@@ -188,6 +195,115 @@ def gather_kept(model, meshes):
     return out
 
 
+def _ensure_model_topology(model, n):
+    """The model's `triangles` in topology slot 0 (uploaded when the attribute or the vertex count changed), selected."""
+    if getattr(model, '_tri_obj', None) is not model.triangles or getattr(model, '_tri_key', (None, None))[1] != n:
+        t = np.asarray(model.triangles)                  # the class attribute is [3,ntri] (synergy3DMM.py:105), Sim3DR wants [ntri,3]
+        _ensure_topology(model, np.ascontiguousarray(t.T if t.shape[0] == 3 else t), n)
+        model._tri_obj = model.triangles                 # same object next time: skip the host-side comparison
+    _select(model, 0)
+
+
+def _raster_triangles(m, verts_t, F, planar, depth, tri, bary, height, width):
+    with torch.cuda.device(m.device):
+        abi.check(m._lib.syn_rasterize_triangles(m._h, verts_t.data_ptr(), F, int(planar), depth.data_ptr(), tri.data_ptr(),
+                                                 bary.data_ptr(), height, width, m._stream()))
+
+
+def rasterize_triangles(vertices, triangles, depth_buffer, triangle_buffer, barycentric_weight, ntri, h, w):
+    """Sim3DR/lib/rasterize.pyx:74-86, the binding's own signature: vertices [nver,3] float32, triangles [>= ntri,3] int32 and three
+    C-contiguous arrays the CALLER initialises (usually -1e8, -1 and 0) and that are updated in place: depth_buffer float32 and
+    triangle_buffer int32 of h*w elements, barycentric_weight float32 of h*w*3.  Where a triangle is deeper than depth_buffer the
+    pixel gets its depth, index and weights; every other element keeps the caller's value."""
+    m = _model()
+    for a, dt, n, name in ((depth_buffer, np.float32, h * w, 'depth_buffer'), (triangle_buffer, np.int32, h * w, 'triangle_buffer'),
+                           (barycentric_weight, np.float32, h * w * 3, 'barycentric_weight')):
+        if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags.c_contiguous or a.size != n:
+            raise TypeError(f'{name} must be a C-contiguous {np.dtype(dt).name} array of {n} elements (rasterize.pyx:74-86)')
+    v = np.ascontiguousarray(vertices, dtype=np.float32)
+    t = np.asarray(triangles)
+    if not 0 < ntri <= t.shape[0]:
+        raise ValueError(f'ntri={ntri} with {t.shape[0]} triangles')
+    _ensure_topology(m, t[:ntri], v.shape[0])
+    m._tri_obj = None                                    # slot 0 may no longer hold the model's own topology: render_batch re-checks
+    dev =[torch.from_numpy(a.reshape(-1)).to(m.device) for a in (depth_buffer, triangle_buffer, barycentric_weight)]
+    _raster_triangles(m, torch.from_numpy(v).to(m.device), 1, 0, dev[0], dev[1], dev[2], h, w)
+    for a, d in zip((depth_buffer, triangle_buffer, barycentric_weight), dev):
+        a.reshape(-1)[...] = d.cpu().numpy()
+
+
+def _visibility(model, meshes, height, width):
+    F, _, n = meshes.shape
+    _ensure_model_topology(model, n)
+    planar = _planar_arg(meshes)
+    dev = model.device
+    depth = torch.full((F, height, width), -1e8, dtype=torch.float32, device=dev)       # the binding's usual initial values
+    tri = torch.full((F, height, width), -1, dtype=torch.int32, device=dev)
+    bary = torch.zeros((F, height, width, 3), dtype=torch.float32, device=dev)
+    visible = torch.empty((F, n), dtype=torch.uint8, device=dev)
+    _raster_triangles(model, meshes, F, planar, depth, tri, bary, height, width)
+    with torch.cuda.device(dev):
+        abi.check(model._lib.syn_vertex_visibility(model._h, tri.data_ptr(), F, height, width, visible.data_ptr(), model._stream()))
+    return depth, tri, bary, visible
+
+
+def visibility_batch(model, meshes, height, width):
+    """Visibility buffers of F meshes on the device: meshes [F,3,N] float32 device tensor in image coordinates (what
+    reconstruct(..., dense=True) returns; pitched rows are read in place), topology = the model's `triangles`, uploaded once.
+    Returns (depth [F,H,W] float32, -1e8 where nothing was drawn; tri [F,H,W] int32, -1 there; bary [F,H,W,3] float32, 0 there;
+    visible [F,N] bool: the vertex is a corner of a triangle that won a pixel)."""
+    depth, tri, bary, visible = _visibility(model, meshes, int(height), int(width))
+    return depth, tri, bary, visible.view(torch.bool)
+
+
+def _frame(model, img):
+    t = (img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img)))
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] > 4:
+        raise TypeError('img must be uint8 [H,W,ch] with ch <= 4')
+    return t.to(model.device).contiguous()
+
+
+def vertex_colors_from_image(model, img, meshes, normalize=False):
+    """One colour per vertex from a frame: img uint8 [H,W,ch] (array or device tensor), meshes [F,3,N] float32 device tensor in the
+    frame's pixel coordinates.  Bilinear sample at the vertex' (x, y), clamped to the frame, in the float32 operation order of the
+    reference's bilinear code (rasterize_kernel.cpp:428-447).  Returns a float32 device tensor [F,N,ch], 0..255 or / 255 with
+    normalize=True; a vertex with a non-finite coordinate gets 0."""
+    F, _, n = meshes.shape
+    _ensure_model_topology(model, n)
+    planar = _planar_arg(meshes)
+    img_t = _frame(model, img)
+    H, W, ch = img_t.shape
+    out = torch.empty((F, n, ch), dtype=torch.float32, device=model.device)
+    with torch.cuda.device(model.device):
+        abi.check(model._lib.syn_sample_vertex_colors(model._h, meshes.data_ptr(), F, planar, img_t.data_ptr(), H, W, ch,
+                                                      int(bool(normalize)), out.data_ptr(), model._stream()))
+    return out
+
+
+def texture_from_image(model, img, meshes, tex_hw=256, occlusion=True):
+    """From a photograph and the meshes reconstructed from it to UV texture images: every vertex takes its colour from the frame
+    (vertex_colors_from_image) and writes it to its texel of the model's UV map (param_pack.uv_vert), the inverse of
+    uv_vertex_colors.  occlusion=True writes only the vertices visibility_batch finds visible at the frame's size; texels no
+    vertex writes stay 0 (no hole filling).  Where vertices share a texel the highest vertex index wins.
+    tex_hw: texture size, an int or (height, width).  Returns (uv_tex uint8 [F,th,tw,ch], mask uint8 [F,th,tw], 255 where written),
+    device tensors; uv_tex is what render_batch(uv_tex=) and uv_vertex_colors take.  Nothing is downloaded in between."""
+    F, _, n = meshes.shape
+    n_vert, _ = _ensure_uv_map(model)
+    if n != n_vert:
+        raise ValueError(f'meshes have {n} vertices, the UV map {n_vert}')
+    th, tw = (int(tex_hw), int(tex_hw)) if np.isscalar(tex_hw) else (int(tex_hw[0]), int(tex_hw[1]))
+    img_t = _frame(model, img)
+    H, W, ch = img_t.shape
+    colors = vertex_colors_from_image(model, img_t, meshes)
+    visible = _visibility(model, meshes, H, W)[3] if occlusion else None
+    tex = torch.empty((F, th, tw, ch), dtype=torch.uint8, device=model.device)
+    mask = torch.empty((F, th, tw), dtype=torch.uint8, device=model.device)
+    with torch.cuda.device(model.device):
+        abi.check(model._lib.syn_uv_scatter(model._h, colors.data_ptr(), visible.data_ptr() if visible is not None else None, F, ch,
+                                            tex.data_ptr(), mask.data_ptr(), th, tw, model._stream()))
+    return tex, mask
+
+
 def get_normal(vertices, triangles):
     """Sim3DR/Sim3DR.py:8-11: vertices [nver,3] float32, triangles [ntri,3] int32 -> normals [nver,3] float32."""
     m = _model()
@@ -320,11 +436,7 @@ def render_batch(model, img, meshes, alpha=0.6, cfg=None, uv_tex=None, tex=None)
         _select(model, 1)
         return _render_textured(model, img, kept, tex, alpha, pipe)
     F, _, n = meshes.shape
-    if getattr(model, '_tri_obj', None) is not model.triangles or getattr(model, '_tri_key', (None, None))[1] != n:
-        t = np.asarray(model.triangles)                  # the class attribute is [3,ntri] (synergy3DMM.py:105), Sim3DR wants [ntri,3]
-        _ensure_topology(model, np.ascontiguousarray(t.T if t.shape[0] == 3 else t), n)
-        model._tri_obj = model.triangles                 # same object next time: skip the host-side comparison
-    _select(model, 0)
+    _ensure_model_topology(model, n)
     planar = _planar_arg(meshes)       # the pitched rows reconstruct() writes are read in place: no packed copy on the device path
     with torch.cuda.device(model.device):
         _, light = _shade(model, meshes, planar=planar, cfg=_cfg16(pipe))
