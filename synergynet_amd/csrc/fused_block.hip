@@ -107,11 +107,7 @@ __global__ __launch_bounds__(C::NW * 64) void fused_block_kernel(
     float *Wle = Wds + C::WD_FLOATS, *Wlp = Wle + C::WE_FLOATS, *Ebn = Wlp + C::WP_FLOATS;   // only carved when WLDS
     constexpr int NT = C::NT;
     const int tid = threadIdx.x, lane = tid & 63;
-#ifdef SYN_NO_RFL
-    const int wave = tid >> 6;
-#else
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: branches on it stay scalar
-#endif
     const int r16 = lane & 15, g = lane >> 4;
     const int wn = wave % C::WN, wp = wave / C::WN;
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};

@@ -138,16 +138,6 @@ struct LbCfg {
     static_assert((FPW == 4 || NS >= 4 ? 1 : 2) * LDS_DW * 4 <= 160 * 1024, "one 8-wave or two 4-wave workgroups per CU");
 };
 
-#ifndef SYN_LB_SHADOW
-#define SYN_LB_SHADOW 0               // 1: channel tile 1's expand MFMAs inside depthwise passes 0 / 1 (in-wave MFMA shadow: the round-6 experiment,
-                                     //    measured 252.9 against 249.0 us for the features.7-14 chain -- profiles/r6/mfma_shadow_experiment.txt); 0: rounds 2-5
-#endif
-#ifndef SYN_LB_SHADOW_PIN
-#define SYN_LB_SHADOW_PIN 7           // vector instructions pinned behind each shadowed MFMA (sched_group_barrier); 0: the compiler's own order
-#endif
-#ifndef SYN_LB_DW2
-#define SYN_LB_DW2 1                // 0: lane shifts on the input rows (rounds 2-4), for A/B runs
-#endif
 // compiler fence between the phases of a hidden group: without it every load of a group is hoisted to the top of the loop body
 // and unchained arithmetic floats across the scheduling barriers (~370 registers live)
 #define SYNL_FENCE() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -311,24 +301,8 @@ __device__ __forceinline__ void lb_stage(unsigned *smem, const LbStageArgs &sa, 
 #pragma unroll
             for (int r = 0; r < 4; ++r) D[t][r] = es;
         }
-        // SYN_LB_SHADOW (round 6, VERDICT r5 #3 -- the in-wave interleave experiment): channel tile 0 of the group is expanded first (all k32 steps,
-        // four blocks = four accumulator chains); tile 1's 12 MFMAs per k32 step ride INSIDE depthwise passes 0 and 1 -- which read tile 0 only --
-        // so that this wave's vector instructions issue in the shadow of its own matrix instructions (tools/ubench/mfma_interleave.hip: two
-        // plain VALU hide behind a 16-cycle MFMA inside one wave).  No register of another group is needed; the block-input fragments are read
-        // twice.  Stages with EPF == KE == 2 (features.8-11).
-        constexpr bool SHADOW = SYN_LB_SHADOW && C::EPF == KE && KE == 2 && !C::S2;
-        auto expand_unit = [&](int kc, int t) __attribute__((always_inline)) {       // one k32 step of one channel tile: 12 MFMAs on D[t][0..3]
-            u32x4 Bx[4][2];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int p = 0; p < 2; ++p) Bx[r][p] = *(const u32x4 *)&Xf[((kc * 4 + r) * 2 + p) * 256 + lane * 4];
-            mac3x4(Ae[kc][t], Bx[0], D[t][0], Ae[kc][t], Bx[1], D[t][1], Ae[kc][t], Bx[2], D[t][2], Ae[kc][t], Bx[3], D[t][3]);
-        };
-        if constexpr (SHADOW) {
-#pragma unroll
-            for (int kc = 0; kc < KE; ++kc) { expand_unit(kc, 0); SYNL_FENCE(); }
-        } else {
+        // (both channel tiles of the group are expanded here, in front of the depthwise.  Running tile 1's MFMAs inside depthwise passes 0 / 1,
+        // in the shadow of this wave's own vector work, was the round-6 negative: profiles/r6/mfma_shadow_experiment.txt)
 #pragma unroll
         for (int kc = 0; kc < KE; ++kc) {
             if (kc + C::EPF < KE) fetch_e(G, kc + C::EPF);
@@ -344,12 +318,10 @@ __device__ __forceinline__ void lb_stage(unsigned *smem, const LbStageArgs &sa, 
                 SYNL_FENCE();
             }
         }
-        }
         // EPF == KE: the next group's expand fragments are requested HERE, into the registers the expand just stopped reading -- the depthwise
         // phase (~1600 cycles) and the project stand between the request and its use instead of the project alone (~800 cycles against an L2
         // round trip of about that: with the loads replaced by constants the chain runs 270 -> 252 us, this placement gets 6 of those 18)
-        // (SHADOW: after depthwise pass 1, when tile 1 has stopped reading them)
-        if (!SHADOW && C::EPF == KE && G + C::NS < gend) {
+        if (C::EPF == KE && G + C::NS < gend) {
 #pragma unroll
             for (int kc = 0; kc < C::EPF; ++kc) fetch_e(G + C::NS, kc);
         }
@@ -368,19 +340,12 @@ __device__ __forceinline__ void lb_stage(unsigned *smem, const LbStageArgs &sa, 
         for (int th = 0; th < 4; ++th) {
             const int t = th >> 1, hf = th & 1;
             if (th == 3) fetch_p(0);                    // first project fragments: in flight behind the last depthwise pass
-            if constexpr (SHADOW) {
-                if (th < 2) expand_unit(th, 1);        // tile 1, k32 step th: its MFMAs interleave with this pass's vector work (pattern below)
-                if (th == 2 && G + C::NS < gend) {
-#pragma unroll
-                    for (int kc = 0; kc < C::EPF; ++kc) fetch_e(G + C::NS, kc);
-                }
-            }
             const int c0 = 16 * t + 2 * hf;             // + 4 g per lane group
             f32x2 w[9];
 #pragma unroll
             for (int k = 0; k < 9; ++k) w[k] = *(const f32x2 *)&Tb[k * 32 + c0 + g4];
             const f32x2 dsh = *(const f32x2 *)&Tb[9 * 32 + c0 + g4];
-            if (C::S2 || !SYN_LB_DW2) {
+            if (C::S2) {
 #pragma unroll
                 for (int dy = 0; dy < 3; ++dy) { w[3 * dy] *= mL; w[3 * dy + 2] *= mR; }
             }
@@ -405,48 +370,27 @@ __device__ __forceinline__ void lb_stage(unsigned *smem, const LbStageArgs &sa, 
                 O[0] += dpp2<kRowShr1>(E[3]) * w[6];
                 O[0] += E[2] * w[7];
                 O[0] = pk_fma_clamp01(E[3], w[8], O[0]);
-            } else if (SYN_LB_DW2) {
-            // Round 5: the lane shifts move from the INPUT rows to the OUTPUT rows.  A lane shift commutes with the per-channel filter weight, so
-            //   out[r] = B + mL L(A) + mR R(C),   A / B / C = sum over dy of (left / centre / right filter column) x in[r + dy - 1]
-            // needs two shifts per output row (4 rows) where shifting every input row needs two per input row (6 rows: the block's four and the two
-            // halo rows): 20 instead of 28 lane shifts per channel pair, and the image border is a multiplier of the shifted SUM (no filter masking).
-            // Another summation order than rounds 2-4 (dx outermost): same arithmetic class.
-            const f32x2 mL2 = {mL, mL}, mR2 = {mR, mR};
-            f32x2 rowT = E[3], rowB = E[0];
-            asm volatile("" : "+v"(rowT), "+v"(rowB));
-            rowT = dpp2<kRowShr8>(rowT);                 // image row -1 of the block columns (zero fill = the border)
-            rowB = dpp2<kRowShl8>(rowB);                 // image row 4
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const f32x2 &i0 = r == 0 ? rowT : E[r - 1], &i1 = E[r], &i2 = r == 3 ? rowB : E[r + 1];
-                f32x2 A = i0 * w[0], Cc = i0 * w[2], Bc = O[r] + i0 * w[1];
-                A += i1 * w[3]; Bc += i1 * w[4]; Cc += i1 * w[5];
-                A += i2 * w[6]; Bc += i2 * w[7]; Cc += i2 * w[8];
-                Bc += dpp2<kRowShr1>(A) * mL2;
-                O[r] = pk_fma_clamp01(dpp2<kRowShl1>(Cc), mR2, Bc);
-                asm volatile("" : "+v"(O[r]));           // (one output row at a time: three column sums live, not twelve)
-            }
             } else {
-            // input rows q = -1 .. 4 of the block rows (row q feeds outputs q - dy, dy = 0..2: ascending dy per output).  The pins
-            // chain the rows: unchained arithmetic is otherwise scheduled all rows at once.
+                // Round 5: the lane shifts move from the INPUT rows to the OUTPUT rows.  A lane shift commutes with the per-channel filter weight, so
+                //   out[r] = B + mL L(A) + mR R(C),   A / B / C = sum over dy of (left / centre / right filter column) x in[r + dy - 1]
+                // needs two shifts per output row (4 rows) where shifting every input row needs two per input row (6 rows: the block's four and the two
+                // halo rows): 20 instead of 28 lane shifts per channel pair, and the image border is a multiplier of the shifted SUM (no filter masking).
+                // Another summation order than rounds 2-4 (dx outermost): same arithmetic class.
+                const f32x2 mL2 = {mL, mL}, mR2 = {mR, mR};
+                f32x2 rowT = E[3], rowB = E[0];
+                asm volatile("" : "+v"(rowT), "+v"(rowB));
+                rowT = dpp2<kRowShr8>(rowT);                 // image row -1 of the block columns (zero fill = the border)
+                rowB = dpp2<kRowShl8>(rowB);                 // image row 4
 #pragma unroll
-            for (int q = 0; q < 6; ++q) {
-                f32x2 &src = E[q == 0 ? 3 : (q == 5 ? 0 : q - 1)];
-                asm volatile("" : "+v"(src));
-                const f32x2 c = q == 0 ? dpp2<kRowShr8>(src) : (q == 5 ? dpp2<kRowShl8>(src) : src);
-                const f32x2 l = dpp2<kRowShr1>(c), rt = dpp2<kRowShl1>(c);
-#pragma unroll
-                for (int dy = 2; dy >= 0; --dy) {
-                    const int r = q - dy;
-                    if (r < 0 || r > 3) continue;
-                    O[r] += l * w[3 * dy];
-                    O[r] += c * w[3 * dy + 1];
-                    // dy == 2 (input row r + 2) is the last kernel row an output row receives: its last FMA clamps
-                    if (dy == 2) O[r] = pk_fma_clamp01(rt, w[3 * dy + 2], O[r]);
-                    else O[r] += rt * w[3 * dy + 2];
-                    asm volatile("" : "+v"(O[r]));
+                for (int r = 0; r < 4; ++r) {
+                    const f32x2 &i0 = r == 0 ? rowT : E[r - 1], &i1 = E[r], &i2 = r == 3 ? rowB : E[r + 1];
+                    f32x2 A = i0 * w[0], Cc = i0 * w[2], Bc = O[r] + i0 * w[1];
+                    A += i1 * w[3]; Bc += i1 * w[4]; Cc += i1 * w[5];
+                    A += i2 * w[6]; Bc += i2 * w[7]; Cc += i2 * w[8];
+                    Bc += dpp2<kRowShr1>(A) * mL2;
+                    O[r] = pk_fma_clamp01(dpp2<kRowShl1>(Cc), mR2, Bc);
+                    asm volatile("" : "+v"(O[r]));           // (one output row at a time: three column sums live, not twelve)
                 }
-            }
             }
 #pragma unroll
             for (int r = 0; r < NB; ++r) {
@@ -454,15 +398,6 @@ __device__ __forceinline__ void lb_stage(unsigned *smem, const LbStageArgs &sa, 
                 if (hf) {
 #pragma unroll
                     for (int p = 0; p < 2; ++p) asm volatile("" : "+v"(Bd[r][p]));
-                }
-            }
-            if constexpr (SHADOW && SYN_LB_SHADOW_PIN > 0) {
-                if (th < 2) {                           // 12 x (1 MFMA, SYN_LB_SHADOW_PIN vector instructions): the pass's ~95 VALU spread under the MFMAs
-#pragma unroll
-                    for (int i = 0; i < 12; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, SYN_LB_SHADOW_PIN, 0);
-                    }
                 }
             }
             SYNL_FENCE();
@@ -1113,14 +1048,8 @@ void fused_block_lb_kernel(LbStageArgs sa, int B, unsigned long long *prof = nul
 }
 
 //                    CIN  HID COUT  RES  EPF PPF
-#ifndef SYN_L8_PPF
-#define SYN_L8_PPF 3
-#endif
-#ifndef SYN_L11_PPF
-#define SYN_L11_PPF 3
-#endif
-using L8 = LbCfg<      64, 384,  64, true,  2, SYN_L8_PPF>;     // features.8-10
-using L11 = LbCfg<     64, 384,  96, false, 2, SYN_L11_PPF>;     // features.11
+using L8 = LbCfg<      64, 384,  64, true,  2, 3>;     // features.8-10
+using L11 = LbCfg<     64, 384,  96, false, 2, 3>;     // features.11
 using L12 = LbCfg<     96, 576,  96, true,  1, 3>;     // features.12, 13
 using L14 = LbCfg<     96, 576, 160, false, 1, 2, 2, true>;   // features.14 (stride 2: 8x8 -> 4x4)
 
@@ -1134,9 +1063,6 @@ static_assert(L8::FACE_DW <= kChainFaceDw && L11::FACE_DW <= kChainFaceDw && L12
 constexpr int kChainLdsDw = L8::FPW * kChainFaceDw + L8::NW * L8::TB_DW;
 static_assert(2 * kChainLdsDw * 4 <= 160 * 1024, "two workgroups per CU");
 
-#ifndef SYN_L2_TOUCH
-#define SYN_L2_TOUCH 1              // 0: no L2 warm-up of the weight fragments (A/B)
-#endif
 // one stage's expand fragments, project fragments and per-group tables (the layouts fetch_e / fetch_p / fetch_t walk)
 template <int NG, int KE, int MT>
 __device__ __forceinline__ void lb_touch_stage(const LbStageArgs &sa, unsigned gi, unsigned nth, unsigned &sink) {
@@ -1148,25 +1074,20 @@ template <bool WITH7, bool WITH14>
 __global__ __launch_bounds__(L8::NT) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void fused_chain_lb_kernel(LbChainArgs ca, int B) {
     unsigned long long pt_[5] = {0, 0, 0, 0, 0}, tk = 0;
-#ifndef SYN_LB_LDS_PAD
-#define SYN_LB_LDS_PAD 0              // experiment knob: extra LDS dwords (22000: one workgroup per CU = ONE wave per SIMD)
-#endif
-    __shared__ __attribute__((aligned(16))) unsigned smem[kChainLdsDw + SYN_LB_LDS_PAD];
+    __shared__ __attribute__((aligned(16))) unsigned smem[kChainLdsDw];
     // every stage's weights (2.6 MB for features.7-14) into this XCD's L2 before the walk starts (syn_internal.h l2_touch): the waves fetch their
     // fragments one group ahead, which covers an L2 hit but not the miss the first CU of an XCD takes on every group of a cold run
     // (B = 1024, interleaved on one box: 267.0 against 271.6 us without, gpurun_out/r5c3)
     unsigned sink = 0;
-    if (SYN_L2_TOUCH) {
-        const unsigned gi = (blockIdx.x >> 3) * (unsigned)L8::NT + threadIdx.x, nth = ((gridDim.x + 7) >> 3) * (unsigned)L8::NT;
-        if (WITH7) lb_touch_stage<L7::NG, 1, L7::MT>(ca.s[0], gi, nth, sink);
-        lb_touch_stage<L8::NG, L8::KE, L8::MT>(ca.s[1], gi, nth, sink);
-        lb_touch_stage<L8::NG, L8::KE, L8::MT>(ca.s[2], gi, nth, sink);
-        lb_touch_stage<L8::NG, L8::KE, L8::MT>(ca.s[3], gi, nth, sink);
-        lb_touch_stage<L11::NG, L11::KE, L11::MT>(ca.s[4], gi, nth, sink);
-        lb_touch_stage<L12::NG, L12::KE, L12::MT>(ca.s[5], gi, nth, sink);
-        lb_touch_stage<L12::NG, L12::KE, L12::MT>(ca.s[6], gi, nth, sink);
-        if (WITH14) lb_touch_stage<L14::NG, L14::KE, L14::MT>(ca.s[7], gi, nth, sink);
-    }
+    const unsigned gi = (blockIdx.x >> 3) * (unsigned)L8::NT + threadIdx.x, nth = ((gridDim.x + 7) >> 3) * (unsigned)L8::NT;
+    if (WITH7) lb_touch_stage<L7::NG, 1, L7::MT>(ca.s[0], gi, nth, sink);
+    lb_touch_stage<L8::NG, L8::KE, L8::MT>(ca.s[1], gi, nth, sink);
+    lb_touch_stage<L8::NG, L8::KE, L8::MT>(ca.s[2], gi, nth, sink);
+    lb_touch_stage<L8::NG, L8::KE, L8::MT>(ca.s[3], gi, nth, sink);
+    lb_touch_stage<L11::NG, L11::KE, L11::MT>(ca.s[4], gi, nth, sink);
+    lb_touch_stage<L12::NG, L12::KE, L12::MT>(ca.s[5], gi, nth, sink);
+    lb_touch_stage<L12::NG, L12::KE, L12::MT>(ca.s[6], gi, nth, sink);
+    if (WITH14) lb_touch_stage<L14::NG, L14::KE, L14::MT>(ca.s[7], gi, nth, sink);
     if constexpr (WITH7) {
         lb7_stage<L8, false, kChainFaceDw>(smem, ca.s[0], B, pt_, tk);
         lb_stage<L8, L8, false, false, kChainFaceDw>(smem, ca.s[1], B, pt_, tk);
@@ -1181,7 +1102,7 @@ void fused_chain_lb_kernel(LbChainArgs ca, int B) {
         lb_stage<L14, void, false, false, kChainFaceDw>(smem, ca.s[7], B, pt_, tk);
     } else
         lb_stage<L12, void, false, false, kChainFaceDw>(smem, ca.s[6], B, pt_, tk);
-    if (SYN_L2_TOUCH) l2_touch_done(sink);
+    l2_touch_done(sink);
 }
 
 // Small batches (round 4; BASELINE configs[1] is 128 faces): features.8 .. 14 (round 5: 7 .. 14) as ONE launch with ONE face per workgroup.  Below
@@ -1196,22 +1117,15 @@ constexpr int cmax4(int a, int b, int c, int d) { return (a > b ? a : b) > (c > 
 // SIMD's two waves cover each other's round trips, a wave walks 1-3 groups per block instead of 3-5, and the partial sums meet in two
 // levels (streams 4 .. 7 into 0 .. 3, then as above).  Landmarks-only step, four -> eight streams (ms, interleaved on one box): B = 1 0.244 -> 0.225,
 // 8 0.265 -> 0.245, 64 0.300 -> 0.281, 128 0.330 -> 0.310, 256 0.429 -> 0.409.
-using L8e = LbCfg<     64, 384,  64, true,  2, SYN_L8_PPF, 1, false, 8>;
-using L11e = LbCfg<    64, 384,  96, false, 2, SYN_L11_PPF, 1, false, 8>;
+using L8e = LbCfg<     64, 384,  64, true,  2, 3, 1, false, 8>;
+using L11e = LbCfg<    64, 384,  96, false, 2, 3, 1, false, 8>;
 using L12e = LbCfg<    96, 576,  96, true,  1, 3, 1, false, 8>;
 using L14e = LbCfg<    96, 576, 160, false, 1, 2, 1, true, 8>;
-constexpr int kChainFaceDwE = cmax4(L8e::FACE_DW, L11e::FACE_DW, L12e::FACE_DW, L14e::FACE_DW);
-constexpr int kChainLdsDwE = L8e::FPW * kChainFaceDwE + L8e::NW * L8e::TB_DW;
-static_assert(kChainLdsDwE * 4 <= 160 * 1024, "one workgroup per CU");
-
-static_assert(L7::XF_DW <= kChainFaceDwE, "features.7's class fragments fit the chain's face buffer");
-#ifndef SYN_SMALL8_SPLIT
-#define SYN_SMALL8_SPLIT 1             // fragments | exchange buffer side by side, four barriers per stage instead of six (0: the aliased buffer of round 4, for A/B runs)
-#endif
+// fragments | exchange buffer side by side (lb_stage RED_OFF): four barriers per stage instead of the six of one aliased buffer
 constexpr int kChainXfDwE = cmax4(L7::XF_DW, L8e::XF_DW, L12e::XF_DW, L14e::XF_DW);
 constexpr int kChainRedDwE = cmax4(L8e::RED_DW, L11e::RED_DW, L12e::RED_DW, L14e::RED_DW);
-constexpr int kRedOffE = SYN_SMALL8_SPLIT ? kChainXfDwE : 0;
-constexpr int kFaceDwE = SYN_SMALL8_SPLIT ? kChainXfDwE + kChainRedDwE : kChainFaceDwE;
+constexpr int kRedOffE = kChainXfDwE;
+constexpr int kFaceDwE = kChainXfDwE + kChainRedDwE;
 constexpr int kLdsDwE = kFaceDwE + L8e::NW * L8e::TB_DW;
 static_assert(kLdsDwE * 4 <= 160 * 1024, "one workgroup per CU");
 template <bool WITH7 = false>

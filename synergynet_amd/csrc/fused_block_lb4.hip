@@ -98,26 +98,13 @@ struct Lb4StageArgs {
     int g0 = 0, g1 = 0;      // hidden groups [g0, g1) of this workgroup's slice (g1 = 0: all); slice = blockIdx.y
 };
 
-// SYN_LB4_ABL: TIMING-ONLY ablations (wrong results; tools/build_variant.sh): 1 no weight fetch from L2 | 2 no park into LDS | 4 no exchange
-// barrier | 8 no project-fragment LDS reads | 16 no depthwise arithmetic | 32 no group barrier
-#ifndef SYN_LB4_ABL
-#define SYN_LB4_ABL 0
-#endif
 template <int N>
 __device__ __forceinline__ void lb4_fetch(u32x4 *pf, const unsigned *src /* + 4 lane */, int wave) {
 #pragma unroll
-    for (int i = 0; i < N; ++i) {
-        if (SYN_LB4_ABL & 1) { pf[i] = (u32x4){(unsigned)wave, 1u, 2u, 3u}; asm volatile("" : "+v"(pf[i])); }
-        else pf[i] = *(const u32x4 *)(src + (wave + 8 * i) * 256);
-    }
+    for (int i = 0; i < N; ++i) pf[i] = *(const u32x4 *)(src + (wave + 8 * i) * 256);
 }
 template <int N>
 __device__ __forceinline__ void lb4_park(const u32x4 *pf, unsigned *dst /* + 4 lane */, int wave) {
-    if (SYN_LB4_ABL & 2) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) asm volatile("" :: "v"(pf[i]));
-        return;
-    }
 #pragma unroll
     for (int i = 0; i < N; ++i) *(u32x4 *)&dst[(wave + 8 * i) * 256] = pf[i];
 }
@@ -185,18 +172,16 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
         c6e = t0[11 * 32]; inv_p = t0[11 * 32 + 1];
     }
     for (int G = gb; G < ge; ++G) {
-        if (!(SYN_LB4_ABL & 32)) __syncthreads();        // every wave has written its pieces of group G and is done with group G-1
+        __syncthreads();                                 // every wave has written its pieces of group G and is done with group G-1
         if (G + 1 < ge) lb4_fetch<NPW>(pf, Glb + (size_t)(G + 1) * C::GRP_DW + l4, wave);
         else if (HANDOFF) lb4_fetch<NPWN>(pf, GlbNext + l4, wave);          // the next block's first group
         const unsigned *We = smem + ((G - gb) & 1) * GRPL, *Wp = We + C::WE_DW;
         const float *Tb = reinterpret_cast<const float *>(Wp + C::WP_DW);
-#ifndef SYN_LB4_V1
         __builtin_amdgcn_sched_barrier(0);               // the next group's fetch stays in front of this group's LDS reads
-#endif
         // fragments of this wave.  Round 5: the eight waves read 22 KB each here, the LDS delivers 128 bytes per cycle, and the expand chain
         // used to wait for ALL of it (the project fragments were pinned in front of it): ~1400 cycles per group in which nothing else ran.
         // Now only the expand fragments and the group's constants stand in front of the expand chain; the project fragments are requested
-        // behind it and land during the depthwise arithmetic, which leaves the LDS idle.  (SYN_LB4_V1: the old order, for A/B runs.)
+        // behind it and land during the depthwise arithmetic, which leaves the LDS idle.
         u32x4 Ae[KE][2], Ap[MTW][2];
         // (the LDS returns in order: the accumulator's start value first, then the fragments in the order the chain consumes them, then the filter)
         f32x4 D = *(const f32x4 *)&Tb[10 * 32 + 16 * t + g4];
@@ -205,12 +190,6 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
 #pragma unroll
             for (int p = 1; p >= 0; --p) Ae[kc][p] = *(const u32x4 *)&We[((t * KE + kc) * 2 + p) * 256 + l4];
         constexpr int MTW0 = MTW > 5 ? MTW / 2 : MTW;    // (320 output channels: the second half of the project fragments after the exchange)
-#ifdef SYN_LB4_V1
-#pragma unroll
-        for (int i = 0; i < MTW0; ++i)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) Ap[i][p] = *(const u32x4 *)&Wp[((t * MTW + i) * 2 + p) * 256 + l4];
-#else
         // depthwise filter, its BN shift: two channels x two halves per lane group, requested with the expand fragments
         f32x2 wt[2][9], dsht[2];
 #pragma unroll
@@ -219,63 +198,34 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
             for (int k = 0; k < 9; ++k) wt[hf][k] = *(const f32x2 *)&Tb[k * 32 + 16 * t + 2 * hf + g4];
             dsht[hf] = *(const f32x2 *)&Tb[9 * 32 + 16 * t + 2 * hf + g4];
         }
-#endif
         // ---- expand 1x1 + BN shift: D = channels 32 G + 16 t + 4 g + i of pixel n (three partial products, smallest first) ----
-#ifndef SYN_LB4_V1
         __builtin_amdgcn_sched_barrier(0);               // every read above is issued before the first matrix instruction (the LDS returns in order: counted waits)
-#endif
 #pragma unroll
         for (int kc = 0; kc < KE; ++kc) {
             D = mfmaq(Ae[kc][1], Xr[kc][0], D);
             D = mfmaq(Ae[kc][0], Xr[kc][1], D);
             D = mfmaq(Ae[kc][0], Xr[kc][0], D);
         }
-#ifdef SYN_LB4_V1
-#pragma unroll
-        for (int i = 0; i < MTW0; ++i)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) asm volatile("" : "+v"(Ap[i][p]));      // (keeps these reads up here instead of next to their MFMAs)
-#else
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < MTW0; ++i)
 #pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                if (SYN_LB4_ABL & 8) Ap[i][p] = Ae[i % KE][p];
-                else Ap[i][p] = *(const u32x4 *)&Wp[((t * MTW + i) * 2 + p) * 256 + l4];
-            }
+            for (int p = 0; p < 2; ++p) Ap[i][p] = *(const u32x4 *)&Wp[((t * MTW + i) * 2 + p) * 256 + l4];
         __builtin_amdgcn_sched_barrier(0);
-#endif
         // ---- ReLU6, depthwise 3x3 + BN shift + ReLU6 on the registers, split into this wave's half of the project operand ----
         u32x4 own;                                      // {piece 0 dwords hf 0, 1 | piece 1 dwords hf 0, 1}
-        if (SYN_LB4_ABL & 16) own = __builtin_bit_cast(u32x4, D);
-        else
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-#ifdef SYN_LB4_V1
-            const int c0 = 16 * t + 2 * hf;             // + 4 g per lane group
-            f32x2 w[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) w[k] = *(const f32x2 *)&Tb[k * 32 + c0 + g4];
-            const f32x2 dsh = *(const f32x2 *)&Tb[9 * 32 + c0 + g4];
-#pragma unroll
-            for (int dy = 0; dy < 3; ++dy) { w[3 * dy] *= mL; w[3 * dy + 2] *= mR; }
-#else
             const f32x2 (&w)[9] = wt[hf];
             const f32x2 dsh = dsht[hf];
-#endif
             f32x2 E;
             // ReLU6 as clamp modifiers (fused_block_lb.hip): E = relu6 / 6 = clamp(D / (96 Se)); the last add of the output clamps too
             E[0] = __builtin_amdgcn_fmed3f(D[2 * hf] * c6e, 0.0f, 1.0f);
             E[1] = __builtin_amdgcn_fmed3f(D[2 * hf + 1] * c6e, 0.0f, 1.0f);
             // horizontal first (two lane shifts), then the three row sums shifted vertically (two more): 8 DPP moves per channel pair
             // instead of 16.  (Summation order differs from the other kernels': dx inside dy inside the vertical sum.)
-#ifdef SYN_LB4_V1
-            const f32x2 l = dppq2<kShr1>(E), rt = dppq2<kShl1>(E);
-#else
             // the image border in x: the shifted VALUE is zeroed (two multiplies) instead of six filter entries -- the same products, bit for bit
             const f32x2 l = dppq2<kShr1>(E) * mL, rt = dppq2<kShl1>(E) * mR;
-#endif
             f32x2 H[3];
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
@@ -295,7 +245,7 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
         }
         // ---- the partner's half: K slots 0-3 of a lane group are tile 0's channels, 4-7 tile 1's ----
         *(u32x4 *)&Xch[((fl * 2 + t) * 64 + lane) * 4] = own;
-        if (!(SYN_LB4_ABL & 4)) __syncthreads();
+        __syncthreads();
         const u32x4 oth = *(const u32x4 *)&Xch[((fl * 2 + (1 - t)) * 64 + lane) * 4];
 #pragma unroll
         for (int i = MTW0; i < MTW; ++i)
@@ -398,30 +348,17 @@ constexpr int kChain4LdsDw = 2 * kChain4Grp + Q15::XCH_DW;
 static_assert(kChain4LdsDw * 4 <= 160 * 1024 && 4 * 5 * 2 * 256 <= kChain4Grp, "LDS budget; the handed-over fragments of four faces fit one buffer half");
 struct Lb4ChainArgs { Lb4StageArgs s[3]; };
 
-// L2 warm-up of the three weight runs at kernel start (syn_internal.h l2_touch): measured SLOWER here -- 167.4 against 163.3 us, interleaved on one
-// box (gpurun_out/r5c3), while the same touch gains 4.5 us in the features.7-14 chain: this kernel's groups are paced by the LDS (224 KB through
-// it per group) and its two barriers, not by where the weight lines come from.  Off; SYN_LB4_L2_TOUCH=1 builds it for A/B runs.
-#ifndef SYN_LB4_L2_TOUCH
-#define SYN_LB4_L2_TOUCH 0
-#endif
-#define SYN_L2_TOUCH SYN_LB4_L2_TOUCH
+// No L2 warm-up of the three weight runs at kernel start (syn_internal.h l2_touch), although the same touch gains 4.5 us in the features.7-14
+// chain: this kernel's groups are paced by the LDS (224 KB through it per group) and its two barriers, not by where the weight lines come from
+// (round-5 negative, 167.4 against 163.3 us: docs/history.md).
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void fused_chain_lb4_kernel(Lb4ChainArgs ca, int B) {
     __shared__ __attribute__((aligned(16))) unsigned smem[kChain4LdsDw];
     u32x4 Xr[5][2];
     f32x4 vres[5];
-    // the three blocks' weight runs (1.2 + 1.2 + 1.8 MB) into this XCD's L2 before the first group is needed (syn_internal.h l2_touch)
-    unsigned sink = 0;
-    if (SYN_L2_TOUCH) {
-        const unsigned gi = (blockIdx.x >> 3) * 512u + threadIdx.x, nth = ((gridDim.x + 7) >> 3) * 512u;
-        l2_touch(ca.s[0].Glb, Q15::NG * Q15::GRP_DW * 4u, gi, nth, sink);
-        l2_touch(ca.s[1].Glb, Q15::NG * Q15::GRP_DW * 4u, gi, nth, sink);
-        l2_touch(ca.s[2].Glb, Q17::NG * Q17::GRP_DW * 4u, gi, nth, sink);
-    }
     lb4_stage<Q15, Q15, true, kChain4Grp>(smem, ca.s[0], ca.s[1].Glb, B, Xr, vres);
     lb4_stage<Q15, Q17, false, kChain4Grp>(smem, ca.s[1], ca.s[2].Glb, B, Xr, vres);
     lb4_stage<Q17, void, false, kChain4Grp>(smem, ca.s[2], nullptr, B, Xr, vres);
-    if (SYN_L2_TOUCH) l2_touch_done(sink);
 }
 
 template <class C>

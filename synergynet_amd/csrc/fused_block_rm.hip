@@ -170,53 +170,43 @@ __device__ __forceinline__ void rm_block(unsigned *smem, const float *__restrict
     else { ia = j >> 4; icol[0] = 2 * (j & 15) - 1; icol[C::NB - 1] = 2 * (j & 15); oa = j >> 4; ocol = j & 15; }
     // Round 5: what the first row step needs from global memory is requested BEFORE the constants are staged (another round trip to L2 / HBM
     // behind a barrier): the compute waves' weight fragments, and -- as touches whose data is dropped -- the first two input rows of the first unit
-    // of the row-staging service waves (their real loads then hit the cache).  SYN_RM_EARLY=0: the old order.
-#ifndef SYN_RM_EARLY
-#define SYN_RM_EARLY 1
-#endif
+    // of the row-staging service waves (their real loads then hit the cache).
     u32x4 ae[C::KS][2], ap[2][2];
     unsigned early_sink = 0;
-    if (SYN_RM_EARLY) {
-        if (!service) {
+    if (!service) {                             // this wave's weight fragments stay in registers for the whole (persistent) kernel
 #pragma unroll
-            for (int s = 0; s < C::KS; ++s)
+        for (int s = 0; s < C::KS; ++s)
 #pragma unroll
-                for (int p = 0; p < 2; ++p) ae[s][p] = *(const u32x4 *)(Ae3 + ((size_t)(wave * C::KS + s) * 2 + p) * 256 + lane * 4);
-            if (!C::LEAN)
+            for (int p = 0; p < 2; ++p) ae[s][p] = *(const u32x4 *)(Ae3 + ((size_t)(wave * C::KS + s) * 2 + p) * 256 + lane * 4);
+        if (!C::LEAN)
 #pragma unroll
-                for (int s = 0; s < 2; ++s)
+            for (int s = 0; s < 2; ++s)
 #pragma unroll
-                    for (int p = 0; p < 2; ++p) ap[s][p] = *(const u32x4 *)(Ap3 + ((size_t)(wave * 2 + s) * 2 + p) * 256 + lane * 4);
-        } else if (svc_in && ub_begin < ub_end) {
-            const int unit = ub_begin + uw, fu = C::NBD > 1 ? unit / C::NBD : unit, r0 = C::NBD > 1 ? (unit - fu * C::NBD) * C::HB : 0;
-            const int f_in = fu * C::NF + ia, y0 = C::NBD > 1 ? (C::S == 1 ? r0 - 1 : 2 * (r0 - 1)) : 0;
+                for (int p = 0; p < 2; ++p) ap[s][p] = *(const u32x4 *)(Ap3 + ((size_t)(wave * 2 + s) * 2 + p) * 256 + lane * 4);
+    } else if (svc_in && ub_begin < ub_end) {
+        const int unit = ub_begin + uw, fu = C::NBD > 1 ? unit / C::NBD : unit, r0 = C::NBD > 1 ? (unit - fu * C::NBD) * C::HB : 0;
+        const int f_in = fu * C::NF + ia, y0 = C::NBD > 1 ? (C::S == 1 ? r0 - 1 : 2 * (r0 - 1)) : 0;
 #pragma unroll
-            for (int b = 0; b < C::NB; ++b)
+        for (int b = 0; b < C::NB; ++b)
 #pragma unroll
-                for (int yy = 0; yy < 2; ++yy) {
-                    const int y = y0 + yy;
-                    if ((unsigned)icol[b] < (unsigned)H && f_in < B && (unsigned)y < (unsigned)H) {
-                        const float *src = X + ((size_t)(f_in * H + y) * H + icol[b]) * C::CIN + 8 * h;
-                        asm volatile("global_load_dword %0, %1, off" : "+v"(early_sink) : "v"(src) : "memory");
-                    }
+            for (int yy = 0; yy < 2; ++yy) {
+                const int y = y0 + yy;
+                if ((unsigned)icol[b] < (unsigned)H && f_in < B && (unsigned)y < (unsigned)H) {
+                    const float *src = X + ((size_t)(f_in * H + y) * H + icol[b]) * C::CIN + 8 * h;
+                    asm volatile("global_load_dword %0, %1, off" : "+v"(early_sink) : "v"(src) : "memory");
                 }
-        }
+            }
     }
-    // power-of-two operand scales of the fp16 pieces (synergy_abi.hip): the expand accumulators start at Se x shift, ReLU6 clamps at
-    // 6 Se and the depthwise filter carries 1 / Se; the project sums are rescaled by 1 / Sp where the service wave reduces them
+    // power-of-two operand scales of the fp16 pieces (synergy_abi.hip): the expand accumulators start at Se x shift and
+    // leave through the multiply by 1 / (6 Se) below; the project sums are rescaled by 6 / Sp where the service wave reduces them
     //
     // ReLU6 without instructions of its own (round 5; the register-resident blocks and the stem since round 4): both activations are carried as
     // relu6(x) / 6 in [0, 1] = what the `clamp` output modifier leaves -- on the multiply that rescales the expand accumulator (1 / (6 Se), 0 on
     // padding lanes) and on the LAST fused multiply-add a depthwise output receives.  The 6 rides on the constants: plain depthwise filter,
-    // depthwise shift / 6, output rescale 6 / Sp.  Per row step and wave 32 v_med3 (4 issue cycles each) become 16 multiplies (2.7); SYN_RM_MED3=1: the old form.
-#ifndef SYN_RM_MED3
-#define SYN_RM_MED3 0
-#endif
-    constexpr bool CLAMP = !SYN_RM_MED3;
-    const float Se = scl_e[0], inv_se = scl_e[1], c6e = CLAMP ? scl_e[1] * (1.0f / 6.0f) : scl_e[2], inv_sp = CLAMP ? scl_p[1] * 6.0f : scl_p[1];
-    const float f_scale = CLAMP ? 1.0f : inv_se, d_scale = CLAMP ? 1.0f / 6.0f : 1.0f;
-    for (int i = tid; i < 9 * C::HIDP; i += NT) { const int c = i % C::HIDP; Filt[i] = c < C::HID ? Wd[(i / C::HIDP) * C::HID + c] * f_scale : 0.f; }
-    for (int i = tid; i < C::HIDP; i += NT) { Filt[DSH + i] = i < C::HID ? d_shift[i] * d_scale : 0.f; Esh[i] = i < C::HID ? e_shift[i] * Se : 0.f; }
+    // depthwise shift / 6, output rescale 6 / Sp.  Per row step and wave 32 v_med3 (4 issue cycles each) become 16 multiplies (2.7).
+    const float Se = scl_e[0], c6e = scl_e[1] * (1.0f / 6.0f), inv_sp = scl_p[1] * 6.0f;
+    for (int i = tid; i < 9 * C::HIDP; i += NT) { const int c = i % C::HIDP; Filt[i] = c < C::HID ? Wd[(i / C::HIDP) * C::HID + c] : 0.f; }
+    for (int i = tid; i < C::HIDP; i += NT) { Filt[DSH + i] = i < C::HID ? d_shift[i] * (1.0f / 6.0f) : 0.f; Esh[i] = i < C::HID ? e_shift[i] * Se : 0.f; }
     if (tid < 32) Psh[tid] = tid < C::COUT ? p_shift[tid] : 0.f;
     if (C::LEAN)
         for (int i = tid; i < C::APL_DW / 4; i += NT) *(u32x4 *)&ApL[4 * i] = *(const u32x4 *)&Ap3[4 * i];
@@ -351,19 +341,7 @@ __device__ __forceinline__ void rm_block(unsigned *smem, const float *__restrict
     // =========================================================================================================================
     // compute wave: hidden group `wave` of unit uw
     // =========================================================================================================================
-    // this wave's weight fragments stay in registers for the whole (persistent) kernel
-    if (!SYN_RM_EARLY) {
-#pragma unroll
-        for (int s = 0; s < C::KS; ++s)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) ae[s][p] = *(const u32x4 *)(Ae3 + ((size_t)(wave * C::KS + s) * 2 + p) * 256 + lane * 4);
-        if (!C::LEAN)
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int p = 0; p < 2; ++p) ap[s][p] = *(const u32x4 *)(Ap3 + ((size_t)(wave * 2 + s) * 2 + p) * 256 + lane * 4);
-    }
-
+    // (this wave's weight fragments ae / ap were requested before the constants were staged, above)
     f32x4 wreg[C::WREG > 0 ? C::WREG : 1][9], wbase[C::WREG > 0 ? C::WREG : 1];
 #pragma unroll
     for (int q = 0; q < C::WREG; ++q) {
@@ -377,7 +355,7 @@ __device__ __forceinline__ void rm_block(unsigned *smem, const float *__restrict
         const int unit = ub + uw;
         const int fu = C::NBD > 1 ? unit / C::NBD : unit, r0 = C::NBD > 1 ? (unit - fu * C::NBD) * C::HB : 0;
         const int f_in = fu * C::NF + ia;
-        float ehi[C::NB];                         // ReLU6 ceiling of the expanded pixel: 6 inside the image, 0 on padding lanes (clamp form: the multiplier 1 / (6 Se) | 0)
+        float ehi[C::NB];                         // ReLU6 of the expanded pixel as a clamped multiply: the multiplier 1 / (6 Se) inside the image, 0 on padding lanes
         float ehs[C::NB];                         // ... of the row being expanded (bands: 0 for the rows above / below the image)
 #pragma unroll
         for (int b = 0; b < C::NB; ++b) ehs[b] = ehi[b] = ((unsigned)icol[b] < (unsigned)H && f_in < B) ? c6e : 0.0f;
@@ -404,11 +382,11 @@ __device__ __forceinline__ void rm_block(unsigned *smem, const float *__restrict
             }
             // (compiler-made clamp: a vector instruction that reads a matrix result needs wait states only the compiler inserts)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) e[r] = CLAMP ? __builtin_amdgcn_fmed3f(e[r] * ehs[b], 0.0f, 1.0f) : __builtin_amdgcn_fmed3f(e[r], 0.0f, ehs[b]);
+            for (int r = 0; r < 16; ++r) e[r] = __builtin_amdgcn_fmed3f(e[r] * ehs[b], 0.0f, 1.0f);
         };
         // ---- finished depthwise row -> ReLU6 -> fp16 x2 pieces (in place: register 8s+e = K slot e of step s) -> project
         //      partial over this wave's 32 hidden channels -> LDS ----
-        auto finalize = [&](f32x16 &d, int pslot, bool raw = false) {        // raw: an output row whose last kernel row does not exist (clamp form: not clamped yet)
+        auto finalize = [&](f32x16 &d, int pslot, bool raw = false) {        // raw: an output row whose last kernel row does not exist (not clamped yet)
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -419,8 +397,7 @@ __device__ __forceinline__ void rm_block(unsigned *smem, const float *__restrict
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     float v0 = d[8 * s + 2 * t], v1 = d[8 * s + 2 * t + 1];
-                    if (!CLAMP) { v0 = __builtin_amdgcn_fmed3f(v0, 0.0f, 6.0f); v1 = __builtin_amdgcn_fmed3f(v1, 0.0f, 6.0f); }
-                    else if (raw) { v0 = __builtin_amdgcn_fmed3f(v0, 0.0f, 1.0f); v1 = __builtin_amdgcn_fmed3f(v1, 0.0f, 1.0f); }
+                    if (raw) { v0 = __builtin_amdgcn_fmed3f(v0, 0.0f, 1.0f); v1 = __builtin_amdgcn_fmed3f(v1, 0.0f, 1.0f); }
                     unsigned ha, hb;
                     split2r(v0, v1, ha, hb);
                     db[0][t] = ha; db[1][t] = hb;
@@ -439,7 +416,7 @@ __device__ __forceinline__ void rm_block(unsigned *smem, const float *__restrict
             for (int q = 0; q < C::NQ; ++q) *(f32x4 *)(dst + q * 256) = (f32x4){acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
         };
         // three taps of one kernel row into one accumulator quad; `init`: the accumulator starts at the BN shift (Filt row 9)
-        // `last` (clamp form): this kernel row completes the output row -- its last multiply-add clamps to [0, 1]
+        // `last`: this kernel row completes the output row -- its last multiply-add clamps to [0, 1]
         auto taps3 = [&](f32x16 &d, int q, const float *wq, int ky, const f32x4 &l4, const f32x4 &c4, const f32x4 &r4, bool init, bool last = false) {
             const f32x4 w0 = *(const f32x4 *)(wq + (3 * ky + 0) * C::HIDP), w1 = *(const f32x4 *)(wq + (3 * ky + 1) * C::HIDP),
                         w2 = *(const f32x4 *)(wq + (3 * ky + 2) * C::HIDP);
@@ -449,7 +426,7 @@ __device__ __forceinline__ void rm_block(unsigned *smem, const float *__restrict
             for (int t = 0; t < 4; ++t) {
                 const float b0 = init ? base[t] : d[4 * q + t];
                 const float v = __builtin_fmaf(r4[t], w2[t], __builtin_fmaf(c4[t], w1[t], __builtin_fmaf(l4[t], w0[t], b0)));
-                d[4 * q + t] = CLAMP && last ? __builtin_amdgcn_fmed3f(v, 0.0f, 1.0f) : v;
+                d[4 * q + t] = last ? __builtin_amdgcn_fmed3f(v, 0.0f, 1.0f) : v;
             }
             // pin the update here: otherwise the compiler sinks these FMAs to where the accumulator is next read (the following
             // row's step) and keeps their operands + filter quads alive across the barrier instead
@@ -462,7 +439,7 @@ __device__ __forceinline__ void rm_block(unsigned *smem, const float *__restrict
             for (int t = 0; t < 4; ++t) {
                 const float b0 = init ? base[t] : d[4 * q + t];
                 const float v = __builtin_fmaf(r4[t], wr[3 * ky + 2][t], __builtin_fmaf(c4[t], wr[3 * ky + 1][t], __builtin_fmaf(l4[t], wr[3 * ky][t], b0)));
-                d[4 * q + t] = CLAMP && last ? __builtin_amdgcn_fmed3f(v, 0.0f, 1.0f) : v;
+                d[4 * q + t] = last ? __builtin_amdgcn_fmed3f(v, 0.0f, 1.0f) : v;
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t) asm volatile("" : "+v"(d[4 * q + t]));
@@ -482,7 +459,7 @@ __device__ __forceinline__ void rm_block(unsigned *smem, const float *__restrict
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const float v = __builtin_fmaf(e[4 * q + t], wa[t], d[4 * q + t]);
-                d[4 * q + t] = CLAMP && last ? __builtin_amdgcn_fmed3f(v, 0.0f, 1.0f) : v;
+                d[4 * q + t] = last ? __builtin_amdgcn_fmed3f(v, 0.0f, 1.0f) : v;
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t) asm volatile("" : "+v"(d[4 * q + t]));
@@ -703,15 +680,9 @@ static void launch_rm(const FusedBlockArgs &a, int B, hipStream_t s, int wgs_per
 // which split a face over many workgroups, are faster and the launcher declines.
 //                       CIN  HID COUT  H  S NF  RES   waves/SIMD  units/workgroup
 template <int U> using R2 = RmCfg< 16,  96,  24, 60, 2, 1, false, (U == 4 ? 4 : 3), U>;    // features.2   60 -> 30      U x (3 + 1) waves
-#ifndef SYN_R3_WREG
-#define SYN_R3_WREG 1
-#endif
-template <int U> using R3 = RmCfg< 24, 144,  24, 30, 1, 1, true,  3, U, false, SYN_R3_WREG>;                   // features.3   30            U x (5 + 1) waves
+template <int U> using R3 = RmCfg< 24, 144,  24, 30, 1, 1, true,  3, U, false, 1>;                   // features.3   30            U x (5 + 1) waves
 template <int U> using R4 = RmCfg< 24, 144,  32, 30, 2, 2, false, 3, U>;                   // features.4   30 -> 15      U x (5 + 1) waves, two faces per unit
-#ifndef SYN_R5_SVC2
-#define SYN_R5_SVC2 1
-#endif
-template <int U> using R5 = RmCfg< 32, 192,  32, 15, 1, 2, true,  4, U, true, 0, 1, SYN_R5_SVC2 != 0>;    // features.5/6 15     U x (6 + 2) waves, two faces per unit, 4 per SIMD
+template <int U> using R5 = RmCfg< 32, 192,  32, 15, 1, 2, true,  4, U, true, 0, 1, true>;    // features.5/6 15     U x (6 + 2) waves, two faces per unit, 4 per SIMD
 // small batches: NBD row bands per face (RmCfg::NBD).  A band march has a floor of its own -- its steps are a dependent chain of ~1.3-2 us
 // each whatever the batch (features.2: 12 steps + prologue = 16-18 us at B = 1, features.3: 25) -- against 12 us for the tiled kernels, so the
 // bands pay in a window: features.2 from ~40 faces (B = 64 / 128 / 256: 20 / 24 / 38 us against 24 / 36 / 57 tiled; six bands of five output
@@ -719,7 +690,7 @@ template <int U> using R5 = RmCfg< 32, 192,  32, 15, 1, 2, true,  4, U, true, 0,
 // workgroup).  features.4 (two faces per unit: 21 against 23 us at B = 128, 34 against 32 at 256) and the other band counts / unit counts
 // tried (features.2: 3 or 5 bands 30 / 26 us, two units 29; features.3: 2 bands 29, 5 bands 38) are not instantiated.  tools/band_ab.sh.
 template <int U, int NBD> using R2b = RmCfg< 16,  96,  24, 60, 2, 1, false, 3, U, false, 0, NBD>;
-template <int U, int NBD> using R3b = RmCfg< 24, 144,  24, 30, 1, 1, true,  3, U, false, SYN_R3_WREG, NBD>;
+template <int U, int NBD> using R3b = RmCfg< 24, 144,  24, 30, 1, 1, true,  3, U, false, 1, NBD>;
 constexpr int kBand2Min = 40, kBand3Min = 96;
 
 // Two consecutive blocks in one launch (B >= 513: the configurations launch_fused_block_rm would pick for either): features.5 + 6 (first = 5) and

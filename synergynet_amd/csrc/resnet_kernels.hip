@@ -690,14 +690,8 @@ void conv_lt_kernel(const float *__restrict__ in, const unsigned *__restrict__ W
     // Raw barriers: __syncthreads() would drain the loads in flight.  No branches inside a step (the last steps park / fetch clamped
     // leftovers nobody reads): the compiler's vmcnt bookkeeping falls back to vmcnt(0) at every join.
 #define LT_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#ifndef SYN_LT_DEFER
-#define SYN_LT_DEFER 1
-#endif
-#ifndef SYN_LT_PIN
-#define SYN_LT_PIN 1
-#endif
     // step s: slot_c = ring slot of step s + 1 (parked now), which then receives the loads of step s + 1 + D
-    constexpr bool DEFER = SYN_LT_DEFER && MTW == 4;             // (128-pixel tiles: the 24 operand registers kept across the barrier do not fit into the 128 of two workgroups per CU)
+    constexpr bool DEFER = MTW == 4;             // (128-pixel tiles: the 24 operand registers kept across the barrier do not fit into the 128 of two workgroups per CU)
     auto step = [&](int s, auto slot_c) {
         read_a(s);
         if (DEFER) {
@@ -717,7 +711,7 @@ void conv_lt_kernel(const float *__restrict__ in, const unsigned *__restrict__ W
         prod(1, 0);
         prod(0, 0);
         if (!DEFER) prod(0, 1);
-        if (DEFER && SYN_LT_PIN) __builtin_amdgcn_sched_barrier(0);      // (else the compiler sinks these MFMAs past the next barrier)
+        if (DEFER) __builtin_amdgcn_sched_barrier(0);      // (else the compiler sinks these MFMAs past the next barrier)
     };
     if (DEFER) {
 #pragma unroll
@@ -898,30 +892,21 @@ void conv_lp_kernel(const float *__restrict__ in, const unsigned *__restrict__ W
     };
     // A step, in G chunks: NM / G MFMAs of step s (registers of set SET_THIS), then ONE load of step s + 3 and NR / G fragment reads of step
     // s + 1 -- the loads cost an in-order wave 60 - 180 cycles of issue each (MI355X_MICROARCH: LDS-DMA issue cost); in a block in front of
-    // the MFMAs they left the matrix pipe idle, behind 8 queued MFMAs each they are covered (SYN_LP_INTERLEAVE=0: the block form).
+    // the MFMAs they left the matrix pipe idle, behind 8 queued MFMAs each they are covered.
     // Before it: the stage of step s + 1 has landed (own loads: counted vmcnt -- G stay in flight -- then everybody's: barrier), this wave's
     // fragments of step s are in registers (lgkmcnt 0: every wave is done with the stage of step s before the barrier -> refill it).
-#ifndef SYN_LP_INTERLEAVE
-#define SYN_LP_INTERLEAVE 1
-#endif
     auto step = [&](int o_this, int o_next, auto set_this, auto set_next) {
         asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(G) : "memory");
         prepare();
-        if (SYN_LP_INTERLEAVE) {
-            static_for<G>([&](auto c) {
-                constexpr int C = decltype(c)::value;
-                __builtin_amdgcn_sched_barrier(0);
-                static_for<NM / G>([&](auto k) { mfma_k(set_this, std::integral_constant<int, C * (NM / G) + decltype(k)::value>{}); });
-                __builtin_amdgcn_sched_barrier(0);
-                issue_k(o_this, c);
-                static_for<(C + 1) * NR / G - C * NR / G>([&](auto k) { read_k(o_next, set_next, std::integral_constant<int, C * NR / G + decltype(k)::value>{}); });
-            });
+        static_for<G>([&](auto c) {
+            constexpr int C = decltype(c)::value;
             __builtin_amdgcn_sched_barrier(0);
-        } else {
-            static_for<G>([&](auto k) { issue_k(o_this, k); });
-            static_for<NR>([&](auto k) { read_k(o_next, set_next, k); });
-            static_for<NM>([&](auto k) { mfma_k(set_this, k); });
-        }
+            static_for<NM / G>([&](auto k) { mfma_k(set_this, std::integral_constant<int, C * (NM / G) + decltype(k)::value>{}); });
+            __builtin_amdgcn_sched_barrier(0);
+            issue_k(o_this, c);
+            static_for<(C + 1) * NR / G - C * NR / G>([&](auto k) { read_k(o_next, set_next, std::integral_constant<int, C * NR / G + decltype(k)::value>{}); });
+        });
+        __builtin_amdgcn_sched_barrier(0);
     };
     int o0 = 0, o1 = ST_DW, o2 = 2 * ST_DW;
     issue(o0);
@@ -1033,15 +1018,6 @@ void launch_conv_f16x2(const float *in, const unsigned *W3, const float *scale, 
 // The block output is read back only as the next block's identity: 1.18 GB instead of 1.65 GB per bottleneck of layer 1 at B = 512, and
 // one launch less.
 // =====================================================================================
-#ifndef SYN_C3F_L2_MT
-#define SYN_C3F_L2_MT 2
-#endif
-#ifndef SYN_C3F_L1_MT
-#define SYN_C3F_L1_MT 2                // 16-pixel tiles per wave in layer 1's fused launches (1: half the registers, three workgroups per CU)
-#endif
-#ifndef SYN_C3F_L1_TC
-#define SYN_C3F_L1_TC 4                // output-channel tiles of conv3 per chunk in layer 1's middle blocks
-#endif
 // DS (layer1.0: 64 -> 256, stride 1): the block's downsample branch (1x1 conv + BN, resnet_backbone.py:127-128) is evaluated IN the kernel
 // instead of being read as `identity`: the block input of the workgroup's pixels (64 channels) stays in registers as a second B operand, the
 // downsample weights of a chunk come straight from L2 (natural K order, one tile ahead), and the 256-channel branch -- 472 MB written by a
@@ -1386,13 +1362,17 @@ static void launch_c3f_t(const float *T2, const unsigned *W3, const float *scale
 #undef SYN_C3F_GO
 }
 
+constexpr int kC3fL1Mt = 2;            // 16-pixel tiles per wave in layer 1's fused launches (1: half the registers, three workgroups per CU)
+constexpr int kC3fL2Mt = 2;            // ... and in layer 2's
+constexpr int kC3fL1Tc = 4;            // output-channel tiles of conv3 per chunk in layer 1's middle blocks
+
 // ... with the block's downsample branch evaluated in the kernel (DS above): layer1.0.  Every tensor in the pair format.  c2 != nullptr: conv2 in front (T2 unused).
 bool launch_conv_c3f_ds(const float *T2, const unsigned *W3, const float *scale3, const float *shift3, const float *X, const unsigned *Wd,
                         const float *scale_d, const float *shift_d, float *out, const unsigned *W1f, const float *s1, const float *scale1,
                         const float *shift1, float *T1n, int M, int K, int Kd, int N3, int N1, hipStream_t s, float *stat3, float *stat1, const C2Args *c2) {
     if (K != 64 || Kd != 64 || N3 != 256 || N1 != 64) return false;
     const DsArgs ds{X, Wd, scale_d, shift_d};
-    constexpr int MT = SYN_C3F_L1_MT;
+    constexpr int MT = kC3fL1Mt;
     const int m_tiles = (M + 64 * MT - 1) / (64 * MT), grid = ((m_tiles + 7) / 8) * 8;
     // (32-channel chunks: with 64 the second B operand spills)
     if (c2) conv_c3f_kernel<2, 4, MT, 2, true, false, true><<<grid, 256, 0, s>>>(T2, W3, scale3, shift3, nullptr, out, W1f, s1, scale1, shift1, T1n, M, N3, m_tiles, stat3, stat1, ds, *c2);
@@ -1408,9 +1388,9 @@ bool launch_conv_c3f(const float *T2, const unsigned *W3, const float *scale3, c
     if (N3 % 64 || N3 > 512) return false;
     if (c2 && K != 64 && K != 128) return false;
 #define SYN_C3F(KS3, NT1, MT, TC) launch_c3f_t<KS3, NT1, MT, TC>(T2, W3, scale3, shift3, identity, out, W1f, s1, scale1, shift1, T1n, M, N3, s, stat3, stat1, res_pair, c2)
-    if (K == 64 && N1 == 64) SYN_C3F(2, 4, SYN_C3F_L1_MT, SYN_C3F_L1_TC);      // layer 1
-    else if (K == 64 && N1 == 128) SYN_C3F(2, 8, SYN_C3F_L1_MT, 2);        // layer 1 -> layer 2 (32-channel chunks: 48 KB of LDS, < 256 registers)
-    else if (K == 128 && N1 == 128) SYN_C3F(4, 8, SYN_C3F_L2_MT, 2);       // layer 2
+    if (K == 64 && N1 == 64) SYN_C3F(2, 4, kC3fL1Mt, kC3fL1Tc);      // layer 1
+    else if (K == 64 && N1 == 128) SYN_C3F(2, 8, kC3fL1Mt, 2);        // layer 1 -> layer 2 (32-channel chunks: 48 KB of LDS, < 256 registers)
+    else if (K == 128 && N1 == 128) SYN_C3F(4, 8, kC3fL2Mt, 2);       // layer 2
     else return false;
 #undef SYN_C3F
     return true;

@@ -88,10 +88,7 @@ struct StemRmCfg {
     // service waves.  Round 5: FOUR, one per SIMD (wave ids NCW .. NCW + 3 follow the 2 U compute waves cyclically), each converting a quarter of a
     // stage.  One service wave (two for F32) sat on SIMD 0 (and 1) beside that SIMD's two compute waves: ~600 of its ~3600 issue cycles per row
     // step against ~3000 on the other SIMDs, and every step ends at a workgroup barrier -- the whole chip ran at SIMD 0's pace.
-#ifndef SYN_STEM_NSV
-#define SYN_STEM_NSV 4
-#endif
-    static constexpr int NSV = SYN_STEM_NSV > 0 ? SYN_STEM_NSV : (F32 ? 2 : 1);
+    static constexpr int NSV = 4;
     static constexpr int NCW = 2 * U, NT = (NCW + NSV) * 64;       // compute waves (face, half) + the service wave(s)
     static constexpr int SLOT_DW = (F32 ? 2 : 1) * kRowDw;         // one image row: plane of high pieces | (F32) plane of low pieces
     static constexpr int UNIT_DW = (kSlots + 1) * SLOT_DW;         // ring + one all-padding row (image row -1)
