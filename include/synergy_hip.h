@@ -318,6 +318,23 @@ int syn_sample_vertex_colors(syn_handle *h, const float *vertices, int F, int pl
 int syn_uv_scatter(syn_handle *h, const float *colors, const uint8_t *visible, int F, int channels, uint8_t *tex, uint8_t *mask, int tex_h,
                    int tex_w, void *stream);
 
+/* Fills the texels no vertex wrote: deterministic push-pull (pyramid) completion of uint8 UV textures, integer arithmetic only, so the
+ * result is defined byte for byte (tests/texture_fill_cases.py states it in numpy).
+ *   level 0  w = (mask != 0), c = tex * w per channel.  merge != 0: the T views collapse into ONE texture, w = sum_t (mask_t != 0),
+ *            c = sum_t tex_t * (mask_t != 0).
+ *   push     level l+1 is ceil(H_l/2) x ceil(W_l/2); w and c are the plain sums over the up-to-four children that exist.
+ *   own      where w > 0: floor((2c + w) / (2w)) (round half up).
+ *   pull     from the 1x1 level down: V = own where w > 0, elsewhere (9 V[py,px] + 3 V[py,nx] + 3 V[ny,px] + V[ny,nx] + 8) >> 4 on the
+ *            level above, py = y >> 1, ny = clamp(py + (y odd ? +1 : -1), 0, H_{l+1} - 1), px / nx likewise.  tex_out = V_0.
+ * Valid texels keep their value (merged: the rounded mean of the views that saw them); a texture without a valid texel comes out 0.
+ * tex_in: device uint8 [T,tex_h,tex_w,channels]; mask: device uint8 [T,tex_h,tex_w], nonzero = valid, not modified; tex_out: device
+ * uint8 [T,tex_h,tex_w,channels], or [1,tex_h,tex_w,channels] with merge.  Three launches on `stream` whatever T and the size, nothing
+ * is synchronised; the pyramid lives in the render scratch.  SYN_ERR_INVALID (nothing enqueued): a NULL pointer, T < 1, channels
+ * outside 1..4, tex_h or tex_w outside 1..4096, tex_out overlapping tex_in or mask, merge with T*tex_h*tex_w > 2^24 (the sums would
+ * not fit 32 bits). */
+int syn_texture_fill(syn_handle *h, const uint8_t *tex_in, const uint8_t *mask, int T, int tex_h, int tex_w, int channels, int merge,
+                     uint8_t *tex_out, void *stream);
+
 /* ---- FaceBoxes face detector: the boxes get_all_outputs crops (synergy3DMM.py:169-171) ----
  * syn_detector_flat_count / syn_load_detector: FaceBoxesNet's state_dict (FaceBoxes/models/faceboxes.py:64-114) flattened in
  * forward order -- conv1, conv2, inception{1,2,3}.{branch1x1, branch1x1_2, branch3x3_reduce, branch3x3, branch3x3_reduce_2,

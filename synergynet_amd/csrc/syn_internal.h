@@ -294,6 +294,13 @@ void launch_uv_scatter(const float *colors /*[F,nver,ch]*/, const unsigned char 
                        const int *coord_v, unsigned *owner /*[F,th,tw] scratch*/, unsigned char *tex /*[F,th,tw,ch]*/,
                        unsigned char *mask /*[F,th,tw]*/, int F, int nver, int th, int tw, int ch, hipStream_t s);
 
+// ---- push-pull completion of UV textures (texture_kernels.hip): three launches for any size and batch ----
+// scratch: texture_fill_scratch_bytes(Tout, ...) bytes, Tout = 1 with merge else T; out [Tout,th,tw,ch]
+constexpr int kTextureFillMaxDim = 4096;                        // th, tw beyond it are refused by syn_texture_fill; the kernels' LDS is sized by it
+size_t texture_fill_scratch_bytes(int Tout, int th, int tw, int ch);
+void launch_texture_fill(const unsigned char *tex /*[T,th,tw,ch]*/, const unsigned char *mask /*[T,th,tw]*/, unsigned *scratch,
+                         unsigned char *out, int T, int th, int tw, int ch, int merge, hipStream_t s);
+
 // ---- AFLW2000-3D landmark error (eval_kernels.hip) ----
 void launch_nme(const float *fit, const float *gt, const float *roi, float *nme, int N, hipStream_t s);
 

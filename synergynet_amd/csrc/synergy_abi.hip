@@ -2597,6 +2597,30 @@ int syn_uv_scatter(syn_handle *h, const float *colors, const uint8_t *visible, i
     return SYN_OK;
 }
 
+int syn_texture_fill(syn_handle *h, const uint8_t *tex_in, const uint8_t *mask, int T, int tex_h, int tex_w, int channels, int merge,
+                     uint8_t *tex_out, void *stream) {
+    if (!h || !tex_in || !mask || !tex_out) return fail(SYN_ERR_INVALID, "syn_texture_fill: NULL argument");
+    if (T < 1 || tex_h < 1 || tex_h > syn::kTextureFillMaxDim || tex_w < 1 || tex_w > syn::kTextureFillMaxDim || channels < 1 || channels > 4)
+        return fail(SYN_ERR_INVALID, "syn_texture_fill: T=%d tex_h=%d tex_w=%d channels=%d (T >= 1, sizes 1..4096, channels 1..4)", T, tex_h,
+                    tex_w, channels);
+    const size_t texels = (size_t)tex_h * tex_w;
+    if (merge && (unsigned long long)T * texels > (1ull << 24))
+        return fail(SYN_ERR_INVALID, "syn_texture_fill: merging T=%d views of %d x %d exceeds 2^24 texels, the sums would not fit 32 bits", T,
+                    tex_h, tex_w);
+    const int Tout = merge ? 1 : T;
+    const unsigned long long tiles = (unsigned long long)Tout * ((tex_h + 63) / 64) * ((tex_w + 63) / 64);
+    if (tiles >= (1ull << 31)) return fail(SYN_ERR_INVALID, "syn_texture_fill: T=%d textures of %d x %d are more tiles than one grid holds", T, tex_h, tex_w);
+    const uint8_t *in_end = tex_in + (size_t)T * texels * channels, *out_end = tex_out + (size_t)Tout * texels * channels;
+    if (tex_out < in_end && tex_in < out_end) return fail(SYN_ERR_INVALID, "syn_texture_fill: tex_out overlaps tex_in");
+    if (tex_out < mask + (size_t)T * texels && mask < out_end) return fail(SYN_ERR_INVALID, "syn_texture_fill: tex_out overlaps mask");
+    DeviceGuard g(h->device);
+    int rc = ensure_rws(h, syn::texture_fill_scratch_bytes(Tout, tex_h, tex_w, channels));
+    if (rc) return rc;
+    syn::launch_texture_fill(tex_in, mask, (unsigned *)h->rws, tex_out, T, tex_h, tex_w, channels, merge != 0, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 int syn_add_weighted(syn_handle *h, const uint8_t *a, float alpha, const uint8_t *b, float beta, uint8_t *out, size_t n,
                      void *stream) {
     if (!h || !a || !b || !out) return fail(SYN_ERR_INVALID, "syn_add_weighted: NULL argument");

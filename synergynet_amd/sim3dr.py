@@ -18,9 +18,10 @@ all on the device.  The handle keeps two topology slots (full mesh, kept mesh); 
 Visibility buffers: `rasterize_triangles` is the third entry point of the reference's binding (Sim3DR/lib/rasterize.pyx:74-86: per
 pixel the winning triangle, its barycentric weights and its depth, written into the caller's arrays).  `visibility_batch` is its
 device-resident form plus the per-vertex visibility that follows from it, `vertex_colors_from_image` samples one colour per vertex
-from a frame, and `texture_from_image` chains them into a UV texture image (and its mask of filled texels) -- what
+from a frame, and `texture_from_image` chains them into a UV texture image (and its mask of written texels) -- what
 `render_batch(uv_tex=)` and `uv_vertex_colors` consume.  syn_rasterize_triangles / syn_vertex_visibility /
-syn_sample_vertex_colors / syn_uv_scatter.
+syn_sample_vertex_colors / syn_uv_scatter.  `fill_texture` (and `texture_from_image(fill=True)`) completes the texels no vertex
+wrote by a push-pull over the texture's pyramid, optionally merging several views of one face first: syn_texture_fill.
 """
 from __future__ import annotations
 
@@ -280,13 +281,48 @@ def vertex_colors_from_image(model, img, meshes, normalize=False):
     return out
 
 
-def texture_from_image(model, img, meshes, tex_hw=256, occlusion=True):
+def _u8(model, a, what, allow_bool=False):
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    if allow_bool and t.dtype == torch.bool:
+        t = t.view(torch.uint8)                                 # same bytes: False 0, True 1
+    if t.dtype != torch.uint8:
+        raise TypeError(f'{what} must be uint8')
+    return t.to(model.device).contiguous()
+
+
+def fill_texture(model, uv_tex, mask, merge=False):
+    """Fills the texels of UV textures that `mask` marks as not written (0), by a deterministic push-pull over the texture's pyramid
+    (syn_texture_fill; DESIGN 5.5c has the definition, integer arithmetic only): written texels keep their value, every other texel
+    gets a smooth blend of the written ones around it, the nearest ones weighing most; a texture without a written texel comes out 0.
+    uv_tex uint8 [H,W,ch] or [T,H,W,ch] with ch <= 4 and H, W <= 4096, mask uint8 (or bool) [H,W] / [T,H,W]; arrays or device tensors.
+    merge=True takes T views of ONE face ([T,H,W,ch], e.g. the frames of a video): a texel seen by several views gets their rounded
+    mean before the holes no view saw are filled.  Returns a uint8 device tensor of the input's shape, or [H,W,ch] with merge; the
+    inputs are not modified.  Three kernel launches whatever T."""
+    t = _u8(model, uv_tex, 'uv_tex')
+    mk = _u8(model, mask, 'mask', allow_bool=True)
+    if t.dim() not in (3, 4) or tuple(mk.shape) != tuple(t.shape[:-1]):
+        raise ValueError(f'uv_tex must be [H,W,ch] or [T,H,W,ch] and mask its shape without the channels, got {tuple(t.shape)} and '
+                         f'{tuple(mk.shape)}')
+    if merge and t.dim() != 4:
+        raise ValueError('merge takes the views as one [T,H,W,ch] array')
+    t4 = t if t.dim() == 4 else t[None]
+    T, th, tw, ch = t4.shape
+    out = torch.empty((1 if merge else T, th, tw, ch), dtype=torch.uint8, device=model.device)
+    with torch.cuda.device(model.device):
+        abi.check(model._lib.syn_texture_fill(model._h, t4.data_ptr(), mk.data_ptr(), T, th, tw, ch, int(bool(merge)), out.data_ptr(),
+                                              model._stream()))
+    return out[0] if merge or t.dim() == 3 else out
+
+
+def texture_from_image(model, img, meshes, tex_hw=256, occlusion=True, fill=False):
     """From a photograph and the meshes reconstructed from it to UV texture images: every vertex takes its colour from the frame
     (vertex_colors_from_image) and writes it to its texel of the model's UV map (param_pack.uv_vert), the inverse of
     uv_vertex_colors.  occlusion=True writes only the vertices visibility_batch finds visible at the frame's size; texels no
-    vertex writes stay 0 (no hole filling).  Where vertices share a texel the highest vertex index wins.
-    tex_hw: texture size, an int or (height, width).  Returns (uv_tex uint8 [F,th,tw,ch], mask uint8 [F,th,tw], 255 where written),
-    device tensors; uv_tex is what render_batch(uv_tex=) and uv_vertex_colors take.  Nothing is downloaded in between."""
+    vertex writes stay 0 unless fill=True, which completes them from the written ones (fill_texture).  Where vertices share a
+    texel the highest vertex index wins.
+    tex_hw: texture size, an int or (height, width).  Returns (uv_tex uint8 [F,th,tw,ch], mask uint8 [F,th,tw], 255 where a vertex
+    wrote -- also with fill=True), device tensors; uv_tex is what render_batch(uv_tex=) and uv_vertex_colors take.  Nothing is
+    downloaded in between."""
     F, _, n = meshes.shape
     n_vert, _ = _ensure_uv_map(model)
     if n != n_vert:
@@ -301,7 +337,7 @@ def texture_from_image(model, img, meshes, tex_hw=256, occlusion=True):
     with torch.cuda.device(model.device):
         abi.check(model._lib.syn_uv_scatter(model._h, colors.data_ptr(), visible.data_ptr() if visible is not None else None, F, ch,
                                             tex.data_ptr(), mask.data_ptr(), th, tw, model._stream()))
-    return tex, mask
+    return (fill_texture(model, tex, mask) if fill else tex), mask
 
 
 def get_normal(vertices, triangles):
