@@ -335,6 +335,49 @@ int syn_uv_scatter(syn_handle *h, const float *colors, const uint8_t *visible, i
 int syn_texture_fill(syn_handle *h, const uint8_t *tex_in, const uint8_t *mask, int T, int tex_h, int tex_w, int channels, int merge,
                      uint8_t *tex_out, void *stream);
 
+/* ---- per-pixel texture mapping: the reference's _render_texture_core (Sim3DR/lib/rasterize_kernel.cpp:353-458, binding commented
+ * out in rasterize.pyx:24-31,104-123), a z-buffer walk that samples a texture IMAGE per pixel instead of interpolating vertex colours ----
+ * syn_load_tex_coords: the texture coordinates of the currently selected topology slot (HOST arrays), stored on the device per slot
+ * until that slot's topology is replaced.  tex_coords [tex_nver,3] float32: x = texture column, y = texture row, in texels (the third
+ * column is not read; row stride 3 as in the reference); tex_triangles [ntri,3] int32, ntri = the slot's triangle count, or NULL for
+ * the slot's own mesh triangles.  Validated like syn_load_triangles: every tex_triangles index in [0, tex_nver), and every index of
+ * the slot's MESH triangles < tex_nver (see quirk 2).  SYN_ERR_NOT_LOADED when the slot is empty. */
+int syn_load_tex_coords(syn_handle *h, const float *tex_coords, int tex_nver, const int32_t *tex_triangles);
+
+/* syn_render_texture: F meshes of the selected topology drawn into image / depth_buffer (device, IN-OUT) with a per-pixel texture
+ * lookup.  All arithmetic is float32 in the reference's operation order, without FMA contraction; with a float32 texture and image the
+ * result is bit-identical to the reference's compiled function.
+ *   candidates  triangle i competes for pixel (x, y) when the pixel lies in max(ceil(min),0) .. min(floor(max),W-1) of its corners
+ *               (likewise in y: the box of _rasterize_triangles) and  x < 2 || x > W-3 || y < 2 || y > H-3 || is_point_in_tri.
+ *               Quirk 1, kept: on the two-pixel frame border the inside test is bypassed (:418) and the weights are extrapolated,
+ *               (1,0,0) for a zero-area triangle.
+ *   depth test  p_depth = w0*d0 + w1*d1 + w2*d2, weights (1-u-v, v, u); a candidate competes only where p_depth > the caller's
+ *               depth_buffer (NaN never does); the greatest depth wins, the earliest index among equals, +0 == -0; the stored depth
+ *               is the winner's own value (a zero keeps its sign).
+ *   coordinate  tex_p = tex_p0*w0 + tex_p1*w1 + tex_p2*w2, left to right.  Quirk 2, kept: x is read through tex_triangles, y through
+ *               the MESH triangle's indices (:393-398).  Quirk 3, kept: tex_coords has row stride 3.  With tex_triangles == the mesh
+ *               triangles (NULL above) quirk 2 vanishes.
+ *   clamp       x = x > tex_w-1 ? tex_w-1 : x;  x = x >= 0 ? x : 0  (y likewise): the reference's max(min()) for every finite value.
+ *               DEFINED here where the reference is not: a NaN coordinate samples coordinate 0 (the reference converts NaN to int
+ *               and reads out of range).
+ *   sample      mapping_type 0: texture[int(round(y)), int(round(x)), k], round half away from zero; 1: xd = x - floor(x), yd
+ *               likewise, ul*(1-xd)*(1-yd) + ur*xd*(1-yd) + dl*(1-xd)*yd + dr*xd*yd left to right over floor / ceil neighbours.
+ *               Channels k < c of the image come from channels k of the tex_c-channel texture.  Pixels nobody wins keep the caller's
+ *               image and depth.
+ * vertices, planar: as syn_mesh_shade.  texture: device [T,tex_h,tex_w,tex_c], float32 (tex_u8 = 0) or uint8 (tex_u8 = 1, read as
+ * (float)byte: identical to converting first), T = 1 (one for all faces) or F.  image: float32 (image_u8 = 0) or uint8 (image_u8 = 1:
+ * winners stored as uint8(clip(rint(v), 0, 255)), the convention of syn_uv_scatter; goes straight into syn_add_weighted).
+ * shared = 0: image [F,H,W,c], depth_buffer [F,H,W], every mesh its own planes, like syn_rasterize_triangles.
+ * shared = 1: image [H,W,c], depth_buffer [H,W]: the result of calling the reference once per mesh, in order, on the SAME image and
+ *   depth buffer -- all faces compete in one z-buffer, the earliest (face, triangle) wins among equal depths.
+ * Two launches on `stream`, nothing is synchronised; the key planes come from the render scratch, which grows on demand.
+ * SYN_ERR_NOT_LOADED: no topology, or no texture coordinates for the selected slot.  SYN_ERR_INVALID, nothing enqueued: a NULL pointer,
+ * c outside 1..4, c > tex_c, tex_c > 4, T not in {1, F}, mapping_type not in {0, 1}, F*ntri >= 2^32, F*H*W >= 2^31, F > 65535, a
+ * texture side above 2^24 or T*tex_h*tex_w >= 2^31, a bad planar. */
+int syn_render_texture(syn_handle *h, const float *vertices, int F, int planar, const void *texture, int tex_u8, int T, int tex_h, int tex_w,
+                       int tex_c, int mapping_type, void *image, int image_u8, float *depth_buffer, int H, int W, int c, int shared,
+                       void *stream);
+
 /* ---- FaceBoxes face detector: the boxes get_all_outputs crops (synergy3DMM.py:169-171) ----
  * syn_detector_flat_count / syn_load_detector: FaceBoxesNet's state_dict (FaceBoxes/models/faceboxes.py:64-114) flattened in
  * forward order -- conv1, conv2, inception{1,2,3}.{branch1x1, branch1x1_2, branch3x3_reduce, branch3x3, branch3x3_reduce_2,

@@ -7,6 +7,7 @@
 //                       texture * light in the lighting epilogue
 //   Sim3DR.rasterize_triangles (Sim3DR/lib/rasterize_kernel.cpp:290-348)  per-pixel winning triangle, weights, depth; on top of it
 //                       vertex visibility, per-vertex colours sampled from a frame and the scatter into a UV texture image
+//   _render_texture_core (Sim3DR/lib/rasterize_kernel.cpp:353-458)  per-pixel texture mapping on the z-buffer, nearest or bilinear
 // The reference walks the 105 840 triangles one at a time on the host.  Here every stage is data parallel and still
 // reproduces the sequential result BIT FOR BIT (tests/test_gpu_render.py):
 //   * arithmetic is plain IEEE single precision in the reference's operation order -- FMA contraction is switched off for
@@ -249,6 +250,11 @@ __device__ __forceinline__ Bary bary(float px, float py, float p0x, float p0y, f
     b.in = (u >= 0) && (v >= 0) && (u + v < 1);
     return b;
 }
+// the bilinear expression of rasterize_kernel.cpp:445-447, left to right (tex_resolve_kernel; sample_vertex_colors_kernel keeps its
+// own copy of the line: routed through this function hipcc swaps the operands of four of its additions)
+__device__ __forceinline__ float bilerp(float ul, float ur, float dl, float dr, float xd, float yd) {
+    return ul * (1 - xd) * (1 - yd) + ur * xd * (1 - yd) + dl * (1 - xd) * yd + dr * xd * yd;
+}
 __device__ __forceinline__ unsigned depth_key(float d) {
     const unsigned u = __builtin_bit_cast(unsigned, d);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -439,6 +445,88 @@ __global__ __launch_bounds__(256) void uv_scatter_kernel(const float *__restrict
     mask[o] = own ? 255 : 0;
 }
 
+// ---- Sim3DR's _render_texture_core (rasterize_kernel.cpp:353-458): the z-buffer walk that samples a texture IMAGE per pixel ----
+// Keys are [order-preserving depth bits (32) | ~index (32)], index = triangle (a key plane per face) or face * ntri + triangle (shared:
+// ONE plane for all faces = the reference called once per mesh, in order, on the same image and depth buffer).
+// Pass 1, one thread per (face, triangle): the box walk of tri_depth_kernel with the line that is commented out there and live here
+// (:418): on the two-pixel frame border the inside test is bypassed and the weights are extrapolated ((1,0,0) for zero area).
+__global__ __launch_bounds__(256) void tex_depth_kernel(const float *__restrict__ vertices, const int *__restrict__ tri,
+                                                        const float *__restrict__ depth0, unsigned long long *__restrict__ zkey,
+                                                        int nver, int ntri, int h, int w, int planar, int shared) {
+    const int i = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+    if (i >= ntri) return;
+    const float *v = vertices + (size_t)f * face_stride(planar, nver);
+    const int t0 = tri[3 * i], t1 = tri[3 * i + 1], t2 = tri[3 * i + 2];
+    const float p0x = vtx(v, planar, nver, t0, 0), p0y = vtx(v, planar, nver, t0, 1), d0 = vtx(v, planar, nver, t0, 2);
+    const float p1x = vtx(v, planar, nver, t1, 0), p1y = vtx(v, planar, nver, t1, 1), d1 = vtx(v, planar, nver, t1, 2);
+    const float p2x = vtx(v, planar, nver, t2, 0), p2y = vtx(v, planar, nver, t2, 1), d2 = vtx(v, planar, nver, t2, 2);
+    const int x_min = max((int)ceilf(fminf(p0x, fminf(p1x, p2x))), 0), x_max = min((int)floorf(fmaxf(p0x, fmaxf(p1x, p2x))), w - 1);
+    const int y_min = max((int)ceilf(fminf(p0y, fminf(p1y, p2y))), 0), y_max = min((int)floorf(fmaxf(p0y, fmaxf(p1y, p2y))), h - 1);
+    if (x_max < x_min || y_max < y_min) return;
+    const size_t plane = shared ? 0 : (size_t)f * h * w;
+    const unsigned long long lo = (unsigned long long)~(shared ? (unsigned)f * (unsigned)ntri + (unsigned)i : (unsigned)i);
+    for (int y = y_min; y <= y_max; ++y)
+        for (int x = x_min; x <= x_max; ++x) {
+            const Bary b = bary((float)x, (float)y, p0x, p0y, p1x, p1y, p2x, p2y);
+            if (!(x < 2 || x > w - 3 || y < 2 || y > h - 3 || b.in)) continue;
+            const float depth = b.w0 * d0 + b.w1 * d1 + b.w2 * d2;
+            const size_t px = plane + (size_t)y * w + x;
+            if (!(depth > depth0[px])) continue;
+            atomicMax(&zkey[px], ((unsigned long long)depth_key(depth == 0.0f ? 0.0f : depth) << 32) | lo);
+        }
+}
+
+namespace {
+__device__ __forceinline__ void store_pixel(float *o, float v) { *o = v; }
+__device__ __forceinline__ void store_pixel(unsigned char *o, float v) { *o = (unsigned char)fminf(fmaxf(rintf(v), 0.0f), 255.0f); }
+}  // namespace
+
+// Pass 2, one thread per (key plane, pixel): where a key won, the weights and the depth of the winner re-derived with the same
+// expressions, its texture coordinate (:427; x through tex_tri, y through the MESH triangle's indices, :393-398, row stride 3),
+// the clamp (:428-429, written so that NaN becomes 0 -- the reference converts NaN to int there), the sample (:433-449) and the
+// stores.  TexT float or uint8 (read as (float)byte), ImgT float or uint8 (uint8(clip(rint(v), 0, 255)), as uv_scatter_kernel).
+template <typename TexT, typename ImgT>
+__global__ __launch_bounds__(256) void tex_resolve_kernel(const float *__restrict__ vertices, const int *__restrict__ tri,
+                                                          const int *__restrict__ tex_tri, const float *__restrict__ tex_coords,
+                                                          const TexT *__restrict__ texture, const unsigned long long *__restrict__ zkey,
+                                                          ImgT *__restrict__ image, float *__restrict__ depth, int nver, int ntri, int h,
+                                                          int w, int c, int planar, int shared, int tex_per_face, int th, int tw, int tc,
+                                                          int mapping) {
+    const int px = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
+    if (px >= h * w) return;
+    const size_t o = (size_t)g * h * w + px;
+    const unsigned long long k = zkey[o];
+    if (k == 0ull) return;
+    unsigned idx = ~(unsigned)k;
+    asm volatile("" : "+v"(idx));                            // the opaque copy of raster_shade_kernel (hipcc 7.2 mask loss)
+    int f = g, i = (int)idx;
+    if (shared) { f = (int)(idx / (unsigned)ntri); i = (int)(idx - (unsigned)f * (unsigned)ntri); }
+    const int y = px / w, x = px % w;
+    const float *v = vertices + (size_t)f * face_stride(planar, nver);
+    const int t0 = tri[3 * i], t1 = tri[3 * i + 1], t2 = tri[3 * i + 2];
+    const Bary b = bary((float)x, (float)y, vtx(v, planar, nver, t0, 0), vtx(v, planar, nver, t0, 1), vtx(v, planar, nver, t1, 0),
+                        vtx(v, planar, nver, t1, 1), vtx(v, planar, nver, t2, 0), vtx(v, planar, nver, t2, 1));
+    depth[o] = b.w0 * vtx(v, planar, nver, t0, 2) + b.w1 * vtx(v, planar, nver, t1, 2) + b.w2 * vtx(v, planar, nver, t2, 2);
+    float tx = b.w0 * tex_coords[3 * tex_tri[3 * i]] + b.w1 * tex_coords[3 * tex_tri[3 * i + 1]] + b.w2 * tex_coords[3 * tex_tri[3 * i + 2]];
+    float ty = b.w0 * tex_coords[3 * t0 + 1] + b.w1 * tex_coords[3 * t1 + 1] + b.w2 * tex_coords[3 * t2 + 1];
+    const float xhi = (float)(tw - 1), yhi = (float)(th - 1);
+    tx = tx > xhi ? xhi : tx; tx = tx >= 0 ? tx : 0.0f;
+    ty = ty > yhi ? yhi : ty; ty = ty >= 0 ? ty : 0.0f;
+    const TexT *t = texture + (tex_per_face ? (size_t)f * th * tw * tc : 0);
+    ImgT *out = image + o * c;
+    if (mapping == 0) {
+        const TexT *s = t + ((size_t)(int)roundf(ty) * tw + (int)roundf(tx)) * tc;
+        for (int q = 0; q < c; ++q) store_pixel(out + q, (float)s[q]);
+    } else {
+        const float fx = floorf(tx), fy = floorf(ty);
+        const float xd = tx - fx, yd = ty - fy;
+        const size_t x0 = (size_t)(int)fx * tc, x1 = (size_t)(int)ceilf(tx) * tc;
+        const TexT *r0 = t + (size_t)(int)fy * tw * tc, *r1 = t + (size_t)(int)ceilf(ty) * tw * tc;
+        for (int q = 0; q < c; ++q)
+            store_pixel(out + q, bilerp((float)r0[x0 + q], (float)r0[x1 + q], (float)r1[x0 + q], (float)r1[x1 + q], xd, yd));
+    }
+}
+
 void launch_mesh_normals(const float *vertices, const int *tri, const int *adj_off, const int *adj_tri, float *tri_normal,
                          float *normal, unsigned *mm, int F, int nver, int ntri, int planar, hipStream_t s) {
     // per-face extrema start at +inf / -inf in key space
@@ -483,6 +571,22 @@ void launch_rasterize_triangles(const float *vertices, const int *tri, unsigned 
     (void)hipMemsetAsync(zkey, 0, sizeof(unsigned long long) * (size_t)F * h * w, s);
     tri_depth_kernel<<<dim3((ntri + 255) / 256, F), 256, 0, s>>>(vertices, tri, depth, zkey, nver, ntri, h, w, planar);
     tri_resolve_kernel<<<dim3((h * w + 255) / 256, F), 256, 0, s>>>(vertices, tri, zkey, depth, tri_buf, weight, nver, h, w, planar);
+}
+
+void launch_render_texture(const float *vertices, const int *tri, const int *tex_tri, const float *tex_coords, const void *texture,
+                           int tex_u8, int tex_per_face, int th, int tw, int tc, int mapping, unsigned long long *zkey, void *image,
+                           int image_u8, float *depth, int F, int nver, int ntri, int h, int w, int c, int planar, int shared,
+                           hipStream_t s) {
+    const int planes = shared ? 1 : F;
+    (void)hipMemsetAsync(zkey, 0, sizeof(unsigned long long) * (size_t)planes * h * w, s);
+    tex_depth_kernel<<<dim3((ntri + 255) / 256, F), 256, 0, s>>>(vertices, tri, depth, zkey, nver, ntri, h, w, planar, shared);
+    const dim3 grid((h * w + 255) / 256, planes);
+#define SYN_TEX_RESOLVE(TexT, ImgT)                                                                                                 \
+    tex_resolve_kernel<TexT, ImgT><<<grid, 256, 0, s>>>(vertices, tri, tex_tri, tex_coords, (const TexT *)texture, zkey, (ImgT *)image, \
+                                                        depth, nver, ntri, h, w, c, planar, shared, tex_per_face, th, tw, tc, mapping)
+    if (tex_u8) { if (image_u8) SYN_TEX_RESOLVE(unsigned char, unsigned char); else SYN_TEX_RESOLVE(unsigned char, float); }
+    else { if (image_u8) SYN_TEX_RESOLVE(float, unsigned char); else SYN_TEX_RESOLVE(float, float); }
+#undef SYN_TEX_RESOLVE
 }
 
 void launch_vertex_visibility(const int *tri_buf, const int *tri, unsigned char *visible, int F, int nver, int ntri, int h, int w,

@@ -286,6 +286,12 @@ void launch_add_weighted(const unsigned char *a, float alpha, const unsigned cha
 void launch_rasterize_triangles(const float *vertices, const int *tri, unsigned long long *zkey /*[F,h,w] scratch*/, float *depth /*[F,h,w]*/,
                                 int *tri_buf /*[F,h,w]*/, float *weight /*[F,h,w,3]*/, int F, int nver, int ntri, int h, int w, int planar,
                                 hipStream_t s);
+// _render_texture_core for F meshes: image / depth in-out, [F,h,w,c] / [F,h,w] or, shared, ONE [h,w,c] / [h,w] all faces compete in;
+// texture [T,th,tw,tc] float or uint8 (tex_per_face: T = F, else 1), image float or uint8; zkey [shared ? 1 : F, h, w] scratch
+void launch_render_texture(const float *vertices, const int *tri, const int *tex_tri, const float *tex_coords /*[tex_nver,3]*/,
+                           const void *texture, int tex_u8, int tex_per_face, int th, int tw, int tc, int mapping, unsigned long long *zkey,
+                           void *image, int image_u8, float *depth, int F, int nver, int ntri, int h, int w, int c, int planar, int shared,
+                           hipStream_t s);
 void launch_vertex_visibility(const int *tri_buf /*[F,h,w]*/, const int *tri, unsigned char *visible /*[F,nver], zeroed here*/, int F,
                               int nver, int ntri, int h, int w, hipStream_t s);
 void launch_sample_vertex_colors(const float *vertices, const unsigned char *image /*[h,w,ch]*/, float *out /*[F,nver,ch]*/, int F, int nver,

@@ -3,6 +3,7 @@
 // launch sequence of the MobileNetV2 forward (reference mobilenetv2_backbone.py:173-189).
 #include "../../include/synergy_hip.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -316,6 +317,11 @@ struct syn_handle {
     int *k_tri = nullptr, *k_adj_off = nullptr, *k_adj_tri = nullptr;
     int k_ntri = 0;
     int topo_slot = 0;
+    // texture coordinates of syn_render_texture, per topology slot (syn_load_tex_coords): [tex_nver,3] floats, then the slot's
+    // tex_triangles [ntri,3] where the caller gave some (texc_own_tri); dropped when the slot's topology is replaced
+    float *d_texc[2] = {nullptr, nullptr};
+    int texc_nver[2] = {0, 0}, texc_own_tri[2] = {0, 0};
+    int tri_max[2] = {0, 0};       // the largest vertex index of each slot's triangles
     void *rws = nullptr;           // render scratch: tri normals | min/max keys | z keys
     size_t rws_bytes = 0;
     // FaceBoxes detector: packed weights + per-frame scratch (syn_load_detector / syn_detect)
@@ -951,6 +957,7 @@ int syn_destroy(syn_handle *h) {
     if (h->k_tri) (void)hipFree(h->k_tri);
     if (h->k_adj_off) (void)hipFree(h->k_adj_off);
     if (h->k_adj_tri) (void)hipFree(h->k_adj_tri);
+    for (float *p : h->d_texc) if (p) (void)hipFree(p);
     if (h->rws) (void)hipFree(h->rws);
     if (h->d_det) (void)hipFree(h->d_det);
     if (h->dws) (void)hipFree(h->dws);
@@ -2385,6 +2392,11 @@ int upload_topology(syn_handle *h, const int32_t *tri, int ntri, int nver, int *
 }
 struct Topo { const int *tri, *adj_off, *adj_tri; int ntri, nver; };
 // the topology syn_mesh_shade* / syn_rasterize work on (syn_select_topology); tri == nullptr: not loaded
+int drop_tex_coords(syn_handle *h, int slot) {
+    if (h->d_texc[slot]) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(h->d_texc[slot]); h->d_texc[slot] = nullptr; }
+    h->texc_nver[slot] = h->texc_own_tri[slot] = 0;
+    return SYN_OK;
+}
 Topo current_topo(const syn_handle *h) {
     if (h->topo_slot == 1) return Topo{h->k_tri, h->k_adj_off, h->k_adj_tri, h->k_ntri, h->n_keep};
     return Topo{h->d_tri, h->d_adj_off, h->d_adj_tri, h->ntri, h->tri_nver};
@@ -2397,9 +2409,12 @@ int syn_load_triangles(syn_handle *h, const int32_t *tri, int ntri, int nver) {
     for (int i = 0; i < 3 * ntri; ++i)
         if (tri[i] < 0 || tri[i] >= nver) return fail(SYN_ERR_INVALID, "syn_load_triangles: tri[%d]=%d out of range", i, tri[i]);
     DeviceGuard g(h->device);
-    int rc = upload_topology(h, tri, ntri, nver, &h->d_tri, &h->d_adj_off, &h->d_adj_tri);
+    int rc = drop_tex_coords(h, 0);
+    if (rc) return rc;
+    rc = upload_topology(h, tri, ntri, nver, &h->d_tri, &h->d_adj_off, &h->d_adj_tri);
     if (rc) { h->ntri = h->tri_nver = 0; return rc; }
     h->ntri = ntri; h->tri_nver = nver;
+    h->tri_max[0] = *std::max_element(tri, tri + 3 * (size_t)ntri);
     h->topo_slot = 0;
     return SYN_OK;
 }
@@ -2421,6 +2436,7 @@ int syn_load_uv_map(syn_handle *h, const int32_t *coord_u, const int32_t *coord_
     for (int i = 0; i < 3 * ntri_kept; ++i)
         if (tri_kept[i] < 0 || tri_kept[i] >= n_keep) return fail(SYN_ERR_INVALID, "syn_load_uv_map: tri_kept[%d]=%d out of range", i, tri_kept[i]);
     DeviceGuard g(h->device);
+    if (int rc0 = drop_tex_coords(h, 1)) return rc0;
     if (h->d_uv) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(h->d_uv); h->d_uv = nullptr; }
     h->uv_nver = h->n_keep = h->k_ntri = 0;
     if (h->topo_slot == 1) h->topo_slot = 0;
@@ -2431,6 +2447,7 @@ int syn_load_uv_map(syn_handle *h, const int32_t *coord_u, const int32_t *coord_
     int rc = upload_topology(h, tri_kept, ntri_kept, n_keep, &h->k_tri, &h->k_adj_off, &h->k_adj_tri);
     if (rc) return rc;
     h->uv_nver = nver; h->n_keep = n_keep; h->k_ntri = ntri_kept;
+    h->tri_max[1] = *std::max_element(tri_kept, tri_kept + 3 * (size_t)ntri_kept);
     for (int i = 0; i < 4; ++i) h->uv_max[i] = mx[i];
     return SYN_OK;
 }
@@ -2547,6 +2564,60 @@ int syn_rasterize_triangles(syn_handle *h, const float *vertices, int F, int pla
     if (rc) return rc;
     syn::launch_rasterize_triangles(vertices, T.tri, (unsigned long long *)h->rws, depth_buffer, triangle_buffer, barycentric_weight, F,
                                     T.nver, T.ntri, H, W, planar, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+int syn_load_tex_coords(syn_handle *h, const float *tex_coords, int tex_nver, const int32_t *tex_triangles) {
+    if (!h || !tex_coords || tex_nver <= 0) return fail(SYN_ERR_INVALID, "syn_load_tex_coords: bad argument");
+    const int slot = h->topo_slot;
+    const Topo tp = current_topo(h);
+    const int ntri = tp.ntri;
+    if (!tp.tri || !ntri) return fail(SYN_ERR_NOT_LOADED, "syn_load_tex_coords: triangles not loaded");
+    if (h->tri_max[slot] >= tex_nver)                    // y is read through the MESH triangle's indices (rasterize_kernel.cpp:393-398)
+        return fail(SYN_ERR_INVALID, "syn_load_tex_coords: the mesh triangles reach vertex %d, tex_nver=%d", h->tri_max[slot], tex_nver);
+    for (int i = 0; tex_triangles && i < 3 * ntri; ++i)
+        if (tex_triangles[i] < 0 || tex_triangles[i] >= tex_nver)
+            return fail(SYN_ERR_INVALID, "syn_load_tex_coords: tex_triangles[%d]=%d out of range", i, tex_triangles[i]);
+    DeviceGuard g(h->device);
+    int rc = drop_tex_coords(h, slot);
+    if (rc) return rc;
+    const size_t fb = sizeof(float) * 3 * (size_t)tex_nver, tb = tex_triangles ? sizeof(int32_t) * 3 * (size_t)ntri : 0;
+    HIP_TRY(hipMalloc((void **)&h->d_texc[slot], fb + tb));
+    HIP_TRY(hipMemcpy(h->d_texc[slot], tex_coords, fb, hipMemcpyHostToDevice));
+    if (tb) HIP_TRY(hipMemcpy((char *)h->d_texc[slot] + fb, tex_triangles, tb, hipMemcpyHostToDevice));
+    h->texc_nver[slot] = tex_nver; h->texc_own_tri[slot] = tb != 0;
+    return SYN_OK;
+}
+
+int syn_render_texture(syn_handle *h, const float *vertices, int F, int planar, const void *texture, int tex_u8, int T, int tex_h, int tex_w,
+                       int tex_c, int mapping_type, void *image, int image_u8, float *depth_buffer, int H, int W, int c, int shared,
+                       void *stream) {
+    if (!h || !vertices || !texture || !image || !depth_buffer) return fail(SYN_ERR_INVALID, "syn_render_texture: NULL argument");
+    if (F <= 0 || F > 65535 || H <= 0 || W <= 0 || (long long)F * H * W >= (1ll << 31))
+        return fail(SYN_ERR_INVALID, "syn_render_texture: F=%d H=%d W=%d (F <= 65535, F*H*W must stay below 2^31)", F, H, W);
+    if (c < 1 || c > 4 || tex_c > 4 || c > tex_c) return fail(SYN_ERR_INVALID, "syn_render_texture: c=%d tex_c=%d (1 <= c <= tex_c <= 4)", c, tex_c);
+    if (T != 1 && T != F) return fail(SYN_ERR_INVALID, "syn_render_texture: T=%d textures for F=%d faces (1 or F)", T, F);
+    if (mapping_type != 0 && mapping_type != 1) return fail(SYN_ERR_INVALID, "syn_render_texture: mapping_type=%d (0 nearest, 1 bilinear)", mapping_type);
+    if (tex_h <= 0 || tex_w <= 0 || tex_h > (1 << 24) || tex_w > (1 << 24) || (long long)T * tex_h * tex_w >= (1ll << 31))
+        return fail(SYN_ERR_INVALID, "syn_render_texture: T=%d tex_h=%d tex_w=%d (sides <= 2^24, T*tex_h*tex_w below 2^31)", T, tex_h, tex_w);
+    const Topo tp = current_topo(h);
+    if (!tp.tri) return fail(SYN_ERR_NOT_LOADED, "syn_render_texture: triangles not loaded");
+    const int slot = h->topo_slot;
+    if (!h->d_texc[slot]) return fail(SYN_ERR_NOT_LOADED, "syn_render_texture: texture coordinates not loaded (syn_load_tex_coords)");
+    if ((unsigned long long)F * (unsigned long long)tp.ntri >= (1ull << 32))
+        return fail(SYN_ERR_INVALID, "syn_render_texture: F=%d meshes of %d triangles exceed the 32-bit index field of the key", F, tp.ntri);
+    if (planar < 0 || (planar > 1 && planar < tp.nver))
+        return fail(SYN_ERR_INVALID, "syn_render_texture: planar=%d (0, 1 or a row pitch >= %d)", planar, tp.nver);
+    if (planar == 1) planar = tp.nver;
+    DeviceGuard g(h->device);
+    int rc = ensure_rws(h, sizeof(unsigned long long) * (size_t)(shared ? 1 : F) * H * W);
+    if (rc) return rc;
+    const float *tc = h->d_texc[slot];
+    const int *tex_tri = h->texc_own_tri[slot] ? (const int *)(tc + 3 * (size_t)h->texc_nver[slot]) : tp.tri;
+    syn::launch_render_texture(vertices, tp.tri, tex_tri, tc, texture, tex_u8 != 0, T == F && F > 1, tex_h, tex_w, tex_c, mapping_type,
+                               (unsigned long long *)h->rws, image, image_u8 != 0, depth_buffer, F, tp.nver, tp.ntri, H, W, c, planar,
+                               shared != 0, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return SYN_OK;
 }

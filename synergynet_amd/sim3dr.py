@@ -22,6 +22,11 @@ from a frame, and `texture_from_image` chains them into a UV texture image (and 
 `render_batch(uv_tex=)` and `uv_vertex_colors` consume.  syn_rasterize_triangles / syn_vertex_visibility /
 syn_sample_vertex_colors / syn_uv_scatter.  `fill_texture` (and `texture_from_image(fill=True)`) completes the texels no vertex
 wrote by a push-pull over the texture's pyramid, optionally merging several views of one face first: syn_texture_fill.
+
+Per-pixel texture mapping: `render_texture_core` is the last compute entry of the reference's binding (its `_render_texture_core`,
+commented out in rasterize.pyx:104-123): a z-buffer walk that samples the texture IMAGE per pixel, nearest or bilinear, so nothing
+between the vertices is thrown away.  `render_texture_batch` is its device-resident form for F meshes and the model's UV map
+(`uv_tex_coords`), all faces in one z-buffer or each in its own planes: syn_load_tex_coords / syn_render_texture.
 """
 from __future__ import annotations
 
@@ -58,6 +63,25 @@ def _count_upload(m, slot):
     m._topology_uploads[slot] += 1
 
 
+def _texc_keys(m):
+    """What the two topology slots hold as texture coordinates (syn_load_tex_coords); `model._tex_coord_uploads` counts the uploads."""
+    if not hasattr(m, '_texc_key'):
+        m._texc_key, m._tex_coord_uploads = [None, None], [0, 0]
+    return m._texc_key
+
+
+def _ensure_tex_coords(m, slot, key, make):
+    """The texture coordinates `make()` returns ([tex_nver,3] float32, [ntri,3] int32 or None) in topology slot `slot`, selected;
+    uploaded when `key` differs from what the slot holds."""
+    _select(m, slot)
+    if _texc_keys(m)[slot] != key:
+        tc, tt = make()
+        abi.check(m._lib.syn_load_tex_coords(m._h, tc.ctypes.data_as(C.c_void_p), tc.shape[0],
+                                             tt.ctypes.data_as(C.c_void_p) if tt is not None else None))
+        m._texc_key[slot] = key
+        m._tex_coord_uploads[slot] += 1
+
+
 def _select(m, slot):
     """Point syn_mesh_shade* / syn_rasterize at a topology slot (0: syn_load_triangles, 1: the kept mesh); a host-side switch."""
     abi.check(m._lib.syn_select_topology(m._h, slot))
@@ -69,6 +93,7 @@ def _ensure_topology(m, triangles, nver):
         abi.check(m._lib.syn_load_triangles(m._h, t.ctypes.data_as(C.c_void_p), t.shape[0], nver))
         m._tri_key = (key, nver)
         _count_upload(m, 0)
+        _texc_keys(m)[0] = None                          # the handle drops a slot's texture coordinates with its topology
     _select(m, 0)
     return t
 
@@ -94,6 +119,7 @@ def _ensure_uv_map(m):
         abi.check(m._lib.syn_load_uv_map(m._h, ptr(cu), ptr(cv), cu.size, ptr(keep), keep.size, ptr(tri), tri.shape[0]))
         m._uv_key = (objs, cu.size, keep.size)
         _count_upload(m, 1)
+        _texc_keys(m)[1] = None
     return m._uv_key[1], m._uv_key[2]
 
 
@@ -338,6 +364,113 @@ def texture_from_image(model, img, meshes, tex_hw=256, occlusion=True, fill=Fals
         abi.check(model._lib.syn_uv_scatter(model._h, colors.data_ptr(), visible.data_ptr() if visible is not None else None, F, ch,
                                             tex.data_ptr(), mask.data_ptr(), th, tw, model._stream()))
     return (fill_texture(model, tex, mask) if fill else tex), mask
+
+
+def _render_texture(m, verts_t, F, planar, tex_t, mapping, image, depth, shared):
+    T, th, tw, tc = tex_t.shape
+    H, W, c = image.shape[-3:]
+    with torch.cuda.device(m.device):
+        abi.check(m._lib.syn_render_texture(m._h, verts_t.data_ptr(), F, int(planar), tex_t.data_ptr(), int(tex_t.dtype == torch.uint8), T, th,
+                                            tw, tc, int(mapping), image.data_ptr(), int(image.dtype == torch.uint8), depth.data_ptr(), H, W,
+                                            c, int(bool(shared)), m._stream()))
+
+
+def render_texture_core(image, vertices, triangles, texture, tex_coords, tex_triangles, depth_buffer, nver, tex_nver, ntri, h, w, c,
+                        tex_h, tex_w, tex_c, mapping_type):
+    """The argument list of the reference's (commented-out) binding, Sim3DR/lib/rasterize.pyx:104-123 -> rasterize_kernel.cpp:353-458:
+    image float32 [h,w,c] and depth_buffer float32 [h,w] are C-contiguous arrays the CALLER initialises and that are updated in place;
+    vertices [nver,3] float32, triangles [>= ntri,3] int32, texture float32 [tex_h,tex_w,tex_c], tex_coords [tex_nver,3] float32 (x =
+    texture column, y = row), tex_triangles [>= ntri,3] int32, mapping_type 0 nearest / 1 bilinear.  Where a triangle is deeper than
+    depth_buffer the pixel gets the texture's colour at its interpolated coordinate and the depth; every other element keeps the
+    caller's value.  include/synergy_hip.h states the semantics, the reference's three quirks included."""
+    m = _model()
+    for a, n, name in ((image, h * w * c, 'image'), (depth_buffer, h * w, 'depth_buffer')):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or not a.flags.c_contiguous or a.size != n:
+            raise TypeError(f'{name} must be a C-contiguous float32 array of {n} elements (rasterize.pyx:104-123)')
+    v = np.ascontiguousarray(vertices, dtype=np.float32)
+    t, tt = np.asarray(triangles), np.asarray(tex_triangles)
+    tex = np.ascontiguousarray(texture, dtype=np.float32)
+    tc = np.ascontiguousarray(tex_coords, dtype=np.float32)
+    if not 0 < ntri <= min(t.shape[0], tt.shape[0]):
+        raise ValueError(f'ntri={ntri} with {t.shape[0]} triangles and {tt.shape[0]} tex_triangles')
+    if v.shape != (nver, 3) or tc.shape != (tex_nver, 3) or tex.size != tex_h * tex_w * tex_c:
+        raise ValueError('vertices must be [nver,3], tex_coords [tex_nver,3] and texture [tex_h,tex_w,tex_c]')
+    _ensure_topology(m, t[:ntri], nver)
+    m._tri_obj = None                                    # slot 0 may no longer hold the model's own topology: render_batch re-checks
+    tt = np.ascontiguousarray(tt[:ntri], dtype=np.int32)
+    _ensure_tex_coords(m, 0, ('arrays', tex_nver, zlib.crc32(tc.tobytes()), zlib.crc32(tt.tobytes())), lambda: (tc, tt))
+    img_d = torch.from_numpy(image.reshape(h, w, c)).to(m.device)
+    dep_d = torch.from_numpy(depth_buffer.reshape(h, w)).to(m.device)
+    _render_texture(m, torch.from_numpy(v).to(m.device), 1, 0, torch.from_numpy(tex.reshape(1, tex_h, tex_w, tex_c)).to(m.device),
+                    mapping_type, img_d, dep_d, True)
+    image.reshape(-1)[...] = img_d.cpu().numpy().reshape(-1)
+    depth_buffer.reshape(-1)[...] = dep_d.cpu().numpy().reshape(-1)
+
+
+def uv_tex_coords(model, tex_h, tex_w, kept=False):
+    """The texture coordinates of the model's UV asset for a tex_h x tex_w texture, [n,3] float32 (n = all vertices, or the kept subset):
+    x = uv[:,0] * (tex_w-1), y = (tex_h-1) - uv[:,1] * (tex_h-1), z = 0, evaluated in the asset's own dtype and cast once.  The
+    continuous counterpart of params.uv_pixel_coords plus the row flip of the UV lookup: a texture from texture_from_image lands where
+    it was taken from."""
+    pp = getattr(model, 'param_pack', None)
+    if pp is None or getattr(pp, 'uv_vert', None) is None:
+        raise RuntimeError('Missing data: the model has no UV asset (BFM_UV.npy)')
+    uv = np.asarray(pp.uv_vert)
+    x, y = uv[:, 0] * (int(tex_w) - 1), (int(tex_h) - 1) - uv[:, 1] * (int(tex_h) - 1)
+    out = np.stack([x, y, np.zeros_like(x)], 1).astype(np.float32)
+    if kept:
+        if pp.keep_ind is None:
+            raise RuntimeError('Missing data: the model has no kept-vertex list (keptInd.npy)')
+        out = out[np.asarray(pp.keep_ind).reshape(-1)]
+    return np.ascontiguousarray(out)
+
+
+def render_texture_batch(model, meshes, uv_tex, height=None, width=None, background=None, mapping='bilinear', shared=True, kept=False):
+    """Per-pixel textured render of F meshes on the device.  meshes [F,3,N] float32 device tensor in image coordinates (what
+    reconstruct(..., dense=True) returns; pitched rows are read in place); uv_tex the UV texture image, uint8 or float32, [th,tw,c] (one
+    for all faces) or [F,th,tw,c] -- what texture_from_image / fill_texture produce; its texture coordinates are uv_tex_coords(model,
+    th, tw), uploaded once per (topology slot, texture size).  mapping 'nearest' or 'bilinear'.
+    shared=True: ONE image [H,W,c] and depth [H,W]; all faces compete in one z-buffer (proper occlusion between faces; the earliest
+    face wins among equal depths).  shared=False: [F,H,W,c] and [F,H,W], every face its own planes.
+    background: uint8 or float32 [H,W,c] (or [F,H,W,c] with shared=False), copied, decides the image dtype and c <= the texture's
+    channels; default zeros float32 of height x width with the texture's channels.  A uint8 image stores uint8(clip(rint(v), 0, 255)).
+    kept=True draws the model's kept vertex subset with the kept topology.  Returns (image, depth) device tensors; depth is -1e8 where
+    nothing was drawn."""
+    F, _, n = meshes.shape
+    tex_t = uv_tex if isinstance(uv_tex, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(uv_tex))
+    if tex_t.dtype not in (torch.uint8, torch.float32) or tex_t.dim() not in (3, 4) or tex_t.shape[-1] > 4:
+        raise TypeError('uv_tex must be uint8 or float32, [th,tw,c] or [F,th,tw,c] with c <= 4')
+    tex_t = tex_t.to(model.device).contiguous()
+    tex_t = tex_t if tex_t.dim() == 4 else tex_t[None]
+    if tex_t.shape[0] not in (1, F):
+        raise ValueError(f'{tex_t.shape[0]} textures for {F} faces (one, or one per face)')
+    mapping_type = {'nearest': 0, 'bilinear': 1}.get(mapping)
+    if mapping_type is None:
+        raise ValueError("mapping must be 'nearest' or 'bilinear'")
+    th, tw = int(tex_t.shape[1]), int(tex_t.shape[2])
+    if kept:
+        meshes = gather_kept(model, meshes)
+    else:
+        _ensure_model_topology(model, n)
+    slot = 1 if kept else 0
+    uv = model.param_pack.uv_vert
+    _ensure_tex_coords(model, slot, ('uv', th, tw, id(uv)), lambda: (uv_tex_coords(model, th, tw, kept=kept), None))
+    model._texc_uv = uv                                  # held, so that its id stays its own
+    planar = _planar_arg(meshes)
+    lead = () if shared else (F,)
+    if background is None:
+        if height is None or width is None:
+            raise ValueError('give height and width, or a background')
+        image = torch.zeros(lead + (int(height), int(width), int(tex_t.shape[3])), dtype=torch.float32, device=model.device)
+    else:
+        bg = background if isinstance(background, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(background))
+        if bg.dtype not in (torch.uint8, torch.float32) or bg.dim() not in (3, 4) or (bg.dim() == 4 and (shared or bg.shape[0] != F)):
+            raise TypeError('background must be uint8 or float32 [H,W,c] (or [F,H,W,c] with shared=False)')
+        bg = bg.to(model.device)
+        image = (bg.expand(lead + tuple(bg.shape)) if bg.dim() == 3 else bg).contiguous().clone()
+    depth = torch.full(tuple(image.shape[:-1]), -1e8, dtype=torch.float32, device=model.device)
+    _render_texture(model, meshes, F, planar, tex_t, mapping_type, image, depth, shared)
+    return image, depth
 
 
 def get_normal(vertices, triangles):
