@@ -421,6 +421,52 @@ int syn_landmarks_pose(syn_handle *h, const float *param, int B, int param_len, 
  * the de-whitened translation WITHOUT the ROI affine (the reference concatenates P before predict_pose rescales t3d). */
 int syn_pose_matrix(syn_handle *h, const float *param, int B, float *pmat, void *stream);
 
+/* ---- synergy refinement: MLP_for (landmark residual) and MLP_rev (landmarks -> parameters) ----
+ *
+ * The two point-MLPs of the reference model (backbone_nets/pointnet_backbone.py; built at synergy3DMM.py:82-84 and used at
+ * model_building.py:149-153):   Lr = Lc + 0.05 * MLP_for(Lc, pool, param[:,12:52], param[:,52:62]),   param_S2 = MLP_rev(Lr).
+ * Every GEMM runs on the exact fp32 matrix instruction; a face's result does not depend on the batch it is in.
+ *
+ * FLAT layout (syn_synergy_flat_count floats): the tensors of MLP_for(68).state_dict() and then MLP_rev(68).state_dict() in
+ * state_dict order without num_batches_tracked (checkpoint keys forwardDirection.* / reverseDirection.*), i.e. per MLP all convs
+ * (weight [out,in,1] then bias) followed by all BatchNorms (weight, bias, running_mean, running_var).
+ *
+ * FOLDED layout (syn_synergy_folded_count floats, logical -- the device repack is private): per layer W [out][in] | scale [out] |
+ * shift [out] with scale = gamma / sqrt(var + 1e-5) and shift = (bias - mean) * scale + beta, so y = relu(scale * (W x) + shift):
+ *   MLP_for: conv1 [64][3], conv2 [64][64], conv3 [64][64], conv4 [128][64], conv5 [1024][128],
+ *            conv6 split by input column: Wpoint [512][64] (point features) | Wface [512][2354] (global 1024 | pool 1280 | shape 40 |
+ *            expr 10) | scale [512] | shift [512],  conv7 [256][512], conv8 [128][256], conv9 [3][128]
+ *   MLP_rev: conv1 .. conv5 as above, then the three heads as ONE layer [62][1024] in the order ori 12 | shape 40 | expr 10. */
+size_t syn_synergy_flat_count(void);
+size_t syn_synergy_folded_count(void);
+/* Device-free fold of a flat state into the folded layout (like syn_pack_constants_host).  SYN_ERR_INVALID on wrong counts. */
+int syn_fold_synergy_host(const float *flat, size_t n, float *folded, size_t n_folded);
+
+/* Folds `flat`, repacks it for the kernels and uploads it (6.4 MB); calling it again replaces the weights.  The weights are NOT part
+ * of the constants blob (syn_export_constants): every rank loads them itself. */
+int syn_load_synergy(syn_handle *h, const float *flat, size_t n);
+
+/* Refined landmarks from whitened parameters and the backbone's 1280-d pooled feature.  Lc is reconstructed exactly as
+ * syn_landmarks_pose does (crop space; transform = 1: with the y flip the MLP was trained on) and MLP_for runs on it with the
+ * whitened shape / expression codes; lmk_refined = Lc + 0.05 * residual (the residual is relu'd by the reference: never negative).  With
+ * roi both outputs receive the ROI affine x * sx + x0 / y * sy + y0 / z * (sx + sy) / 2 with sx = (ex - x0) / 120 (lmk_coarse then
+ * equals syn_landmarks_pose(roi) bit for bit).  global_feat: MLP_for's max-pooled feature.  lmk_coarse and lmk_refined must not
+ * overlap.  Scratch (33.8 KB per face, shared by the three entry points) is owned by the handle and grows lazily: calls on one handle
+ * must be ordered on one stream, and the FIRST call at a new largest B frees and reallocates it behind a device-wide synchronisation
+ * -- it stalls every stream once and must not happen inside a stream capture (run the largest batch once before capturing).
+ * SYN_ERR_NOT_LOADED before syn_load_synergy / syn_load_basis; SYN_ERR_INVALID for B <= 0 or NULL pointers or overlapping outputs or
+ * a handle whose backbone is resnet50 (its pooled feature is 2048-d: the refinement is unavailable there). */
+int syn_refine_landmarks(syn_handle *h, const float *param /*[B 62] whitened*/, const float *pool /*[B 1280]*/, int B, int transform,
+                         const float *roi /*nullable [B 5]*/, float *lmk_coarse /*nullable [B 3 68]*/, float *lmk_refined /*[B 3 68]*/,
+                         float *global_feat /*nullable [B 1024]*/, void *stream);
+
+/* The same MLP on landmarks the caller supplies (crop space): no reconstruction and no ROI.  lmk_refined must not overlap lmk. */
+int syn_refine_points(syn_handle *h, const float *lmk /*[B 3 68]*/, const float *pool, const float *param, int B, float *lmk_refined,
+                      float *global_feat /*nullable*/, void *stream);
+
+/* MLP_rev: landmarks [B,3,68] in crop space -> whitened parameters [B,62] (ori 12 | shape 40 | expr 10; relu'd like the reference). */
+int syn_landmarks_to_param(syn_handle *h, const float *lmk /*[B 3 68]*/, int B, float *param /*[B 62]*/, void *stream);
+
 /* ---- introspection (bench / profiling) --------------------------------------------- */
 
 /* Number of kernel launches one per-layer syn_backbone_forward issues. */

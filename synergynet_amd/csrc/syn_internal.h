@@ -322,6 +322,32 @@ void launch_det_nms(const float *cand, const int *n_cand, int max_cand, int top_
                     hipStream_t s);
 int det_sort_capacity();
 
+// ---- synergy refinement: MLP_for / MLP_rev (synergy_kernels.hip) ----
+// Weights: row-major [N][K] fp32, N padded to a multiple of 16 (conv9: 3 -> 16, MLP_rev's head: 62 -> 64) and K to a multiple of 16
+// (conv1: 3 -> 4, one MFMA step) with zeros; scale / shift per output channel, padded like N (syn_load_synergy).
+constexpr int kSynPts = 68;                 // points per face (MLP_for(68) / MLP_rev(68), synergy3DMM.py:82-84)
+constexpr int kSynGlobal = 1024;            // width of the max-pooled global feature
+constexpr int kSynFaceK = kSynGlobal + kPool + 40 + 10;      // per-face input columns of conv6: global | pool | shape | expr = 2354
+constexpr int kSynFaceKpad = (kSynFaceK + 15) / 16 * 16;     // 2368
+struct SynTrunkW { const float *W[5], *scale[5], *shift[5]; };                   // conv1 .. conv5
+struct SynHeadW {
+    const float *W6p, *scale6, *shift6;      // conv6, per-point columns [512][64]
+    const float *W7, *scale7, *shift7;       // [256][512]
+    const float *W8, *scale8, *shift8;       // [128][256]
+    const float *W9, *scale9, *shift9;       // [16][128], rows 3..15 zero
+};
+// conv1-conv5 + max over a face's 68 points: lmk [B,3,68] -> gf[b * gf_pitch + 0..1023] (and gf2 [B,1024] when given); pf: conv2's
+// output [B*68,64] (MLP_for's point features) or null
+void launch_syn_trunk(const SynTrunkW &w, const float *lmk, int B, float *pf, float *gf, int gf_pitch, float *gf2, hipStream_t s);
+// columns 1024 .. 2367 of X6 [B,2368]: pool | whitened param[12:62] | zeros
+void launch_syn_face_concat(const float *pool, const float *param, float *X6, int B, hipStream_t s);
+// out[b][n] = sum_k W[n][k] X[b][k] (scale == null) or relu(scale[n] * sum + shift[n]); W [ceil32(N)][Kpad], Kpad % 16 == 0
+void launch_syn_face_gemm(const float *X, int ldx, const float *W, int Kpad, const float *scale, const float *shift, float *out, int ldo,
+                          int N, int B, hipStream_t s);
+// conv6 .. conv9 on the point features + g6 [B,512] (the per-face half of conv6), out = lmk_in + 0.05 res, then the ROI affine if roi
+void launch_syn_point_head(const SynHeadW &w, const float *pf, const float *g6, const float *lmk_in, const float *roi, float *out, int B,
+                           hipStream_t s);
+
 void launch_pose(const float *param, const float *mean62, const float *std62, const float *roi,
                  double *angles /*nullable together with t3d*/, float *t3d, float *pmat /*nullable [B,3,4]*/, int B, hipStream_t s);
 // landmarks + pose in one launch (recon_kernels.hip lmk_pose_kernel): fp32 landmark tiles, plain fp32 multiply-adds

@@ -296,6 +296,13 @@ static_assert(sizeof(RangeInfo) <= 64 * sizeof(float), "RangeInfo must fit its s
 
 }  // namespace
 
+// where the synergy MLPs' kernel-ready weights sit in syn_handle::d_syn (floats; syn_load_synergy)
+struct SynOffsets {
+    size_t tW[2][5], tscale[2][5], tshift[2][5];      // trunks conv1 .. conv5: [0] MLP_for, [1] MLP_rev
+    size_t W6p, W6f, scale6, shift6, W7, scale7, shift7, W8, scale8, shift8, W9, scale9, shift9;
+    size_t Wrev, scale_rev, shift_rev;                // MLP_rev's three heads as one [64][1024] layer
+};
+
 struct syn_handle {
     int device = 0;
     int arch = 0;                  // 0 = mobilenet_v2 (reference default), 1 = resnet50 (BASELINE config 5)
@@ -324,6 +331,11 @@ struct syn_handle {
     int tri_max[2] = {0, 0};       // the largest vertex index of each slot's triangles
     void *rws = nullptr;           // render scratch: tri normals | min/max keys | z keys
     size_t rws_bytes = 0;
+    // synergy refinement (syn_load_synergy / syn_refine_* / syn_landmarks_to_param): weights + per-call scratch, grown lazily
+    float *d_syn = nullptr;
+    SynOffsets syn_off = {};
+    float *sws = nullptr;          // Lc | point features | conv6 face rows | conv6 face sums | global feature
+    size_t sws_bytes = 0;
     // FaceBoxes detector: packed weights + per-frame scratch (syn_load_detector / syn_detect)
     float *d_det = nullptr;
     void *dws = nullptr;
@@ -959,6 +971,8 @@ int syn_destroy(syn_handle *h) {
     if (h->k_adj_tri) (void)hipFree(h->k_adj_tri);
     for (float *p : h->d_texc) if (p) (void)hipFree(p);
     if (h->rws) (void)hipFree(h->rws);
+    if (h->d_syn) (void)hipFree(h->d_syn);
+    if (h->sws) (void)hipFree(h->sws);
     if (h->d_det) (void)hipFree(h->d_det);
     if (h->dws) (void)hipFree(h->dws);
     delete h;
@@ -2916,6 +2930,240 @@ int syn_pose_matrix(syn_handle *h, const float *param, int B, float *pmat, void 
     if (!h->d_basis) return fail(SYN_ERR_NOT_LOADED, "syn_pose_matrix: whitening statistics not loaded");
     DeviceGuard g(h->device);
     syn::launch_pose(param, basis_mean(h), basis_std(h), nullptr, nullptr, nullptr, pmat, B, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Synergy refinement: MLP_for / MLP_rev of backbone_nets/pointnet_backbone.py (include/synergy_hip.h; kernels: synergy_kernels.hip)
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct SynLayer { int cin, cout; };
+const SynLayer kSynFor[9] = {{3, 64}, {64, 64}, {64, 64}, {64, 128}, {128, 1024}, {64 + syn::kSynFaceK, 512}, {512, 256}, {256, 128}, {128, 3}};
+const SynLayer kSynRev[8] = {{3, 64}, {64, 64}, {64, 64}, {64, 128}, {128, 1024}, {1024, 12}, {1024, 40}, {1024, 10}};
+size_t syn_mlp_count(const SynLayer *L, int n, int per_channel) {
+    size_t c = 0;
+    for (int i = 0; i < n; ++i) c += (size_t)L[i].cin * L[i].cout + (size_t)per_channel * L[i].cout;
+    return c;
+}
+size_t synergy_flat_count() { return syn_mlp_count(kSynFor, 9, 5) + syn_mlp_count(kSynRev, 8, 5); }      // conv bias + 4 BatchNorm vectors
+size_t synergy_folded_count() { return syn_mlp_count(kSynFor, 9, 2) + syn_mlp_count(kSynRev, 8, 2); }  // scale + shift
+
+struct SynFolded { int cin = 0, cout = 0; std::vector<float> W, scale, shift; };
+// one MLP of the flat layout: all convs (weight, bias), then all BatchNorms (gamma, beta, mean, var); eval BatchNorm1d, eps 1e-5
+std::vector<SynFolded> fold_mlp(const float *flat, const SynLayer *L, int n) {
+    std::vector<SynFolded> out(n);
+    const float *conv = flat, *bn = flat + syn_mlp_count(L, n, 1);
+    for (int i = 0; i < n; ++i) {
+        SynFolded &f = out[i];
+        f.cin = L[i].cin; f.cout = L[i].cout;
+        const size_t nw = (size_t)f.cin * f.cout;
+        f.W.assign(conv, conv + nw);
+        const float *bias = conv + nw, *gamma = bn, *beta = bn + f.cout, *mean = bn + 2 * f.cout, *var = bn + 3 * f.cout;
+        f.scale.resize(f.cout); f.shift.resize(f.cout);
+        for (int c = 0; c < f.cout; ++c) {
+            const double sc = (double)gamma[c] / std::sqrt((double)var[c] + 1e-5);
+            f.scale[c] = (float)sc;
+            f.shift[c] = (float)(((double)bias[c] - (double)mean[c]) * sc + (double)beta[c]);
+        }
+        conv += nw + f.cout;
+        bn += 4 * (size_t)f.cout;
+    }
+    return out;
+}
+// MLP_rev's three heads as one [62][1024] layer: ori 12 | shape 40 | expr 10
+SynFolded merge_rev_heads(const std::vector<SynFolded> &r) {
+    SynFolded m;
+    m.cin = 1024;
+    for (int i = 5; i < 8; ++i) {
+        m.cout += r[i].cout;
+        m.W.insert(m.W.end(), r[i].W.begin(), r[i].W.end());
+        m.scale.insert(m.scale.end(), r[i].scale.begin(), r[i].scale.end());
+        m.shift.insert(m.shift.end(), r[i].shift.begin(), r[i].shift.end());
+    }
+    return m;
+}
+// columns [c0, c1) of a layer's weights
+std::vector<float> weight_columns(const SynFolded &f, int c0, int c1) {
+    std::vector<float> w((size_t)f.cout * (c1 - c0));
+    for (int n = 0; n < f.cout; ++n)
+        for (int k = c0; k < c1; ++k) w[(size_t)n * (c1 - c0) + (k - c0)] = f.W[(size_t)n * f.cin + k];
+    return w;
+}
+
+// kernel-ready image: every matrix row-major [rows_pad][cols_pad] zero padded, every vector zero padded to rows_pad
+struct SynBlob {
+    std::vector<float> v;
+    size_t matrix(const std::vector<float> &W, int rows, int cols, int rows_pad, int cols_pad) {
+        const size_t at = v.size();
+        v.resize(at + (size_t)rows_pad * cols_pad, 0.f);
+        for (int r = 0; r < rows; ++r)
+            for (int c = 0; c < cols; ++c) v[at + (size_t)r * cols_pad + c] = W[(size_t)r * cols + c];
+        return at;
+    }
+    size_t vector(const std::vector<float> &x, int n_pad) {
+        const size_t at = v.size();
+        v.resize(at + n_pad, 0.f);
+        for (size_t i = 0; i < x.size(); ++i) v[at + i] = x[i];
+        return at;
+    }
+};
+int pad16(int x) { return (x + 15) / 16 * 16; }
+
+int ensure_sws(syn_handle *h, size_t bytes) {
+    if (bytes <= h->sws_bytes) return SYN_OK;
+    if (h->sws) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->sws)); h->sws = nullptr; h->sws_bytes = 0; }
+    HIP_TRY(hipMalloc(&h->sws, bytes));
+    h->sws_bytes = bytes;
+    return SYN_OK;
+}
+// scratch of a B-face call (floats): Lc [B,3,68] | pf [B*68,64] | X6 [B,2368] | g6 [B,512] | gf [B,1024]
+constexpr size_t kSwsLc = 3 * syn::kSynPts, kSwsPf = 64 * syn::kSynPts, kSwsX6 = syn::kSynFaceKpad, kSwsG6 = 512, kSwsGf = syn::kSynGlobal;
+constexpr size_t kSwsPerFace = kSwsLc + kSwsPf + kSwsX6 + kSwsG6 + kSwsGf;
+
+syn::SynTrunkW trunk_weights(const syn_handle *h, int which) {
+    syn::SynTrunkW w;
+    for (int i = 0; i < 5; ++i) {
+        w.W[i] = h->d_syn + h->syn_off.tW[which][i];
+        w.scale[i] = h->d_syn + h->syn_off.tscale[which][i];
+        w.shift[i] = h->d_syn + h->syn_off.tshift[which][i];
+    }
+    return w;
+}
+
+int synergy_ready(const syn_handle *h, const char *who) {
+    if (h->arch == 1)
+        return fail(SYN_ERR_INVALID, "%s: the synergy refinement needs the 1280-d pooled feature of mobilenet_v2; this handle runs resnet50 (2048-d)", who);
+    if (!h->d_syn) return fail(SYN_ERR_NOT_LOADED, "%s: synergy weights not loaded (syn_load_synergy)", who);
+    return SYN_OK;
+}
+
+// MLP_for on crop-space landmarks `lmk` (device) -> out = (lmk + 0.05 res), ROI affine if roi
+int run_refine(syn_handle *h, const float *lmk, const float *pool, const float *param, int B, const float *roi, float *out, float *global_feat,
+               hipStream_t s) {
+    float *pf = h->sws + kSwsLc * B, *X6 = pf + kSwsPf * B, *g6 = X6 + kSwsX6 * B;
+    const SynOffsets &o = h->syn_off;
+    const float *d = h->d_syn;
+    syn::launch_syn_trunk(trunk_weights(h, 0), lmk, B, pf, X6, syn::kSynFaceKpad, global_feat, s);
+    syn::launch_syn_face_concat(pool, param, X6, B, s);
+    syn::launch_syn_face_gemm(X6, syn::kSynFaceKpad, d + o.W6f, syn::kSynFaceKpad, nullptr, nullptr, g6, 512, 512, B, s);
+    const syn::SynHeadW hw = {d + o.W6p, d + o.scale6, d + o.shift6, d + o.W7, d + o.scale7, d + o.shift7,
+                              d + o.W8, d + o.scale8, d + o.shift8, d + o.W9, d + o.scale9, d + o.shift9};
+    syn::launch_syn_point_head(hw, pf, g6, lmk, roi, out, B, s);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+bool overlap(const float *a, const float *b, size_t n) { return a < b + n && b < a + n; }
+}  // namespace
+
+extern "C" {
+
+size_t syn_synergy_flat_count(void) { return synergy_flat_count(); }
+size_t syn_synergy_folded_count(void) { return synergy_folded_count(); }
+
+int syn_fold_synergy_host(const float *flat, size_t n, float *folded, size_t n_folded) {
+    if (!flat || !folded) return fail(SYN_ERR_INVALID, "syn_fold_synergy_host: NULL argument");
+    if (n != synergy_flat_count() || n_folded != synergy_folded_count())
+        return fail(SYN_ERR_INVALID, "syn_fold_synergy_host: %zu / %zu floats, expected %zu / %zu", n, n_folded, synergy_flat_count(), synergy_folded_count());
+    const std::vector<SynFolded> f = fold_mlp(flat, kSynFor, 9), r = fold_mlp(flat + syn_mlp_count(kSynFor, 9, 5), kSynRev, 8);
+    float *p = folded;
+    auto put = [&p](const std::vector<float> &x) { p = std::copy(x.begin(), x.end(), p); };
+    auto layer = [&put](const SynFolded &L) { put(L.W); put(L.scale); put(L.shift); };
+    for (int i = 0; i < 5; ++i) layer(f[i]);
+    put(weight_columns(f[5], 0, 64));
+    put(weight_columns(f[5], 64, f[5].cin));
+    put(f[5].scale); put(f[5].shift);
+    for (int i = 6; i < 9; ++i) layer(f[i]);
+    for (int i = 0; i < 5; ++i) layer(r[i]);
+    layer(merge_rev_heads(r));
+    if ((size_t)(p - folded) != n_folded) return fail(SYN_ERR_INVALID, "syn_fold_synergy_host: internal layout mismatch");
+    return SYN_OK;
+}
+
+int syn_load_synergy(syn_handle *h, const float *flat, size_t n) {
+    if (!h || !flat) return fail(SYN_ERR_INVALID, "syn_load_synergy: NULL argument");
+    if (n != synergy_flat_count()) return fail(SYN_ERR_INVALID, "syn_load_synergy: %zu floats, expected %zu", n, synergy_flat_count());
+    const std::vector<SynFolded> f = fold_mlp(flat, kSynFor, 9), r = fold_mlp(flat + syn_mlp_count(kSynFor, 9, 5), kSynRev, 8);
+    SynBlob b;
+    SynOffsets o = {};
+    for (int which = 0; which < 2; ++which) {
+        const std::vector<SynFolded> &m = which ? r : f;
+        for (int i = 0; i < 5; ++i) {
+            o.tW[which][i] = b.matrix(m[i].W, m[i].cout, m[i].cin, m[i].cout, i == 0 ? 4 : m[i].cin);     // conv1: K = 3 -> 4 (one MFMA step)
+            o.tscale[which][i] = b.vector(m[i].scale, m[i].cout);
+            o.tshift[which][i] = b.vector(m[i].shift, m[i].cout);
+        }
+    }
+    o.W6p = b.matrix(weight_columns(f[5], 0, 64), 512, 64, 512, 64);
+    o.W6f = b.matrix(weight_columns(f[5], 64, f[5].cin), 512, syn::kSynFaceK, 512, syn::kSynFaceKpad);
+    o.scale6 = b.vector(f[5].scale, 512); o.shift6 = b.vector(f[5].shift, 512);
+    o.W7 = b.matrix(f[6].W, 256, 512, 256, 512); o.scale7 = b.vector(f[6].scale, 256); o.shift7 = b.vector(f[6].shift, 256);
+    o.W8 = b.matrix(f[7].W, 128, 256, 128, 256); o.scale8 = b.vector(f[7].scale, 128); o.shift8 = b.vector(f[7].shift, 128);
+    o.W9 = b.matrix(f[8].W, 3, 128, 16, 128); o.scale9 = b.vector(f[8].scale, 16); o.shift9 = b.vector(f[8].shift, 16);
+    const SynFolded hd = merge_rev_heads(r);
+    o.Wrev = b.matrix(hd.W, hd.cout, 1024, pad16(hd.cout), 1024);
+    o.scale_rev = b.vector(hd.scale, pad16(hd.cout)); o.shift_rev = b.vector(hd.shift, pad16(hd.cout));
+    DeviceGuard g(h->device);
+    if (h->d_syn) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->d_syn)); h->d_syn = nullptr; }     // replacing: nothing may still read the old weights
+    HIP_TRY(hipMalloc(&h->d_syn, b.v.size() * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->d_syn, b.v.data(), b.v.size() * sizeof(float), hipMemcpyHostToDevice));
+    h->syn_off = o;
+    return SYN_OK;
+}
+
+int syn_refine_landmarks(syn_handle *h, const float *param, const float *pool, int B, int transform, const float *roi, float *lmk_coarse,
+                         float *lmk_refined, float *global_feat, void *stream) {
+    if (!h || !param || !pool || !lmk_refined) return fail(SYN_ERR_INVALID, "syn_refine_landmarks: NULL argument");
+    if (B <= 0) return fail(SYN_ERR_INVALID, "syn_refine_landmarks: B=%d", B);
+    int rc = synergy_ready(h, "syn_refine_landmarks");
+    if (rc != SYN_OK) return rc;
+    if (!h->d_basis) return fail(SYN_ERR_NOT_LOADED, "syn_refine_landmarks: 3DMM basis not loaded");
+    if (h->n_lmk != syn::kSynPts) return fail(SYN_ERR_INVALID, "syn_refine_landmarks: the landmark basis has %d points, the MLPs take %d", h->n_lmk, syn::kSynPts);
+    if (lmk_coarse && overlap(lmk_coarse, lmk_refined, kSwsLc * B)) return fail(SYN_ERR_INVALID, "syn_refine_landmarks: lmk_coarse overlaps lmk_refined");
+    DeviceGuard g(h->device);
+    rc = ensure_sws(h, kSwsPerFace * B * sizeof(float));
+    if (rc != SYN_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    float *Lc = h->sws;
+    // crop-space Lc with syn_landmarks_pose's own kernel (no pose: angles == null); with a ROI the caller's coarse copy is that kernel's
+    // ROI output, so that it equals syn_landmarks_pose(roi) bit for bit
+    syn::launch_lmk_pose(param, basis_mean(h), basis_std(h), basis_lmk(h), h->n_lmk, h->nlp, nullptr, transform, Lc, nullptr, nullptr, B, s);
+    if (lmk_coarse) {
+        if (roi) syn::launch_lmk_pose(param, basis_mean(h), basis_std(h), basis_lmk(h), h->n_lmk, h->nlp, roi, transform, lmk_coarse, nullptr, nullptr, B, s);
+        else HIP_TRY(hipMemcpyAsync(lmk_coarse, Lc, kSwsLc * B * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    return run_refine(h, Lc, pool, param, B, roi, lmk_refined, global_feat, s);
+}
+
+int syn_refine_points(syn_handle *h, const float *lmk, const float *pool, const float *param, int B, float *lmk_refined, float *global_feat,
+                      void *stream) {
+    if (!h || !lmk || !pool || !param || !lmk_refined) return fail(SYN_ERR_INVALID, "syn_refine_points: NULL argument");
+    if (B <= 0) return fail(SYN_ERR_INVALID, "syn_refine_points: B=%d", B);
+    int rc = synergy_ready(h, "syn_refine_points");
+    if (rc != SYN_OK) return rc;
+    if (overlap(lmk, lmk_refined, kSwsLc * B)) return fail(SYN_ERR_INVALID, "syn_refine_points: lmk_refined overlaps lmk");
+    DeviceGuard g(h->device);
+    rc = ensure_sws(h, kSwsPerFace * B * sizeof(float));
+    if (rc != SYN_OK) return rc;
+    return run_refine(h, lmk, pool, param, B, nullptr, lmk_refined, global_feat, (hipStream_t)stream);
+}
+
+int syn_landmarks_to_param(syn_handle *h, const float *lmk, int B, float *param, void *stream) {
+    if (!h || !lmk || !param) return fail(SYN_ERR_INVALID, "syn_landmarks_to_param: NULL argument");
+    if (B <= 0) return fail(SYN_ERR_INVALID, "syn_landmarks_to_param: B=%d", B);
+    int rc = synergy_ready(h, "syn_landmarks_to_param");
+    if (rc != SYN_OK) return rc;
+    DeviceGuard g(h->device);
+    rc = ensure_sws(h, kSwsPerFace * B * sizeof(float));
+    if (rc != SYN_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    float *gf = h->sws + (kSwsPerFace - kSwsGf) * B;
+    const SynOffsets &o = h->syn_off;
+    syn::launch_syn_trunk(trunk_weights(h, 1), lmk, B, nullptr, gf, syn::kSynGlobal, nullptr, s);
+    syn::launch_syn_face_gemm(gf, syn::kSynGlobal, h->d_syn + o.Wrev, syn::kSynGlobal, h->d_syn + o.scale_rev, h->d_syn + o.shift_rev, param,
+                              SYN_PARAM_DIM, SYN_PARAM_DIM, B, s);
     HIP_TRY(hipGetLastError());
     return SYN_OK;
 }

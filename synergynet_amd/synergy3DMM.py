@@ -111,6 +111,24 @@ def flatten_backbone(sd: dict, prefix: str = '', arch: str = 'mobilenet_v2') -> 
     return np.concatenate(parts)
 
 
+def synergy_state_from_checkpoint(state_dict):
+    """The forwardDirection.* / reverseDirection.* tensors (MLP_for / MLP_rev, reference synergy3DMM.py:82-84) of a checkpoint's
+    state_dict, DataParallel 'module.' prefixes stripped, as {key: tensor}; None when the checkpoint carries none of them.  A
+    checkpoint that carries only some is broken: KeyError names what is missing.  Device-free."""
+    from .synth import synergy_layers, SYNERGY_PREFIXES
+    found = {}
+    for k, v in state_dict.items():
+        kk = k.replace('module.', '')
+        if kk.startswith(SYNERGY_PREFIXES) and not kk.endswith('num_batches_tracked'):
+            found[kk] = v
+    if not found:
+        return None
+    missing = [k for k, _ in synergy_layers() if k not in found]
+    if missing:
+        raise KeyError(f'checkpoint carries {len(found)} synergy tensors but lacks {missing[:4]}{" ..." if len(missing) > 4 else ""}')
+    return {k: found[k] for k, _ in synergy_layers()}
+
+
 class _Container(nn.Module):
     """Empty node of the state_dict key tree (so state_dict() keys equal the reference's)."""
 
@@ -164,6 +182,7 @@ class SynergyNet(nn.Module):
         self._n_vert = self._n_lmk = 0
         self._have_backbone = self._have_basis = False
         self._range_checked = False
+        self.has_synergy = False        # MLP_for / MLP_rev weights uploaded (load_weights / load_synergy_state)
         if not load_constants:          # constants arrive later through import_constants() (synergynet_amd/dist.py)
             self.eval()
             from . import inference
@@ -339,7 +358,8 @@ class SynergyNet(nn.Module):
 
     def load_weights(self, path):
         """reference synergy3DMM.py:156-164: torch checkpoint {'state_dict': ...} with DataParallel
-        'module.' prefixes; keys this class does not have (MLP_for/MLP_rev, training-only) are ignored.
+        'module.' prefixes.  The two point-MLPs (forwardDirection.* / reverseDirection.*) are uploaded for refine_landmarks /
+        landmarks_to_param when the checkpoint carries them (has_synergy); other keys this class does not have are ignored.
         A checkpoint that carries the 3DMM buffers overrides the .npy values, as in the reference."""
         model_dict = self.state_dict()
         checkpoint = torch.load(path, map_location=lambda storage, loc: storage)['state_dict']
@@ -353,6 +373,18 @@ class SynergyNet(nn.Module):
         self._upload_backbone()
         if basis_touched:
             self._upload_basis()
+        syn_sd = synergy_state_from_checkpoint(checkpoint)
+        if syn_sd is not None:
+            self.load_synergy_state(syn_sd)
+
+    def load_synergy_state(self, sd, prefix=''):
+        """Uploads MLP_for / MLP_rev from a state_dict with the reference's key names (forwardDirection.* / reverseDirection.*;
+        synth.make_synergy_state for synthetic ones).  Calling it again replaces the weights."""
+        from .synth import flatten_synergy
+        flat = flatten_synergy({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in sd.items()}, prefix)
+        assert flat.size == self._lib.syn_synergy_flat_count()
+        abi.check(self._lib.syn_load_synergy(self._h, flat.ctypes.data_as(C.c_void_p), flat.size))
+        self.has_synergy = True
 
     # --- multi-GPU: rank `src` loads, everybody else receives (SURVEY 8e) ---
     def constants_nbytes(self) -> int:
@@ -535,6 +567,67 @@ class SynergyNet(nn.Module):
                                                    out.data_ptr(), ang.data_ptr(), t3d.data_ptr(), self._stream()))
         return out, (ang, t3d)
 
+    # ------------------------------------------------------------------ synergy refinement (MLP_for / MLP_rev)
+    def _need_synergy(self):
+        if self.arch == 'resnet50':
+            raise RuntimeError('the synergy refinement needs the 1280-d pooled feature of mobilenet_v2; arch=resnet50 pools 2048')
+        if not self.has_synergy:
+            raise RuntimeError('synergy weights not loaded: the checkpoint carried no forwardDirection.* / reverseDirection.* keys '
+                               '(load_synergy_state)')
+
+    def _check_faces(self, name, t, shape):
+        t = self._dev_f32(t)
+        if t.dim() != len(shape) + 1 or tuple(t.shape[1:]) != shape:
+            raise RuntimeError(f'{name} must be [B,{",".join(map(str, shape))}], got {tuple(t.shape)}')
+        return t
+
+    def refine_landmarks(self, param, pool, roi=None, transform=True, return_coarse=False):
+        """model_building.py:149-152 on device: Lc = reconstruct_vertex_62(param), Lr = Lc + 0.05 MLP_for(Lc, pool, shape code, expression
+        code) -> [B,3,68] (with `roi` in image space, like landmarks_and_pose).  return_coarse: (Lr, Lc), Lc as landmarks_and_pose gives it."""
+        self._need_synergy()
+        p, po = self._check_faces('param', param, (62,)), self._check_faces('pool', pool, (1280,))
+        B = p.shape[0]
+        if po.shape[0] != B:
+            raise RuntimeError('param and pool must hold the same number of faces')
+        r = self._check_faces('roi', roi, (5,)) if roi is not None else None
+        if r is not None and r.shape[0] != B:
+            raise RuntimeError('roi must be [B,5] (sx,sy,ex,ey,score)')
+        with torch.cuda.device(self.device):
+            out = torch.empty((B, 3, 68), dtype=torch.float32, device=self.device)
+            coarse = torch.empty_like(out) if return_coarse else None
+            abi.check(self._lib.syn_refine_landmarks(self._h, p.data_ptr(), po.data_ptr(), B, int(transform), r.data_ptr() if r is not None else None,
+                                                     coarse.data_ptr() if return_coarse else None, out.data_ptr(), None, self._stream()))
+        return (out, coarse) if return_coarse else out
+
+    def refine_points(self, lmk, pool, param):
+        """Lr = lmk + 0.05 MLP_for(lmk, pool, param[:,12:52], param[:,52:62]) on landmarks the caller supplies (crop space) -> [B,3,68]"""
+        self._need_synergy()
+        l, po, p = self._check_faces('lmk', lmk, (3, 68)), self._check_faces('pool', pool, (1280,)), self._check_faces('param', param, (62,))
+        B = l.shape[0]
+        if po.shape[0] != B or p.shape[0] != B:
+            raise RuntimeError('lmk, pool and param must hold the same number of faces')
+        with torch.cuda.device(self.device):
+            out = torch.empty((B, 3, 68), dtype=torch.float32, device=self.device)
+            abi.check(self._lib.syn_refine_points(self._h, l.data_ptr(), po.data_ptr(), p.data_ptr(), B, out.data_ptr(), None, self._stream()))
+        return out
+
+    def landmarks_to_param(self, lmk):
+        """MLP_rev (model_building.py:153): crop-space landmarks [B,3,68] -> whitened parameters [B,62]"""
+        self._need_synergy()
+        l = self._check_faces('lmk', lmk, (3, 68))
+        with torch.cuda.device(self.device):
+            out = torch.empty((l.shape[0], 62), dtype=torch.float32, device=self.device)
+            abi.check(self._lib.syn_landmarks_to_param(self._h, l.data_ptr(), l.shape[0], out.data_ptr(), self._stream()))
+        return out
+
+    def forward_synergy(self, input):
+        """[B,3,120,120] -> dict(param, lmk, lmk_refined, param_rev): backbone, refinement and the reverse direction of the training
+        graph (model_building.py:144-153), all on device with no host round trip between them; landmarks in crop space."""
+        self._need_synergy()
+        param, pool = self.forward_test(self._dev_f32(input), return_pool=True)
+        lmk_refined, lmk = self.refine_landmarks(param, pool, return_coarse=True)
+        return dict(param=param, lmk=lmk, lmk_refined=lmk_refined, param_rev=self.landmarks_to_param(lmk_refined))
+
     def pose_matrix_batch(self, param):
         """Batched predict_pose(..., ret_mat=True) (utils/inference.py:146-157): [B,3,4] fp32 = [R | t3d] of parse_pose
         (:86-92), the translation column WITHOUT the ROI affine (the reference builds P before rescaling t3d)."""
@@ -697,7 +790,7 @@ class SynergyNet(nn.Module):
             self.face_detector = FaceBoxes(device=self.device)
         return self.face_detector(frame)
 
-    def get_all_outputs_batch(self, frames, rects=None, dense=True, chunk_faces=64):
+    def get_all_outputs_batch(self, frames, rects=None, dense=True, chunk_faces=64, refine=False):
         """get_all_outputs for a LIST of frames: every face of every frame goes through ONE backbone forward, ONE
         reconstruction and ONE download.  frames: uint8 BGR [H,W,3] arrays (sizes may differ); rects: per frame a list of
         detections [xmin,ymin,xmax,ymax,score] (mutated into the ROI like get_all_outputs does), or None -> face_detector(frame).
@@ -707,7 +800,11 @@ class SynergyNet(nn.Module):
         chunk_faces: from 2 x chunk_faces faces on, the frames go through the device in chunks of at least that many faces so that the
         host staging of a chunk overlaps the device work and the downloads of the one before (same results: faces are independent;
         16 full-HD frames x 8 faces: 4.35 -> 3.53 ms per call with two chunks; chunks of 32 / 16 faces: 5.1 / 6.0 ms -- a chunk costs a
-        small-batch forward of its own, ~0.4 ms)."""
+        small-batch forward of its own, ~0.4 ms).
+        refine: pts_res holds the REFINED landmarks (refine_landmarks, image space) instead of the coarse ones; meshes and poses are
+        unchanged.  RuntimeError when the synergy weights were not loaded."""
+        if refine:
+            self._need_synergy()
         from .inference import lanczos4_tables
         import time
         t_start = time.perf_counter()
@@ -769,8 +866,16 @@ class SynergyNet(nn.Module):
                 abi.check(self._lib.syn_crop_resize_frames(self._h, dev_blk.data_ptr(), foff_d.data_ptr(), fdim_d.data_ptr(), fidx_d.data_ptr(),
                                                            box_d.data_ptr(), ofs_d[0].data_ptr(), coef_d[0].data_ptr(), ofs_d[1].data_ptr(),
                                                            coef_d[1].data_ptr(), crops.data_ptr(), m, self._stream()))
-                param = self.forward_crops_u8(crops)
+                if refine:
+                    param, pool = self.forward_crops_u8(crops, return_pool=True)
+                else:
+                    param = self.forward_crops_u8(crops)
                 lmk_d, (ang_d, t3d_d) = self.landmarks_and_pose(param, roi=roi_d, transform=True)
+                if refine:
+                    # the call above stays: it is where the pose comes from (the same bits as without refine).  Its coarse landmarks are
+                    # replaced here; syn_refine_landmarks rebuilds Lc in crop space itself (one more launch of the ~6 us landmark kernel,
+                    # next to ~70 MFLOP per face of MLP work)
+                    lmk_d = self.refine_landmarks(param, pool, roi=roi_d, transform=True)
                 mesh_d = None
                 if dense:
                     # packed rows on the device (the kernel's guarded store path; 0.04 us per face more than pitched rows), so that the
@@ -810,7 +915,7 @@ class SynergyNet(nn.Module):
         self.last_timing = dict(faces=n, host_s=(t_enq - t_start) + (t_end - t_dev), device_wait_s=t_dev - t_enq)
         return out
 
-    def get_all_outputs(self, input, rects=None):
+    def get_all_outputs(self, input, rects=None, refine=False):
         """reference synergy3DMM.py:167-207: BGR uint8 image [H,W,3] -> (list of (3,68) landmarks,
         list of (3,53215) meshes, list of [angles_deg, translation]) with one entry per face.
 
@@ -820,4 +925,4 @@ class SynergyNet(nn.Module):
         reference constructs FaceBoxes here, :170-171)."""
         if rects is None:
             rects = self._detect(input)
-        return self.get_all_outputs_batch([input], [rects])[0]
+        return self.get_all_outputs_batch([input], [rects], refine=refine)[0]

@@ -93,6 +93,55 @@ def make_backbone_state(seed: int = 1234) -> dict:
     return sd
 
 
+# The two point-MLPs (reference backbone_nets/pointnet_backbone.py): (conv name, BatchNorm name, cin, cout) in module order
+SYNERGY_FOR = [('conv1', 'bn1', 3, 64), ('conv2', 'bn2', 64, 64), ('conv3', 'bn3', 64, 64), ('conv4', 'bn4', 64, 128),
+               ('conv5', 'bn5', 128, 1024), ('conv6', 'bn6', 2418, 512), ('conv7', 'bn7', 512, 256), ('conv8', 'bn8', 256, 128),
+               ('conv9', 'bn9', 128, 3)]
+SYNERGY_REV = SYNERGY_FOR[:5] + [('conv6_1', 'bn6_1', 1024, 12), ('conv6_2', 'bn6_2', 1024, 40), ('conv6_3', 'bn6_3', 1024, 10)]
+SYNERGY_PREFIXES = ('forwardDirection.', 'reverseDirection.')       # reference synergy3DMM.py:82-84
+
+
+def synergy_layers():
+    """Ordered (state_dict key, shape) list of MLP_for(68) then MLP_rev(68) -- the order of the modules' own state_dict() without
+    num_batches_tracked: per MLP every conv (weight [out,in,1], bias), then every BatchNorm (weight, bias, running_mean, running_var).
+    This list IS the flat layout of syn_load_synergy (include/synergy_hip.h), as mbv2_layers() is the backbone's."""
+    out = []
+    for prefix, table in zip(SYNERGY_PREFIXES, (SYNERGY_FOR, SYNERGY_REV)):
+        for conv, _, cin, cout in table:
+            out += [(f'{prefix}{conv}.weight', (cout, cin, 1)), (f'{prefix}{conv}.bias', (cout,))]
+        for _, bn, _, cout in table:
+            out += [(f'{prefix}{bn}.{t}', (cout,)) for t in ('weight', 'bias', 'running_mean', 'running_var')]
+    return out
+
+
+def make_synergy_state(seed: int = 8643) -> dict:
+    """state_dict of both point-MLPs (numpy float32, reference key names with the forwardDirection. / reverseDirection. prefixes).
+    He-normal conv weights N(0, 2 / fan_in), bias N(0, 0.1); BatchNorm gamma U(0.5, 1.5), beta N(0, 0.1), running_mean N(0, 0.1),
+    running_var U(0.5, 1.5): about 40 % of MLP_for's residual survives the last ReLU on landmark-scale inputs."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for prefix, table in zip(SYNERGY_PREFIXES, (SYNERGY_FOR, SYNERGY_REV)):
+        for conv, bn, cin, cout in table:
+            sd[f'{prefix}{conv}.weight'] = (rng.standard_normal((cout, cin, 1)) * np.sqrt(2.0 / cin)).astype(np.float32)
+            sd[f'{prefix}{conv}.bias'] = (rng.standard_normal(cout) * 0.1).astype(np.float32)
+            sd[f'{prefix}{bn}.weight'] = rng.uniform(0.5, 1.5, cout).astype(np.float32)
+            sd[f'{prefix}{bn}.bias'] = (rng.standard_normal(cout) * 0.1).astype(np.float32)
+            sd[f'{prefix}{bn}.running_mean'] = (rng.standard_normal(cout) * 0.1).astype(np.float32)
+            sd[f'{prefix}{bn}.running_var'] = rng.uniform(0.5, 1.5, cout).astype(np.float32)
+    return sd
+
+
+def flatten_synergy(sd: dict, prefix: str = '') -> np.ndarray:
+    """The flat float32 array syn_load_synergy / syn_fold_synergy_host take: the tensors of synergy_layers() in order."""
+    parts = []
+    for key, shape in synergy_layers():
+        a = np.asarray(sd[prefix + key], dtype=np.float32)
+        if tuple(a.shape) != shape:
+            raise ValueError(f'{prefix + key}: shape {tuple(a.shape)}, expected {shape}')
+        parts.append(a.reshape(-1))
+    return np.ascontiguousarray(np.concatenate(parts))
+
+
 def resnet50_convs():
     """Ordered conv table of the reference ResNet-50 (backbone_nets/resnet_backbone.py:139-254, Bottleneck :90-136):
     dicts with key (conv weight prefix), bn, cin, cout, k, stride, relu, plus block bookkeeping."""
