@@ -393,9 +393,24 @@ int syn_detector_prior_count(int Hs, int Ws);
  * network, priors, decoding (boxes * (Ws,Hs,Ws,Hs) / scale, :101-104), score > conf_thr, top_k by score (any number of
  * candidates; top_k <= 8192), NMS (cpu_nms.pyx semantics, IoU >= nms_thr suppresses), first keep_top_k rows.
  * dets: device [keep_top_k,5] (x1, y1, x2, y2, score) in original-frame pixels, score-descending; n_dets: HOST int, rows
- * valid (the call synchronises `stream`).  The vis_thres filter (:133-140) is the caller's. */
+ * valid (the call synchronises `stream`).  The vis_thres filter (:133-140) is the caller's.  It is the N = 1 case of
+ * syn_detect_batch's launches plus the download of the count. */
 int syn_detect(syn_handle *h, const uint8_t *frame, int H, int W, int Hs, int Ws, float scale, float conf_thr, float nms_thr,
                int top_k, int keep_top_k, float *dets, int *n_dets, void *stream);
+/* The same detector on N frames of ONE size in the same launches (a frame index on every kernel; the weights are shared): frames
+ * device [N,H,W,3] uint8 BGR, contiguous; H, W, Hs, Ws, scale and the thresholds as above, for all frames.  Per frame the rows are
+ * bit for bit those of the single-frame call on that frame, whatever N and the neighbours are.  dets: device [N,keep_top_k,5];
+ * n_dets: DEVICE int [N], rows valid per frame.  The call only enqueues on `stream` (the candidate counters are reset there by
+ * the call itself) and synchronises nothing; the one exception is a call that needs more scratch than any before it on this
+ * handle, which waits for the device before the workspace is reallocated.  Calls on one handle share that workspace: enqueue
+ * them on one stream (or order the streams).  Refused with nothing enqueued: NULL pointers, N outside
+ * 1..SYN_DETECT_BATCH_MAX_FRAMES, the argument ranges the single-frame call refuses (top_k > 8192 included), weights not loaded, a
+ * batch whose scratch would exceed SYN_DETECT_BATCH_MAX_SCRATCH_BYTES (about 8.2 floats, 33 bytes, per pixel of the
+ * Hs x Ws network input: 25 MB per 720x1080 frame, 0.41 GB for 16 of them, about 40 fit; split larger batches into several calls). */
+#define SYN_DETECT_BATCH_MAX_FRAMES 1024
+#define SYN_DETECT_BATCH_MAX_SCRATCH_BYTES ((size_t)1 << 30)
+int syn_detect_batch(syn_handle *h, const uint8_t *frames, int N, int H, int W, int Hs, int Ws, float scale, float conf_thr,
+                     float nms_thr, int top_k, int keep_top_k, float *dets, int *n_dets, void *stream);
 
 /* calc_nme (benchmark_aflw2000.py:107-139): fit [N,2,68] fitted landmarks in 120x120 crop coordinates, gt [N,3,68] ground truth
  * in image coordinates, roi [N,4] crop boxes (sx, sy, ex, ey) -> nme [N] float32.  All device pointers. */

@@ -16,6 +16,7 @@ from .build import LIB
 
 SYN_ERR_INVALID, SYN_ERR_NOT_LOADED = -1, -3
 SYN_ERR_PARAM_LEN = -4
+SYN_DETECT_BATCH_MAX_FRAMES = 1024          # include/synergy_hip.h: syn_detect_batch refuses a larger N
 _lib = None
 
 
@@ -60,6 +61,8 @@ _SIGS = {
     'syn_detector_prior_count': (C.c_int, [C.c_int, C.c_int]),
     'syn_detect': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
                              C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
+    'syn_detect_batch': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int,
+                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'syn_nme': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     'syn_load_triangles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     'syn_mesh_shade': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

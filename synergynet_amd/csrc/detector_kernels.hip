@@ -4,8 +4,11 @@
 //   decode                   FaceBoxes/utils/box_utils.py:177-196
 //   FaceBoxes.__call__       FaceBoxes/FaceBoxes.py:60-143 (frame down-scaling, mean subtraction, thresholds, top-k, NMS)
 //   cpu_nms                  FaceBoxes/utils/nms/cpu_nms.pyx:17-68
-// The detector runs once per frame (~1.3 GFLOP at 720x1080), not once per face, so its convolutions are plain fp32 VALU
-// direct convolutions over NHWC activations -- no MFMA tiling: the whole network is ~30 short launches.  Channel
+// The detector runs per frame (~1.3 GFLOP at 720x1080), not per face, so its convolutions are plain fp32 VALU
+// direct convolutions over NHWC activations -- no MFMA tiling: the whole network is ~30 short launches.
+// Every kernel takes a frame index from blockIdx.y (syn_detect_batch: N frames of one size per launch; syn_detect: N = 1).  Frame f's
+// activations, logits and candidates live `fstride` floats after frame f-1's in the scratch, its frame / dets / counters at their
+// natural strides; the weights are shared.  The per-thread arithmetic does not see f, so a frame's result does not depend on N.  Channel
 // concatenations (CReLU, Inception, the multibox heads) are free: every kernel writes into a channel window of a wider
 // NHWC buffer.  Everything after the network (priors, decoding, threshold, sort, NMS) stays on the device as well.
 #include "syn_internal.h"
@@ -18,9 +21,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // scale == 1: plain conversion.  Otherwise OpenCV's fixed-point INTER_LINEAR for uint8 (11-bit coefficients, see the
 // oracle's resize_linear_u8; cv2 itself is absent, so that path is restated, not pinned).
 __global__ __launch_bounds__(256) void det_preproc_kernel(const unsigned char *__restrict__ frame, int H, int W, float *__restrict__ out,
-                                                          int Ho, int Wo) {
+                                                          int Ho, int Wo, size_t fstride) {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= Ho * Wo) return;
+    frame += (size_t)blockIdx.y * H * W * 3;
+    out += (size_t)blockIdx.y * fstride;
     const int oy = p / Wo, ox = p % Wo;
     const float mean[3] = {104.f, 117.f, 123.f};
     if (Ho == H && Wo == W) {
@@ -55,10 +60,13 @@ __global__ __launch_bounds__(256) void det_preproc_kernel(const unsigned char *_
 // out: [Ho][Wo][cs_out] channels [co0, co0+Cout) (+ [co0+Cout, co0+2*Cout) for CReLU);  act: 0 none, 1 ReLU, 2 CReLU
 __global__ __launch_bounds__(256) void det_conv_kernel(const float *__restrict__ in, const float *__restrict__ Wt, const float *__restrict__ shift,
                                                        float *__restrict__ out, int Hi, int Wi, int cs_in, int ci0, int Cin, int Ho, int Wo,
-                                                       int cs_out, int co0, int Cout, int Cp, int K, int stride, int pad, int act) {
+                                                       int cs_out, int co0, int Cout, int Cp, int K, int stride, int pad, int act,
+                                                       size_t fstride) {
     const int ncog = Cp >> 2;
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)Ho * Wo * ncog) return;
+    in += (size_t)blockIdx.y * fstride;
+    out += (size_t)blockIdx.y * fstride;
     const int cog = (int)(t % ncog), p = (int)(t / ncog);
     const int oy = p / Wo, ox = p % Wo;
     f32x4 acc = *(const f32x4 *)&shift[4 * cog];
@@ -96,10 +104,12 @@ __global__ __launch_bounds__(256) void det_conv_kernel(const float *__restrict__
 
 // ---- 3x3 pooling, NHWC, C % 4 == 0: max (stride 2, pad 1, -inf padding) or average (stride 1, pad 1, divisor 9) ----
 __global__ __launch_bounds__(256) void det_pool_kernel(const float *__restrict__ in, float *__restrict__ out, int Hi, int Wi, int C, int Ho,
-                                                       int Wo, int stride, int is_max) {
+                                                       int Wo, int stride, int is_max, size_t fstride) {
     const int c4n = C >> 2;
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long)Ho * Wo * c4n) return;
+    in += (size_t)blockIdx.y * fstride;
+    out += (size_t)blockIdx.y * fstride;
     const int c4 = (int)(t % c4n), p = (int)(t / c4n);
     const int oy = p / Wo, ox = p % Wo;
     f32x4 a = is_max ? (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY} : (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -119,13 +129,18 @@ __global__ __launch_bounds__(256) void det_pool_kernel(const float *__restrict__
 }
 
 // ---- priors + softmax + decode + score threshold (prior_box.py:22-48, box_utils.py:189-196, FaceBoxes.py:98-112) ----
-// thread = prior.  Candidates (score > thr) are appended to cand[] = {x1, y1, x2, y2, score, prior index} via an atomic counter.
+// thread = prior.  Candidates (score > thr) are appended to cand[] = {x1, y1, x2, y2, score, prior index} via an atomic counter:
+// frame f's own list through its own counter n_cand[f].
 __global__ __launch_bounds__(256) void det_decode_kernel(const float *__restrict__ loc, const float *__restrict__ conf, int P, int Hn, int Wn,
                                                          int H4, int W4, int H5, int W5, int H6, int W6, float scale, float thr,
                                                          float *__restrict__ cand, int *__restrict__ n_cand, int max_cand,
-                                                         float *__restrict__ boxes_out /*nullable [P,4]*/, float *__restrict__ scores_out) {
+                                                         float *__restrict__ boxes_out /*nullable [P,4]*/, float *__restrict__ scores_out,
+                                                         size_t fstride) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= P) return;
+    const size_t f = blockIdx.y;
+    loc += f * fstride; conf += f * fstride; cand += f * fstride; n_cand += f;
+    if (boxes_out) { boxes_out += f * P * 4; scores_out += f * P; }
     // which source / cell / anchor (anchors per cell: 21 = 16 (32 px, 4x4 dense) + 4 (64 px, 2x2) + 1 (128 px); 1; 1)
     double cx, cy, sk;
     const int n0 = H4 * W4 * 21, n1 = H5 * W5;
@@ -160,15 +175,17 @@ __global__ __launch_bounds__(256) void det_decode_kernel(const float *__restrict
     }
 }
 
-// ---- sort by score (descending; equal scores: lower prior index first) + greedy NMS, one workgroup (FaceBoxes.py:114-127) ----
+// ---- sort by score (descending; equal scores: lower prior index first) + greedy NMS, one workgroup per frame (FaceBoxes.py:114-127) ----
 // keys: [score bits : 32 | ~prior index : 32] sorted descending with an in-LDS bitonic network over kSortN slots.  The reference
 // sorts ALL candidates and keeps the first top_k (FaceBoxes.py:115); when more candidates than the network holds pass the
 // threshold, the top_k largest keys are first selected exactly (8-bit radix select on the unique 64-bit keys, most significant
 // digit first) and only those enter the network -- the same set in the same order as sorting everything.
 constexpr int kSortN = 8192;
 __global__ __launch_bounds__(1024) void det_nms_kernel(const float *__restrict__ cand, const int *__restrict__ n_cand, int max_cand, int top_k,
-                                                       float nms_thr, int keep_top_k, float *__restrict__ dets /*[keep_top_k,5]*/,
-                                                       int *__restrict__ n_out) {
+                                                       float nms_thr, int keep_top_k, float *__restrict__ dets /*[N,keep_top_k,5]*/,
+                                                       int *__restrict__ n_out /*[N]*/, size_t fstride) {
+    cand += (size_t)blockIdx.y * fstride; n_cand += blockIdx.y;
+    dets += (size_t)blockIdx.y * keep_top_k * 5; n_out += blockIdx.y;
     __shared__ unsigned long long key[kSortN];
     __shared__ unsigned slot[kSortN];                  // candidate slot of each key
     __shared__ unsigned char dead[kSortN];
@@ -277,30 +294,33 @@ __global__ __launch_bounds__(1024) void det_nms_kernel(const float *__restrict__
     if (tid == 0) *n_out = n_keep < keep_top_k ? n_keep : keep_top_k;
 }
 
-void launch_det_preproc(const unsigned char *frame, int H, int W, float *out, int Ho, int Wo, hipStream_t s) {
-    det_preproc_kernel<<<(Ho * Wo + 255) / 256, 256, 0, s>>>(frame, H, W, out, Ho, Wo);
+// N frames per launch (grid y); `fstride`: floats between two frames' scratch blocks (all in / out / loc / conf / cand pointers are frame 0's)
+void launch_det_preproc(const unsigned char *frames, int N, int H, int W, float *out, int Ho, int Wo, size_t fstride, hipStream_t s) {
+    det_preproc_kernel<<<dim3((Ho * Wo + 255) / 256, N), 256, 0, s>>>(frames, H, W, out, Ho, Wo, fstride);
 }
-void launch_det_conv(const float *in, const float *Wt, const float *shift, float *out, int Hi, int Wi, int cs_in, int ci0, int Cin, int Ho,
-                     int Wo, int cs_out, int co0, int Cout, int K, int stride, int pad, int act, hipStream_t s) {
+void launch_det_conv(const float *in, const float *Wt, const float *shift, float *out, int N, size_t fstride, int Hi, int Wi, int cs_in, int ci0,
+                     int Cin, int Ho, int Wo, int cs_out, int co0, int Cout, int K, int stride, int pad, int act, hipStream_t s) {
     const int Cp = (Cout + 3) & ~3;
     const long total = (long)Ho * Wo * (Cp >> 2);
-    det_conv_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(in, Wt, shift, out, Hi, Wi, cs_in, ci0, Cin, Ho, Wo, cs_out, co0, Cout, Cp, K,
-                                                                    stride, pad, act);
+    det_conv_kernel<<<dim3((unsigned)((total + 255) / 256), N), 256, 0, s>>>(in, Wt, shift, out, Hi, Wi, cs_in, ci0, Cin, Ho, Wo, cs_out, co0,
+                                                                             Cout, Cp, K, stride, pad, act, fstride);
 }
-void launch_det_pool(const float *in, float *out, int Hi, int Wi, int C, int Ho, int Wo, int stride, int is_max, hipStream_t s) {
+void launch_det_pool(const float *in, float *out, int N, size_t fstride, int Hi, int Wi, int C, int Ho, int Wo, int stride, int is_max,
+                     hipStream_t s) {
     const long total = (long)Ho * Wo * (C >> 2);
-    det_pool_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(in, out, Hi, Wi, C, Ho, Wo, stride, is_max);
+    det_pool_kernel<<<dim3((unsigned)((total + 255) / 256), N), 256, 0, s>>>(in, out, Hi, Wi, C, Ho, Wo, stride, is_max, fstride);
 }
-void launch_det_decode(const float *loc, const float *conf, int P, int Hn, int Wn, int H4, int W4, int H5, int W5, int H6, int W6,
-                       float scale, float thr, float *cand, int *n_cand, int max_cand, float *boxes_out, float *scores_out,
+// n_cand: [N] consecutive counters, reset here on the stream
+void launch_det_decode(const float *loc, const float *conf, int N, size_t fstride, int P, int Hn, int Wn, int H4, int W4, int H5, int W5, int H6,
+                       int W6, float scale, float thr, float *cand, int *n_cand, int max_cand, float *boxes_out, float *scores_out,
                        hipStream_t s) {
-    (void)hipMemsetAsync(n_cand, 0, sizeof(int), s);
-    det_decode_kernel<<<(P + 255) / 256, 256, 0, s>>>(loc, conf, P, Hn, Wn, H4, W4, H5, W5, H6, W6, scale, thr, cand, n_cand, max_cand,
-                                                      boxes_out, scores_out);
+    (void)hipMemsetAsync(n_cand, 0, (size_t)N * sizeof(int), s);
+    det_decode_kernel<<<dim3((P + 255) / 256, N), 256, 0, s>>>(loc, conf, P, Hn, Wn, H4, W4, H5, W5, H6, W6, scale, thr, cand, n_cand, max_cand,
+                                                               boxes_out, scores_out, fstride);
 }
-void launch_det_nms(const float *cand, const int *n_cand, int max_cand, int top_k, float nms_thr, int keep_top_k, float *dets, int *n_out,
-                    hipStream_t s) {
-    det_nms_kernel<<<1, 1024, 0, s>>>(cand, n_cand, max_cand, top_k, nms_thr, keep_top_k, dets, n_out);
+void launch_det_nms(const float *cand, const int *n_cand, int N, size_t fstride, int max_cand, int top_k, float nms_thr, int keep_top_k,
+                    float *dets, int *n_out, hipStream_t s) {
+    det_nms_kernel<<<dim3(1, N), 1024, 0, s>>>(cand, n_cand, max_cand, top_k, nms_thr, keep_top_k, dets, n_out, fstride);
 }
 int det_sort_capacity() { return kSortN; }
 

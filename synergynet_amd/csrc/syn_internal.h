@@ -311,15 +311,18 @@ void launch_texture_fill(const unsigned char *tex /*[T,th,tw,ch]*/, const unsign
 void launch_nme(const float *fit, const float *gt, const float *roi, float *nme, int N, hipStream_t s);
 
 // ---- FaceBoxes detector (detector_kernels.hip) ----
-void launch_det_preproc(const unsigned char *frame, int H, int W, float *out, int Ho, int Wo, hipStream_t s);
-void launch_det_conv(const float *in, const float *Wt, const float *shift, float *out, int Hi, int Wi, int cs_in, int ci0, int Cin, int Ho,
-                     int Wo, int cs_out, int co0, int Cout, int K, int stride, int pad, int act, hipStream_t s);
-void launch_det_pool(const float *in, float *out, int Hi, int Wi, int C, int Ho, int Wo, int stride, int is_max, hipStream_t s);
-void launch_det_decode(const float *loc, const float *conf, int P, int Hn, int Wn, int H4, int W4, int H5, int W5, int H6, int W6,
-                       float scale, float thr, float *cand, int *n_cand, int max_cand, float *boxes_out, float *scores_out,
+// N frames of one size per launch (grid y).  Pointers are frame 0's; frame f's scratch (in / out / loc / conf / cand) lies f * fstride
+// floats further, its frame, dets [keep_top_k,5], boxes_out / scores_out and counters (n_cand[f], n_out[f]) at their natural strides.
+void launch_det_preproc(const unsigned char *frames, int N, int H, int W, float *out, int Ho, int Wo, size_t fstride, hipStream_t s);
+void launch_det_conv(const float *in, const float *Wt, const float *shift, float *out, int N, size_t fstride, int Hi, int Wi, int cs_in, int ci0,
+                     int Cin, int Ho, int Wo, int cs_out, int co0, int Cout, int K, int stride, int pad, int act, hipStream_t s);
+void launch_det_pool(const float *in, float *out, int N, size_t fstride, int Hi, int Wi, int C, int Ho, int Wo, int stride, int is_max,
+                     hipStream_t s);
+void launch_det_decode(const float *loc, const float *conf, int N, size_t fstride, int P, int Hn, int Wn, int H4, int W4, int H5, int W5, int H6,
+                       int W6, float scale, float thr, float *cand, int *n_cand, int max_cand, float *boxes_out, float *scores_out,
                        hipStream_t s);
-void launch_det_nms(const float *cand, const int *n_cand, int max_cand, int top_k, float nms_thr, int keep_top_k, float *dets, int *n_out,
-                    hipStream_t s);
+void launch_det_nms(const float *cand, const int *n_cand, int N, size_t fstride, int max_cand, int top_k, float nms_thr, int keep_top_k,
+                    float *dets, int *n_out, hipStream_t s);
 int det_sort_capacity();
 
 // ---- synergy refinement: MLP_for / MLP_rev (synergy_kernels.hip) ----

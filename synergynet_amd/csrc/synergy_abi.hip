@@ -336,7 +336,7 @@ struct syn_handle {
     SynOffsets syn_off = {};
     float *sws = nullptr;          // Lc | point features | conv6 face rows | conv6 face sums | global feature
     size_t sws_bytes = 0;
-    // FaceBoxes detector: packed weights + per-frame scratch (syn_load_detector / syn_detect)
+    // FaceBoxes detector: packed weights + per-frame scratch (syn_load_detector / syn_detect / syn_detect_batch)
     float *d_det = nullptr;
     void *dws = nullptr;
     size_t dws_bytes = 0;
@@ -2785,14 +2785,16 @@ int syn_load_detector(syn_handle *h, const float *flat, size_t count) {
     return SYN_OK;
 }
 
-// Runs the detector on one uint8 BGR frame (device).  scale: 1 or the down-scaling factor FaceBoxes.__call__ computes
-// (FaceBoxes.py:63-80).  dets [keep_top_k,5] device, n_dets: HOST int (the call synchronises the stream to return it).
-// raw_loc / raw_conf / raw_boxes / raw_scores: optional device outputs of the network / decoder (tests).
-static int run_detect(syn_handle *h, const uint8_t *frame, int H, int W, int Hn, int Wn, float scale, float conf_thr, float nms_thr,
-                      int top_k, int keep_top_k, float *dets, int *n_dets, float *raw_loc, float *raw_conf, float *raw_boxes,
-                      float *raw_scores, hipStream_t s) {
+// Enqueues the detector on N uint8 BGR frames of one size (device, contiguous).  scale: 1 or the down-scaling factor
+// FaceBoxes.__call__ computes (FaceBoxes.py:63-80).  dets [N,keep_top_k,5] device; n_out [N] device, or nullptr for the slot in the
+// workspace that *n_out_ws then points to (syn_detect downloads it).  Nothing synchronises unless the workspace has to grow.
+// raw_loc / raw_conf / raw_boxes / raw_scores: optional device outputs of the network / decoder (tests, N = 1).
+// `who`: the entry point's name for messages;  max_bytes: refuse a larger workspace (0 = no cap).
+static int run_detect(syn_handle *h, const char *who, const uint8_t *frames, int N, int H, int W, int Hn, int Wn, float scale, float conf_thr,
+                      float nms_thr, int top_k, int keep_top_k, float *dets, int *n_out, int **n_out_ws, size_t max_bytes, float *raw_loc,
+                      float *raw_conf, float *raw_boxes, float *raw_scores, hipStream_t s) {
     const DetNet &n = detnet();
-    if (Hn < 1 || Wn < 1) return fail(SYN_ERR_INVALID, "syn_detect: scaled frame %dx%d", Hn, Wn);
+    if (Hn < 1 || Wn < 1) return fail(SYN_ERR_INVALID, "%s: scaled frame %dx%d", who, Hn, Wn);
     const int H1 = cdiv_i(Hn, 4), W1 = cdiv_i(Wn, 4), H2 = cdiv_i(H1, 2), W2 = cdiv_i(W1, 2), H3 = cdiv_i(H2, 2), W3 = cdiv_i(W2, 2);
     const int H4 = cdiv_i(H3, 2), W4 = cdiv_i(W3, 2), H5 = cdiv_i(H4, 2), W5 = cdiv_i(W4, 2), H6 = cdiv_i(H5, 2), W6 = cdiv_i(W5, 2);
     const int P = H4 * W4 * 21 + H5 * W5 + H6 * W6;
@@ -2800,35 +2802,45 @@ static int run_detect(syn_handle *h, const uint8_t *frame, int H, int W, int Hn,
     // the top_k best of them exactly (radix select), which is all FaceBoxes.py:114-116 keeps
     const int max_cand = P;
     if (top_k > syn::det_sort_capacity())
-        return fail(SYN_ERR_INVALID, "syn_detect: top_k=%d exceeds the sorter's %d slots", top_k, syn::det_sort_capacity());
-    // scratch carve (floats)
+        return fail(SYN_ERR_INVALID, "%s: top_k=%d exceeds the sorter's %d slots", who, top_k, syn::det_sort_capacity());
+    // scratch carve (floats): the counters of all frames first, then one block of `fstride` floats per frame
     size_t off = 0;
     auto carve = [&](size_t nfl) { const size_t o = off; off += (nfl + 63) & ~(size_t)63; return o; };
+    const size_t o_cnt = carve((size_t)N), o_nout = carve(64);
+    const size_t head = off;
     const size_t o_img = carve((size_t)Hn * Wn * 3), o_c1 = carve((size_t)H1 * W1 * 48), o_p1 = carve((size_t)H2 * W2 * 48);
     const size_t o_c2 = carve((size_t)H3 * W3 * 128), o_xa = carve((size_t)H4 * W4 * 128), o_xb = carve((size_t)H4 * W4 * 128);
     const size_t o_pool = carve((size_t)H4 * W4 * 128), o_r1 = carve((size_t)H4 * W4 * 24), o_r2 = carve((size_t)H4 * W4 * 24);
     const size_t o_t = carve((size_t)H4 * W4 * 32), o_31 = carve((size_t)H4 * W4 * 128), o_32 = carve((size_t)H5 * W5 * 256);
     const size_t o_41 = carve((size_t)H5 * W5 * 128), o_42 = carve((size_t)H6 * W6 * 256);
-    const size_t o_loc = carve((size_t)P * 4), o_conf = carve((size_t)P * 2), o_cand = carve((size_t)max_cand * 6), o_cnt = carve(64);
-    int rc = ensure_dws(h, off * sizeof(float));
+    const size_t o_loc = carve((size_t)P * 4), o_conf = carve((size_t)P * 2), o_cand = carve((size_t)max_cand * 6);
+    const size_t fstride = off - head;
+    const size_t bytes = (head + fstride * (size_t)N) * sizeof(float);
+    if (max_bytes && bytes > max_bytes)
+        return fail(SYN_ERR_INVALID, "%s: N=%d frames of %dx%d need %zu bytes of scratch, more than the cap of %zu", who, N, Hn, Wn, bytes,
+                    max_bytes);
+    int rc = ensure_dws(h, bytes);
     if (rc) return rc;
     float *B0 = (float *)h->dws;
     const float *Wd = h->d_det;
     size_t li = 0;
     auto conv = [&](const float *in, int Hi, int Wi, int cs_in, int ci0, float *out, int Ho, int Wo, int cs_out, int co0) {
         const DetConv &c = n.convs[li++];
-        syn::launch_det_conv(in, Wd + c.w, Wd + c.shift, out, Hi, Wi, cs_in, ci0, c.cin, Ho, Wo, cs_out, co0, c.cout, c.k, c.stride, c.pad,
-                             c.kind == 0 ? 2 : (c.kind == 1 ? 1 : 0), s);
+        syn::launch_det_conv(in, Wd + c.w, Wd + c.shift, out, N, fstride, Hi, Wi, cs_in, ci0, c.cin, Ho, Wo, cs_out, co0, c.cout, c.k, c.stride,
+                             c.pad, c.kind == 0 ? 2 : (c.kind == 1 ? 1 : 0), s);
     };
-    syn::launch_det_preproc(frame, H, W, B0 + o_img, Hn, Wn, s);
+    auto pool = [&](const float *in, float *out, int Hi, int Wi, int C, int Ho, int Wo, int stride, int is_max) {
+        syn::launch_det_pool(in, out, N, fstride, Hi, Wi, C, Ho, Wo, stride, is_max, s);
+    };
+    syn::launch_det_preproc(frames, N, H, W, B0 + o_img, Hn, Wn, fstride, s);
     conv(B0 + o_img, Hn, Wn, 3, 0, B0 + o_c1, H1, W1, 48, 0);                                   // conv1 (CReLU -> 48)
-    syn::launch_det_pool(B0 + o_c1, B0 + o_p1, H1, W1, 48, H2, W2, 2, 1, s);
+    pool(B0 + o_c1, B0 + o_p1, H1, W1, 48, H2, W2, 2, 1);
     conv(B0 + o_p1, H2, W2, 48, 0, B0 + o_c2, H3, W3, 128, 0);                                  // conv2 (CReLU -> 128)
-    syn::launch_det_pool(B0 + o_c2, B0 + o_xa, H3, W3, 128, H4, W4, 2, 1, s);
+    pool(B0 + o_c2, B0 + o_xa, H3, W3, 128, H4, W4, 2, 1);
     float *x = B0 + o_xa, *y = B0 + o_xb;
     for (int i = 0; i < 3; ++i) {                                                               // Inception: cat[b1, b2, b3, b4]
         conv(x, H4, W4, 128, 0, y, H4, W4, 128, 0);                                             // branch1x1
-        syn::launch_det_pool(x, B0 + o_pool, H4, W4, 128, H4, W4, 1, 0, s);
+        pool(x, B0 + o_pool, H4, W4, 128, H4, W4, 1, 0);
         conv(B0 + o_pool, H4, W4, 128, 0, y, H4, W4, 128, 32);                                  // branch1x1_2(avg_pool)
         conv(x, H4, W4, 128, 0, B0 + o_r1, H4, W4, 24, 0);                                      // branch3x3_reduce
         conv(B0 + o_r1, H4, W4, 24, 0, y, H4, W4, 128, 64);                                     // branch3x3
@@ -2852,15 +2864,30 @@ static int run_detect(syn_handle *h, const uint8_t *frame, int H, int W, int Hn,
         lo += (size_t)sh_[i] * sw_[i] * sa[i] * 4; co += (size_t)sh_[i] * sw_[i] * sa[i] * 2;
     }
     int *cnt = (int *)(B0 + o_cnt);
-    syn::launch_det_decode(loc, conf, P, Hn, Wn, H4, W4, H5, W5, H6, W6, scale, conf_thr, B0 + o_cand, cnt, max_cand, raw_boxes, raw_scores, s);
-    syn::launch_det_nms(B0 + o_cand, cnt, max_cand, top_k, nms_thr, keep_top_k, dets, cnt + 1, s);
+    if (!n_out) n_out = (int *)(B0 + o_nout);
+    if (n_out_ws) *n_out_ws = n_out;
+    syn::launch_det_decode(loc, conf, N, fstride, P, Hn, Wn, H4, W4, H5, W5, H6, W6, scale, conf_thr, B0 + o_cand, cnt, max_cand, raw_boxes,
+                           raw_scores, s);
+    syn::launch_det_nms(B0 + o_cand, cnt, N, fstride, max_cand, top_k, nms_thr, keep_top_k, dets, n_out, s);
     if (raw_loc) HIP_TRY(hipMemcpyAsync(raw_loc, loc, sizeof(float) * 4 * P, hipMemcpyDeviceToDevice, s));
     if (raw_conf) HIP_TRY(hipMemcpyAsync(raw_conf, conf, sizeof(float) * 2 * P, hipMemcpyDeviceToDevice, s));
-    int host_cnt[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(host_cnt, cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+// one frame, count returned to the host: the N = 1 case of the launches above + one 4-byte download and a stream synchronisation
+static int run_detect_one(syn_handle *h, const uint8_t *frame, int H, int W, int Hn, int Wn, float scale, float conf_thr, float nms_thr,
+                          int top_k, int keep_top_k, float *dets, int *n_dets, float *raw_loc, float *raw_conf, float *raw_boxes,
+                          float *raw_scores, hipStream_t s) {
+    int *d_n = nullptr;
+    int rc = run_detect(h, "syn_detect", frame, 1, H, W, Hn, Wn, scale, conf_thr, nms_thr, top_k, keep_top_k, dets, nullptr, &d_n, 0, raw_loc,
+                        raw_conf, raw_boxes, raw_scores, s);
+    if (rc) return rc;
+    int host_cnt = 0;
+    HIP_TRY(hipMemcpyAsync(&host_cnt, d_n, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipGetLastError());
-    *n_dets = host_cnt[1];
+    *n_dets = host_cnt;
     return SYN_OK;
 }
 
@@ -2876,8 +2903,22 @@ int syn_detect(syn_handle *h, const uint8_t *frame, int H, int W, int Hs, int Ws
                     keep_top_k);
     if (!h->d_det) return fail(SYN_ERR_NOT_LOADED, "syn_detect: detector weights not loaded");
     DeviceGuard g(h->device);
-    return run_detect(h, frame, H, W, Hs, Ws, scale, conf_thr, nms_thr, top_k, keep_top_k, dets, n_dets, nullptr, nullptr, nullptr, nullptr,
-                      (hipStream_t)stream);
+    return run_detect_one(h, frame, H, W, Hs, Ws, scale, conf_thr, nms_thr, top_k, keep_top_k, dets, n_dets, nullptr, nullptr, nullptr, nullptr,
+                          (hipStream_t)stream);
+}
+
+int syn_detect_batch(syn_handle *h, const uint8_t *frames, int N, int H, int W, int Hs, int Ws, float scale, float conf_thr, float nms_thr,
+                     int top_k, int keep_top_k, float *dets, int *n_dets, void *stream) {
+    if (!h || !frames || !dets || !n_dets) return fail(SYN_ERR_INVALID, "syn_detect_batch: NULL argument");
+    if (N < 1 || N > SYN_DETECT_BATCH_MAX_FRAMES)
+        return fail(SYN_ERR_INVALID, "syn_detect_batch: N=%d outside 1..%d", N, SYN_DETECT_BATCH_MAX_FRAMES);
+    if (H <= 0 || W <= 0 || Hs <= 0 || Ws <= 0 || Hs > H || Ws > W || !(scale > 0.f) || scale > 1.f || top_k <= 0 || keep_top_k <= 0)
+        return fail(SYN_ERR_INVALID, "syn_detect_batch: H=%d W=%d Hs=%d Ws=%d scale=%g top_k=%d keep_top_k=%d", H, W, Hs, Ws, (double)scale,
+                    top_k, keep_top_k);
+    if (!h->d_det) return fail(SYN_ERR_NOT_LOADED, "syn_detect_batch: detector weights not loaded");
+    DeviceGuard g(h->device);
+    return run_detect(h, "syn_detect_batch", frames, N, H, W, Hs, Ws, scale, conf_thr, nms_thr, top_k, keep_top_k, dets, n_dets, nullptr,
+                      SYN_DETECT_BATCH_MAX_SCRATCH_BYTES, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }
 
 // Test hook, not part of include/synergy_hip.h: network outputs and decoded boxes / scores of every prior.
@@ -2888,7 +2929,7 @@ int syn_debug_detect_raw(syn_handle *h, const uint8_t *frame, int H, int W, int 
     float *dets = nullptr;
     HIP_TRY(hipMalloc((void **)&dets, 750 * 5 * sizeof(float)));
     int nd = 0;
-    int rc = run_detect(h, frame, H, W, Hs, Ws, scale, 0.05f, 0.3f, 5000, 750, dets, &nd, loc, conf, boxes, scores, (hipStream_t)stream);
+    int rc = run_detect_one(h, frame, H, W, Hs, Ws, scale, 0.05f, 0.3f, 5000, 750, dets, &nd, loc, conf, boxes, scores, (hipStream_t)stream);
     (void)hipFree(dets);
     return rc;
 }

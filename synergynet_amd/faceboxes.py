@@ -6,6 +6,10 @@
 
 Everything from the uint8 frame to the NMS result runs in HIP kernels (csrc/detector_kernels.hip) through `syn_detect`; the
 host only computes the down-scaling factor and applies the visualisation threshold, as the reference does in Python.
+
+Not in the reference: a list of frames in one call.  `detect_batch(frames)` / `call_batch(frames)` group the frames by size, upload
+each group with one copy and run it through `syn_detect_batch` (the same kernels with a frame index), with one synchronisation
+for the whole call, or none with `to_host=False`; per frame the rows are bit for bit those of `detect_all` / `__call__`.
 """
 from __future__ import annotations
 
@@ -35,6 +39,24 @@ def flatten_detector(sd) -> np.ndarray:
                       get(name + '.bn.running_var')]
     flat = np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
     return flat
+
+
+def group_by_size(shapes):
+    """shapes: per frame (H, W[, ...]).  -> [((H, W), [positions]), ...]: one entry per distinct size in order of first
+    appearance, the positions of its frames in input order; all positions together are range(len(shapes))."""
+    groups = {}
+    for i, sh in enumerate(shapes):
+        groups.setdefault((int(sh[0]), int(sh[1])), []).append(i)
+    return list(groups.items())
+
+
+def split_detections(rows, counts, thres=vis_thres):
+    """rows [N,K,5] (x1, y1, x2, y2, score), counts [N] valid rows per frame -> per frame the list FaceBoxes.__call__ returns:
+    [[x1, y1, x2, y2, score], ...] of the valid rows with score > thres (FaceBoxes.py:131-141)."""
+    rows, counts = np.asarray(rows), np.asarray(counts)
+    if rows.ndim != 3 or rows.shape[2] != 5 or counts.shape != rows.shape[:1]:
+        raise ValueError('rows must be [N,K,5] and counts [N]')
+    return [[[b[0], b[1], b[2], b[3], b[4]] for b in rows[i, :int(counts[i])] if b[4] > thres] for i in range(rows.shape[0])]
 
 
 class FaceBoxes:
@@ -108,3 +130,80 @@ class FaceBoxes:
     def __call__(self, img_):
         dets = self.detect_all(img_)
         return [[b[0], b[1], b[2], b[3], b[4]] for b in dets if b[4] > vis_thres]      # FaceBoxes.py:131-141
+
+    def _enqueue_batch(self, frames, max_frames):
+        """-> (dets [N,keep_top_k,5] float32, counts [N] int32, row [N]): device buffers written size group after size group, and for
+        input frame i its row in them; enqueued on the current stream, nothing synchronised."""
+        whole = None
+        if isinstance(frames, (np.ndarray, torch.Tensor)):
+            if frames.ndim != 4:
+                raise ValueError('frames must be a list of uint8 [H,W,3] frames or one uint8 [N,H,W,3] block (BGR)')
+            if isinstance(frames, torch.Tensor) and frames.device == self.device:
+                whole = frames                                   # already one block on the device: no copy
+            frames = [frames[i] for i in range(frames.shape[0])]
+        frames = list(frames)
+        if max_frames < 1:
+            raise ValueError('max_frames must be at least 1')
+        for f in frames:
+            ok = (isinstance(f, torch.Tensor) and f.dtype == torch.uint8) or (isinstance(f, np.ndarray) and f.dtype == np.uint8)
+            if not ok or f.ndim != 3 or f.shape[2] != 3:
+                raise ValueError('frame must be uint8 [H,W,3] (BGR)')
+        n = len(frames)
+        dets = torch.empty((n, keep_top_k, 5), dtype=torch.float32, device=self.device)
+        counts = torch.empty((n,), dtype=torch.int32, device=self.device)
+        groups = group_by_size([f.shape for f in frames])
+        row = [0] * n
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            done = 0
+            for (h, w), pos in groups:
+                if whole is not None:
+                    block = whole.contiguous()
+                elif all(isinstance(frames[i], np.ndarray) or not frames[i].is_cuda for i in pos):
+                    block = torch.empty((len(pos), h, w, 3), dtype=torch.uint8, pin_memory=True)      # one page-locked block, one copy
+                    for k, i in enumerate(pos):
+                        block[k].copy_(frames[i] if isinstance(frames[i], torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames[i])))
+                    block = block.to(self.device, non_blocking=True)
+                elif len(pos) == 1 and isinstance(frames[pos[0]], torch.Tensor):
+                    block = frames[pos[0]].to(self.device).contiguous()[None]
+                else:
+                    block = torch.stack([(f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f))).to(self.device)
+                                         for f in (frames[i] for i in pos)])
+                scale = self.frame_scale(h, w)
+                h_s, w_s = self.scaled_size(h, w, scale)
+                for a in range(0, len(pos), max_frames):
+                    m = min(max_frames, len(pos) - a)
+                    abi.check(self._lib.syn_detect_batch(self._h, block[a].data_ptr(), m, h, w, h_s, w_s, float(scale), confidence_threshold,
+                                                         nms_threshold, top_k, keep_top_k, dets[done + a].data_ptr(),
+                                                         counts[done + a:].data_ptr(), stream))
+                for k, i in enumerate(pos):
+                    row[i] = done + k
+                done += len(pos)
+        return dets, counts, row
+
+    def detect_batch(self, frames, to_host=True, max_frames=16):
+        """detect_all for a list of frames: uint8 [H,W,3] BGR numpy arrays or tensors whose sizes may differ, or one [N,H,W,3] block.
+        Frames of one size are stacked into one page-locked block, uploaded with one copy and run through syn_detect_batch in slices of
+        at most `max_frames` (the scratch grows with the slice: about 25 MB per 720x1080 frame).
+        to_host=True: one synchronisation for the whole call; -> per frame, in input order, float32 [n_i,5], the rows detect_all gives.
+        to_host=False: nothing synchronises; -> per frame (dets [keep_top_k,5], count []) device views, valid on the current stream."""
+        dets, counts, row = self._enqueue_batch(frames, max_frames)
+        if not to_host:
+            return [(dets[r], counts[r]) for r in row]
+        rows, cnt = self._download(dets, counts)
+        return [rows[r, :int(cnt[r])].copy() for r in row]
+
+    def _download(self, dets, counts):
+        rows = torch.empty(dets.shape, dtype=torch.float32, pin_memory=True)
+        cnt = torch.empty(counts.shape, dtype=torch.int32, pin_memory=True)
+        with torch.cuda.device(self.device):
+            rows.copy_(dets, non_blocking=True)
+            cnt.copy_(counts, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        return rows.numpy(), cnt.numpy()
+
+    def call_batch(self, frames):
+        """__call__ for a list of frames (see detect_batch): a list, in input order, of the lists __call__ returns."""
+        dets, counts, row = self._enqueue_batch(frames, 16)
+        rows, cnt = self._download(dets, counts)
+        return split_detections(rows[row], cnt[row])

@@ -782,18 +782,30 @@ class SynergyNet(nn.Module):
         coef = c_u[inv].reshape(2, n, 120, 8).astype(np.int16, copy=False)
         return roi, box, ofs, coef
 
-    def _detect(self, frame):
+    def _detector(self):
         if self.face_detector is None:
             # the reference builds FaceBoxes() on every call (:170-171); here once, on first use (HIP kernels,
             # synergynet_amd/faceboxes.py; needs FaceBoxes/weights/FaceBoxesProd.pth or model.face_detector = FaceBoxes(state_dict=...))
             from .faceboxes import FaceBoxes
             self.face_detector = FaceBoxes(device=self.device)
-        return self.face_detector(frame)
+        return self.face_detector
+
+    def _detect(self, frame):
+        return self._detector()(frame)
+
+    def _detect_frames(self, frames):
+        """One detection list per frame: all frames in one call_batch when the detector has it (the HIP FaceBoxes: identical rows), else
+        frame by frame -- a user's own detector is any callable."""
+        det = self._detector()
+        if hasattr(det, 'call_batch'):
+            return det.call_batch(frames)
+        return [det(f) for f in frames]
 
     def get_all_outputs_batch(self, frames, rects=None, dense=True, chunk_faces=64, refine=False):
         """get_all_outputs for a LIST of frames: every face of every frame goes through ONE backbone forward, ONE
         reconstruction and ONE download.  frames: uint8 BGR [H,W,3] arrays (sizes may differ); rects: per frame a list of
-        detections [xmin,ymin,xmax,ymax,score] (mutated into the ROI like get_all_outputs does), or None -> face_detector(frame).
+        detections [xmin,ymin,xmax,ymax,score] (mutated into the ROI like get_all_outputs does), or None -> the face detector: all frames in
+        one `call_batch` when it has that method (the HIP FaceBoxes), else face_detector(frame) per frame.
         Returns a list with one (pts_res, vertices_lst, poses) triple per frame, each exactly what get_all_outputs returns
         (dense=False: vertices_lst is empty -- landmarks + pose only).  The returned arrays of a call are contiguous float32 views
         into page-locked host blocks allocated for this call and owned by the arrays (freed when the last one is dropped).
@@ -810,7 +822,7 @@ class SynergyNet(nn.Module):
         t_start = time.perf_counter()
         frames = list(frames)
         if rects is None:
-            rects = [self._detect(f) for f in frames]
+            rects = self._detect_frames(frames)
         if len(rects) != len(frames):
             raise ValueError('rects must hold one detection list per frame')
         counts = [len(r) for r in rects]
