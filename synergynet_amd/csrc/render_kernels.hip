@@ -15,7 +15,8 @@
 //   * vertex normals are summed per vertex over a CSR list of its incident triangles in ascending triangle order (built
 //     once per topology by the host), which is the order the sequential loop adds them in;
 //   * the z-buffer is a 64-bit atomicMax on  [face index | order-preserving depth bits | ~triangle index] : the sequential
-//     rule "overwrite when strictly deeper" ends at the deepest triangle, earliest index among equals, and a later face
+//     rule "overwrite when strictly deeper" ends at the deepest triangle, earliest index among equals -- +0 and -0 are equal
+//     to the reference's `>`, so the key of a zero depth is taken from +0 whatever its sign -- and a later face
 //     overwrites an earlier one wherever it covers (each face starts from a fresh depth buffer); a second pass re-derives
 //     the barycentric weights of the winning triangle and writes the colour (alpha = 1, the binding's default).
 // Exception: numpy evaluates (v2v*reflection)**5 with glibc powf; the kernel uses an exactly rounded double product, which
@@ -262,6 +263,7 @@ __device__ __forceinline__ unsigned depth_key(float d) {
 }  // namespace
 
 // ---- z-buffer pass 1 (rasterize_kernel.cpp:229-262): one thread per (face, triangle) walks its bounding box ----
+// A zero depth is keyed as +0 (as in tri_depth_kernel): the raw bits would order -0 below +0, which the reference's `>` does not.
 __global__ __launch_bounds__(256) void raster_depth_kernel(const float *__restrict__ vertices, const int *__restrict__ tri,
                                                            unsigned long long *__restrict__ zkey, int nver, int ntri, int h,
                                                            int w, int planar) {
@@ -282,7 +284,7 @@ __global__ __launch_bounds__(256) void raster_depth_kernel(const float *__restri
             if (!b.in) continue;
             const float depth = b.w0 * d0 + b.w1 * d1 + b.w2 * d2;
             if (!(depth > -1e8f)) continue;                       // the fresh depth buffer holds -1e8 (Sim3DR.py:23)
-            atomicMax(&zkey[(size_t)y * w + x], hi | ((unsigned long long)depth_key(depth) << 24) | lo);
+            atomicMax(&zkey[(size_t)y * w + x], hi | ((unsigned long long)depth_key(depth == 0.0f ? 0.0f : depth) << 24) | lo);
         }
 }
 
