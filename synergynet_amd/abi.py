@@ -107,7 +107,10 @@ EXPORTED_SYMBOLS = tuple(_SIGS)          # exactly the symbols include/synergy_h
 _SIGS = dict(_SIGS, syn_debug_feature=(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
              syn_debug_profile_block=(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
              syn_debug_detect_raw=(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 5),
-             syn_debug_poison_workspace=(C.c_int, [C.c_void_p, C.c_int, C.c_int]))
+             syn_debug_poison_workspace=(C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+             syn_debug_det_select_nms=(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
+             syn_debug_det_preproc=(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]))
 
 
 def lib():

@@ -2934,6 +2934,35 @@ int syn_debug_detect_raw(syn_handle *h, const uint8_t *frame, int H, int W, int 
     return rc;
 }
 
+// Test hook, not part of include/synergy_hip.h: det_nms_kernel alone, on candidate lists the caller made.  cand: device
+// [N, max_cand, 6] float32 rows x1, y1, x2, y2, score, prior index (the bit pattern of a uint32), in any order -- the order of the
+// atomic appends;  n_cand: device int [N], may exceed max_cand (clamped, as the decode kernel counts past a full list);
+// dets: device [N, keep_top_k, 5];  n_dets: device int [N].  One launch on `stream`, no weights needed, no scratch.
+int syn_debug_det_select_nms(syn_handle *h, const float *cand, const int *n_cand, int N, int max_cand, int top_k, float nms_thr,
+                             int keep_top_k, float *dets, int *n_dets, void *stream) {
+    if (!h || !cand || !n_cand || !dets || !n_dets) return fail(SYN_ERR_INVALID, "syn_debug_det_select_nms: NULL argument");
+    if (N < 1 || max_cand < 1 || top_k <= 0 || keep_top_k <= 0)
+        return fail(SYN_ERR_INVALID, "syn_debug_det_select_nms: N=%d max_cand=%d top_k=%d keep_top_k=%d", N, max_cand, top_k, keep_top_k);
+    if (top_k > syn::det_sort_capacity())
+        return fail(SYN_ERR_INVALID, "syn_debug_det_select_nms: top_k=%d exceeds the sorter's %d slots", top_k, syn::det_sort_capacity());
+    DeviceGuard g(h->device);
+    syn::launch_det_nms(cand, n_cand, N, (size_t)max_cand * 6, max_cand, top_k, nms_thr, keep_top_k, dets, n_dets, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+// Test hook, not part of include/synergy_hip.h: det_preproc_kernel alone.  frames: device uint8 [N,H,W,3] -> out: device float32
+// [N,Hs,Ws,3] (Hs <= H, Ws <= W).
+int syn_debug_det_preproc(syn_handle *h, const uint8_t *frames, int N, int H, int W, int Hs, int Ws, float *out, void *stream) {
+    if (!h || !frames || !out) return fail(SYN_ERR_INVALID, "syn_debug_det_preproc: NULL argument");
+    if (N < 1 || H <= 0 || W <= 0 || Hs <= 0 || Ws <= 0 || Hs > H || Ws > W)
+        return fail(SYN_ERR_INVALID, "syn_debug_det_preproc: N=%d H=%d W=%d Hs=%d Ws=%d", N, H, W, Hs, Ws);
+    DeviceGuard g(h->device);
+    syn::launch_det_preproc(frames, N, H, W, out, Hs, Ws, (size_t)Hs * Ws * 3, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 int syn_nme(syn_handle *h, const float *fit, const float *gt, const float *roi, float *nme, int N, void *stream) {
     if (!h || !fit || !gt || !roi || !nme) return fail(SYN_ERR_INVALID, "syn_nme: NULL argument");
     if (N <= 0) return fail(SYN_ERR_INVALID, "syn_nme: N=%d", N);
