@@ -196,6 +196,36 @@ int syn_crop_resize_frames(syn_handle *h, const uint8_t *frames, const long long
                            const int *face_frame, const int *box, const int *xofs, const int16_t *xcoef, const int *yofs,
                            const int16_t *ycoef, uint8_t *out, int B, void *stream);
 
+/* The tables above computed on the device, so that detections never visit the host between the detector and the crop
+ * (synergynet_amd get_all_outputs_frames).  All pointers are device pointers; n == 0 / N == 0 is SYN_OK without a launch; NULL
+ * pointers and negative sizes are SYN_ERR_INVALID with nothing enqueued.
+ *
+ * syn_lanczos4_tables: the tap tables of synergynet_amd/inference.py lanczos4_tables(side, 120) for n crop sides: ofs [n,120],
+ * coef [n,120,8], the same integers as the host function for every side (same rounding points: source position in double rounded
+ * to float32, eight weights in double rounded to float32, float32 sum tap 0 first, 11-bit fixed point).  The sides are the
+ * caller's own numbers, so this call reads them back first (it synchronises `stream`) and refuses a side < 1. */
+int syn_lanczos4_tables(syn_handle *h, const int *sides, int n, int *ofs, int16_t *coef, void *stream);
+
+/* Everything syn_crop_resize_frames and syn_landmarks_pose / syn_reconstruct need per face, from n FLOAT32 detections
+ * dets [n,5] (x1, y1, x2, y2, score) as the detector leaves them: roi [n,5] = the enlarged square box of get_all_outputs
+ * (synergy3DMM.py:178-185: centre +- floor(height * 1.2 / 2)) and the score, in float32 arithmetic like numpy's on float32
+ * detections; box [n,4] = rint(roi[0:4]) (ties to even, utils/inference.py:98); xofs / xcoef and yofs / ycoef = the tables of
+ * syn_lanczos4_tables for the box's width and height.  status [n]: non-zero exactly where the host path raises 'degenerate
+ * detection box' (a non-finite or > 2^30 rounded coordinate, width or height <= 0 or beyond int32); such a face keeps its float roi,
+ * gets box (0,0,1,1) and the taps of side 1 -- the crop kernel runs over it harmlessly -- and no other face is affected.  Only
+ * enqueues on `stream`; the caller reads status with its results. */
+int syn_face_tables(syn_handle *h, const float *dets, int n, float *roi, int *box, int *xofs, int16_t *xcoef, int *yofs,
+                    int16_t *ycoef, int *status, void *stream);
+
+/* The vis_thres filter of FaceBoxes.__call__ (FaceBoxes.py:131-141) over the padded rows of syn_detect_batch: dets [N,K,5],
+ * counts [N] rows valid per frame (clamped to 0..K; rows past the count are never read).  Output frame i reads input row
+ * order[i] (order NULL: i; an index outside 0..N-1 is a frame without faces) -- the way from size groups back to input order.
+ * rows [N*K,5]: the rows with score > thres (strict; NaN is not greater), frame after frame, each frame's in their order;
+ * face_frame [N*K]: the output frame of each; frame_faces [N+1]: faces per output frame, then their total.  Entries of rows /
+ * face_frame past the total are left as they were.  One workgroup; only enqueues on `stream`. */
+int syn_compact_detections(syn_handle *h, const float *dets, const int *counts, const int *order, int N, int K, float thres,
+                           float *rows, int *face_frame, int *frame_faces, void *stream);
+
 /* reconstruct_vertex_62 (synergy3DMM.py:116-149) fused with the ROI affine of
  * _predict_vertices (utils/inference.py:127-138).
  * param [B,param_len] whitened; param_len must be 62 (else SYN_ERR_PARAM_LEN).

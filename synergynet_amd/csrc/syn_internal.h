@@ -173,6 +173,13 @@ void launch_crop_resize(const uint8_t *frame, int H, int W, const int *box, cons
                         const int *yofs, const short *ycoef, uint8_t *out, int B, hipStream_t s,
                         const long long *foff = nullptr, const int *fdim = nullptr, const int *fidx = nullptr);   // foff: faces of several frames (frame + foff[fidx[b]], fdim[2 f] x fdim[2 f + 1])
 
+// ---- detections -> per-face crop tables on the device (face_tables.hip; the arithmetic is face_tables.h) ----
+void launch_lanczos4_tables(const int *sides, int n, int *ofs, short *coef, hipStream_t s);
+void launch_face_tables(const float *dets, int n, float *roi, int *box, int *xofs, short *xcoef, int *yofs, short *ycoef, int *status,
+                        hipStream_t s);
+void launch_compact_detections(const float *dets, const int *counts, const int *order, int N, int K, float thres, float *rows,
+                               int *face_frame, int *frame_faces, hipStream_t s);       // one workgroup
+
 // ---- ResNet-50 variant (resnet_kernels.hip) ----
 // implicit-GEMM conv, NHWC: W [Npad][KH*KW*Cin] (tap-major), act 0 none / 1 ReLU after the optional residual add
 // ResNet-50 activation formats (resnet_kernels.hip "pair format"): inside an fp16 x2 forward every tensor a convolution consumes is stored by

@@ -2320,6 +2320,48 @@ int syn_crop_resize_frames(syn_handle *h, const uint8_t *frames, const long long
     return SYN_OK;
 }
 
+int syn_lanczos4_tables(syn_handle *h, const int *sides, int n, int *ofs, int16_t *coef, void *stream) {
+    if (!h) return fail(SYN_ERR_INVALID, "syn_lanczos4_tables: NULL handle");
+    if (n < 0) return fail(SYN_ERR_INVALID, "syn_lanczos4_tables: n=%d", n);
+    if (n == 0) return SYN_OK;
+    if (!sides || !ofs || !coef) return fail(SYN_ERR_INVALID, "syn_lanczos4_tables: NULL argument");
+    DeviceGuard g(h->device);
+    // the sides are the caller's own numbers (syn_face_tables derives and checks its sides itself): read them back and refuse a side
+    // below 1 before anything is launched
+    std::vector<int> host((size_t)n);
+    HIP_TRY(hipMemcpyAsync(host.data(), sides, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    for (int i = 0; i < n; ++i)
+        if (host[i] < 1) return fail(SYN_ERR_INVALID, "syn_lanczos4_tables: sides[%d]=%d (a crop side is at least 1)", i, host[i]);
+    syn::launch_lanczos4_tables(sides, n, ofs, coef, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+int syn_face_tables(syn_handle *h, const float *dets, int n, float *roi, int *box, int *xofs, int16_t *xcoef, int *yofs, int16_t *ycoef,
+                    int *status, void *stream) {
+    if (!h) return fail(SYN_ERR_INVALID, "syn_face_tables: NULL handle");
+    if (n < 0) return fail(SYN_ERR_INVALID, "syn_face_tables: n=%d", n);
+    if (n == 0) return SYN_OK;
+    if (!dets || !roi || !box || !xofs || !xcoef || !yofs || !ycoef || !status) return fail(SYN_ERR_INVALID, "syn_face_tables: NULL argument");
+    DeviceGuard g(h->device);
+    syn::launch_face_tables(dets, n, roi, box, xofs, xcoef, yofs, ycoef, status, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+int syn_compact_detections(syn_handle *h, const float *dets, const int *counts, const int *order, int N, int K, float thres, float *rows,
+                           int *face_frame, int *frame_faces, void *stream) {
+    if (!h) return fail(SYN_ERR_INVALID, "syn_compact_detections: NULL handle");
+    if (N < 0 || K < 1 || (long long)N * K > 0x7fffffffll) return fail(SYN_ERR_INVALID, "syn_compact_detections: N=%d K=%d", N, K);
+    if (N == 0) return SYN_OK;
+    if (!dets || !counts || !rows || !face_frame || !frame_faces) return fail(SYN_ERR_INVALID, "syn_compact_detections: NULL argument");
+    DeviceGuard g(h->device);
+    syn::launch_compact_detections(dets, counts, order, N, K, thres, rows, face_frame, frame_faces, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 int syn_reconstruct_pitched(syn_handle *h, const float *param, int B, int param_len, int dense, int transform, const float *roi,
                             float *out, int row_pitch, int pad_writable, void *stream) {
     if (!h || !param || !out) return fail(SYN_ERR_INVALID, "syn_reconstruct: NULL argument");

@@ -10,6 +10,8 @@ host only computes the down-scaling factor and applies the visualisation thresho
 Not in the reference: a list of frames in one call.  `detect_batch(frames)` / `call_batch(frames)` group the frames by size, upload
 each group with one copy and run it through `syn_detect_batch` (the same kernels with a frame index), with one synchronisation
 for the whole call, or none with `to_host=False`; per frame the rows are bit for bit those of `detect_all` / `__call__`.
+`detect_faces(frames)` is `call_batch` whose result stays on the device: the rows above vis_thres packed in frame order
+(`syn_compact_detections`), for `SynergyNet.get_all_outputs_frames`.
 """
 from __future__ import annotations
 
@@ -131,9 +133,22 @@ class FaceBoxes:
         dets = self.detect_all(img_)
         return [[b[0], b[1], b[2], b[3], b[4]] for b in dets if b[4] > vis_thres]      # FaceBoxes.py:131-141
 
-    def _enqueue_batch(self, frames, max_frames):
+    def _adjacent_block(self, frames, pos, h, w):
+        """The frames `pos` as ONE [m,h,w,3] view without a copy, when they are contiguous uint8 tensors on this device that lie back to
+        back in one storage (views of a block staged by the caller: get_all_outputs_frames); else None."""
+        fs = [frames[i] for i in pos]
+        if not all(isinstance(f, torch.Tensor) and f.device == self.device and f.is_contiguous() for f in fs):
+            return None
+        base, step = fs[0].data_ptr(), h * w * 3
+        if any(f.untyped_storage().data_ptr() != fs[0].untyped_storage().data_ptr() or f.data_ptr() != base + k * step
+               for k, f in enumerate(fs)):
+            return None
+        return torch.as_strided(fs[0], (len(fs), h, w, 3), (step, w * 3, 3, 1))
+
+    def _enqueue_batch(self, frames, max_frames, in_place=False):
         """-> (dets [N,keep_top_k,5] float32, counts [N] int32, row [N]): device buffers written size group after size group, and for
-        input frame i its row in them; enqueued on the current stream, nothing synchronised."""
+        input frame i its row in them; enqueued on the current stream, nothing synchronised.  in_place (detect_faces): a size group
+        whose frames already lie back to back on the device is used where it lies (_adjacent_block)."""
         whole = None
         if isinstance(frames, (np.ndarray, torch.Tensor)):
             if frames.ndim != 4:
@@ -157,8 +172,11 @@ class FaceBoxes:
             stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             done = 0
             for (h, w), pos in groups:
+                adjacent = self._adjacent_block(frames, pos, h, w) if in_place and whole is None else None
                 if whole is not None:
                     block = whole.contiguous()
+                elif adjacent is not None:
+                    block = adjacent
                 elif all(isinstance(frames[i], np.ndarray) or not frames[i].is_cuda for i in pos):
                     block = torch.empty((len(pos), h, w, 3), dtype=torch.uint8, pin_memory=True)      # one page-locked block, one copy
                     for k, i in enumerate(pos):
@@ -201,6 +219,28 @@ class FaceBoxes:
             cnt.copy_(counts, non_blocking=True)
             torch.cuda.current_stream().synchronize()
         return rows.numpy(), cnt.numpy()
+
+    def detect_faces(self, frames, max_frames=16):
+        """call_batch whose result stays on the device: enqueues like detect_batch(to_host=False), then packs the rows with
+        score > vis_thres in INPUT-frame order (syn_compact_detections; the size-group permutation goes in as its `order`).
+        -> (rows [N * keep_top_k, 5] float32, face_frame [N * keep_top_k] int32, frame_faces [N + 1] int32), device tensors valid on the
+        current stream, nothing synchronised: frame_faces holds the faces per frame and then their total n; rows[:n] are the faces
+        frame after frame as call_batch lists them, face_frame[:n] the frame of each; what lies past n is unspecified.
+        frames: as detect_batch takes them; an [m,H,W,3] block on the device, or device frames that already lie back to back, are used
+        in place."""
+        dets, counts, row = self._enqueue_batch(frames, max_frames, in_place=True)
+        n = dets.shape[0]
+        rows = torch.empty((n * keep_top_k, 5), dtype=torch.float32, device=self.device)
+        face_frame = torch.empty((n * keep_top_k,), dtype=torch.int32, device=self.device)
+        frame_faces = torch.empty((n + 1,), dtype=torch.int32, device=self.device)
+        if n == 0:
+            return rows, face_frame, frame_faces.zero_()
+        with torch.cuda.device(self.device):
+            order = torch.tensor(row, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+            abi.check(self._lib.syn_compact_detections(self._h, dets.data_ptr(), counts.data_ptr(), order.data_ptr(), n, keep_top_k, vis_thres,
+                                                       rows.data_ptr(), face_frame.data_ptr(), frame_faces.data_ptr(),
+                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return rows, face_frame, frame_faces
 
     def call_batch(self, frames):
         """__call__ for a list of frames (see detect_batch): a list, in input order, of the lists __call__ returns."""

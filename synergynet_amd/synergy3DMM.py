@@ -11,6 +11,8 @@ Additions that the reference does not have (all optional):
     reference loops over faces in Python (synergy3DMM.py:177-205);
   * `rects=` on `get_all_outputs`: the FaceBoxes detector is out of scope, so
     detections are passed in or produced by a pluggable `face_detector` callable;
+  * `get_all_outputs_frames`: a list of frames in, faces out, the detections kept on the device between detector and crop
+    (`face_tables`, `lanczos4_tables_device`: the ROI / box / Lanczos tap arithmetic of get_all_outputs as kernels);
   * constants can come from an in-memory pack / state_dict (synthetic assets) and can be
     broadcast from rank 0 over RCCL instead of being loaded on every rank.
 """
@@ -926,6 +928,167 @@ class SynergyNet(nn.Module):
         t_end = time.perf_counter()
         self.last_timing = dict(faces=n, host_s=(t_enq - t_start) + (t_end - t_dev), device_wait_s=t_dev - t_enq)
         return out
+
+    # ------------------------------------------------------------------ detections -> crop tables on the device
+    def lanczos4_tables_device(self, sides):
+        """inference.lanczos4_tables(side, 120) for n crop sides at once, on the device (syn_lanczos4_tables): sides int32 [n] (tensor or
+        array, each >= 1) -> (ofs [n,120] int32, coef [n,120,8] int16) device tensors, the host function's integers.  Reads the sides
+        back to refuse one below 1 (it synchronises); the per-face path, `face_tables`, does not."""
+        s = sides if isinstance(sides, torch.Tensor) else torch.as_tensor(np.asarray(sides))
+        if s.dim() != 1 or s.dtype.is_floating_point:
+            raise RuntimeError('sides must be a vector of integers')
+        s = s.to(device=self.device, dtype=torch.int32).contiguous()
+        n = s.shape[0]
+        with torch.cuda.device(self.device):
+            ofs = torch.empty((n, 120), dtype=torch.int32, device=self.device)
+            coef = torch.empty((n, 120, 8), dtype=torch.int16, device=self.device)
+            abi.check(self._lib.syn_lanczos4_tables(self._h, s.data_ptr(), n, ofs.data_ptr(), coef.data_ptr(), self._stream()))
+        return ofs, coef
+
+    def face_tables(self, dets):
+        """_face_tables on the device for float32 detections [n,5] (x1, y1, x2, y2, score) that are already there (syn_face_tables; a
+        host array is uploaded): -> (roi [n,5] float32, box [n,4] int32, ofs [2,n,120] int32, coef [2,n,120,8] int16 -- x tables then y
+        tables -- status [n] int32), device tensors with the bits _face_tables returns for lists of np.float32 scalars.  status is
+        non-zero where _face_tables raises 'degenerate detection box' (that face gets box (0,0,1,1) and the taps of side 1; the
+        others are unaffected); nothing synchronises, the caller reads status when it reads its results."""
+        d = dets if isinstance(dets, torch.Tensor) else torch.as_tensor(np.asarray(dets))
+        if d.dim() != 2 or d.shape[1] != 5 or d.dtype != torch.float32:
+            raise RuntimeError('dets must be float32 [n,5] (x1, y1, x2, y2, score)')
+        d = d.to(self.device).contiguous()
+        n = d.shape[0]
+        with torch.cuda.device(self.device):
+            roi = torch.empty((n, 5), dtype=torch.float32, device=self.device)
+            box = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+            ofs = torch.empty((2, n, 120), dtype=torch.int32, device=self.device)
+            coef = torch.empty((2, n, 120, 8), dtype=torch.int16, device=self.device)
+            status = torch.empty((n,), dtype=torch.int32, device=self.device)
+            abi.check(self._lib.syn_face_tables(self._h, d.data_ptr(), n, roi.data_ptr(), box.data_ptr(), ofs[0].data_ptr(), coef[0].data_ptr(),
+                                                ofs[1].data_ptr(), coef[1].data_ptr(), status.data_ptr(), self._stream()))
+        return roi, box, ofs, coef, status
+
+    def get_all_outputs_frames(self, frames, dense=True, refine=False, to_host=True):
+        """get_all_outputs_batch(frames) with the detections kept on the device from the detector's last kernel to the crop kernel's
+        first: the frames are staged ONCE, size group after size group, into one page-locked block and go up with one copy; the
+        detector runs on views of that block (`detect_faces`), the only traffic to the host before the results is the N + 1 face
+        counts (one synchronisation, to size the batch), the ROI / box / Lanczos tables are computed there (`face_tables`) and
+        syn_crop_resize_frames crops from the same block.  No chunking (get_all_outputs_batch overlaps staging and downloads from 128
+        faces on; this call does not).
+        to_host=True: exactly the list of (pts_res, vertices_lst, poses) triples get_all_outputs_batch(frames) returns, same bits.
+        to_host=False: a dict of device tensors for the whole call -- lmk [n,3,68], angles [n,3] float64, t3d [n,3], mesh [n,3,n_vert]
+        or None, roi [n,5], face_frame [n] int32 (faces are in frame order) -- and frame_faces, the faces per frame, as a host list.
+        ValueError('degenerate detection box') after the final synchronisation when any face's box is degenerate.
+        A face_detector without `detect_faces` (a user's callable): get_all_outputs_batch does the work (to_host=True only)."""
+        if refine:
+            self._need_synergy()
+        det = self._detector()
+        if not hasattr(det, 'detect_faces'):
+            if not to_host:
+                raise RuntimeError('get_all_outputs_frames(to_host=False) needs a face detector with detect_faces (the HIP FaceBoxes)')
+            return self.get_all_outputs_batch(frames, dense=dense, refine=refine)
+        import time
+        from .faceboxes import group_by_size
+        t_start = time.perf_counter()
+        frames = [np.ascontiguousarray(f) for f in frames]
+        for fr in frames:
+            if fr.dtype != np.uint8 or fr.ndim != 3 or fr.shape[2] != 3:
+                raise RuntimeError('frame must be uint8 [H,W,3]')
+        N = len(frames)
+        empty = lambda: ([], [], [])
+        if N == 0:
+            return [] if to_host else self._frames_result_device(0, dense, [])
+        # ONE page-locked block: the frames, each size group contiguous (one [m,H,W,3] view for the detector), then where each INPUT
+        # frame lies (byte offset, height and width: the crop kernel's frame tables)
+        total = 0
+
+        def place(nbytes):
+            nonlocal total
+            at = total
+            total = (at + nbytes + 255) & ~255
+            return at
+        foff = np.zeros(N, dtype=np.int64)
+        for (h, w), pos in group_by_size([f.shape for f in frames]):
+            at = place(len(pos) * h * w * 3)
+            foff[pos] = at + np.arange(len(pos), dtype=np.int64) * (h * w * 3)
+        fdim = np.array([fr.shape[:2] for fr in frames], dtype=np.int32)
+        t_at = [place(foff.nbytes), place(fdim.nbytes)]
+        with torch.cuda.device(self.device):
+            stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            sv = stage.numpy()
+            for at, fr in zip(foff, frames):
+                sv[at:at + fr.nbytes] = fr.reshape(-1)
+            for at, a in zip(t_at, (foff, fdim)):
+                sv[at:at + a.nbytes] = a.reshape(-1).view(np.uint8)
+            dev_blk = stage.to(self.device, non_blocking=True)
+            foff_d = dev_blk[t_at[0]:t_at[0] + foff.nbytes].view(torch.int64)
+            fdim_d = dev_blk[t_at[1]:t_at[1] + fdim.nbytes].view(torch.int32)
+            views = [dev_blk[at:at + fr.nbytes].view(fr.shape) for at, fr in zip(foff.tolist(), frames)]
+            rows, face_frame, frame_faces = det.detect_faces(views)
+            ff_h = torch.empty((N + 1,), dtype=torch.int32, pin_memory=True)
+            ff_h.copy_(frame_faces, non_blocking=True)
+            s_c = torch.cuda.current_stream(self.device)
+            t_enq0 = time.perf_counter()
+            s_c.synchronize()
+            t_dev0 = time.perf_counter()
+            counts = ff_h[:N].tolist()
+            n = int(ff_h[N])
+            if n == 0:
+                self.last_timing = dict(faces=0, host_s=(t_enq0 - t_start) + (time.perf_counter() - t_dev0), device_wait_s=t_dev0 - t_enq0)
+                return [empty() for _ in frames] if to_host else self._frames_result_device(N, dense, counts)
+            face_frame = face_frame[:n]
+            roi_d, box_d, ofs_d, coef_d, status_d = self.face_tables(rows[:n])
+            crops = torch.empty((n, 120, 120, 3), dtype=torch.uint8, device=self.device)
+            abi.check(self._lib.syn_crop_resize_frames(self._h, dev_blk.data_ptr(), foff_d.data_ptr(), fdim_d.data_ptr(), face_frame.data_ptr(),
+                                                       box_d.data_ptr(), ofs_d[0].data_ptr(), coef_d[0].data_ptr(), ofs_d[1].data_ptr(),
+                                                       coef_d[1].data_ptr(), crops.data_ptr(), n, self._stream()))
+            if refine:
+                param, pool = self.forward_crops_u8(crops, return_pool=True)
+            else:
+                param = self.forward_crops_u8(crops)
+            lmk_d, (ang_d, t3d_d) = self.landmarks_and_pose(param, roi=roi_d, transform=True)
+            if refine:          # as in get_all_outputs_batch: the pose comes from the call above, the landmarks are replaced
+                lmk_d = self.refine_landmarks(param, pool, roi=roi_d, transform=True)
+            mesh_d = None
+            if dense:
+                mesh_d = torch.empty((n, 3, self._n_vert), dtype=torch.float32, device=self.device)
+                self.reconstruct(param, roi=roi_d, dense=True, transform=True, out=mesh_d)
+            host = lambda t: torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            status_h = host(status_d)
+            status_h.copy_(status_d, non_blocking=True)
+            if to_host:
+                lmk_h, ang_h, t3d_h = host(lmk_d), host(ang_d), host(t3d_d)
+                mesh_h = host(mesh_d) if dense else None
+                lmk_h.copy_(lmk_d, non_blocking=True)
+                ang_h.copy_(ang_d, non_blocking=True)
+                t3d_h.copy_(t3d_d, non_blocking=True)
+                if dense:
+                    mesh_h.copy_(mesh_d, non_blocking=True)
+            t_enq = time.perf_counter()
+            s_c.synchronize()
+            t_dev = time.perf_counter()
+        if status_h.numpy().any():
+            raise ValueError('degenerate detection box')
+        if to_host:
+            lmk, ang, t3d = lmk_h.numpy(), ang_h.numpy().tolist(), t3d_h.numpy()
+            mesh = mesh_h.numpy() if dense else None
+            out, k = [], 0
+            for c in counts:
+                pts_res = [lmk[i] for i in range(k, k + c)]
+                vertices_lst = [mesh[i] for i in range(k, k + c)] if dense else []
+                poses = [[ang[i], t3d[i]] for i in range(k, k + c)]
+                out.append((pts_res, vertices_lst, poses))
+                k += c
+        else:
+            out = dict(lmk=lmk_d, angles=ang_d, t3d=t3d_d, mesh=mesh_d, roi=roi_d, face_frame=face_frame, frame_faces=counts)
+        t_end = time.perf_counter()
+        self.last_timing = dict(faces=n, host_s=(t_enq0 - t_start) + (t_enq - t_dev0) + (t_end - t_dev),
+                                device_wait_s=(t_dev0 - t_enq0) + (t_dev - t_enq))
+        return out
+
+    def _frames_result_device(self, N, dense, counts):
+        """get_all_outputs_frames(to_host=False) of a call without a face: empty tensors of the right shapes, no launch."""
+        e = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=self.device)
+        return dict(lmk=e((0, 3, self._n_lmk)), angles=e((0, 3), torch.float64), t3d=e((0, 3)), mesh=e((0, 3, self._n_vert)) if dense else None,
+                    roi=e((0, 5)), face_frame=e((0,), torch.int32), frame_faces=list(counts))
 
     def get_all_outputs(self, input, rects=None, refine=False):
         """reference synergy3DMM.py:167-207: BGR uint8 image [H,W,3] -> (list of (3,68) landmarks,
