@@ -119,6 +119,24 @@ size_t syn_resnet50_flat_count(void);
 int syn_load_backbone_resnet50(syn_handle *h, const float *flat, size_t n_floats);
 double syn_resnet50_flops_per_face(void);
 
+/* The MobileNetV1 backbones (reference backbone_nets/mobilenetv1_backbone.py:47-140; `--arch mobilenet_1` of main_train.py, the
+ * default of benchmark_validate.py).  Backbone ids, as in the `arch` word of the constants header:
+ *   0 mobilenet_v2 | 1 resnet50 | 2 mobilenet_1 (width 1.0) | 3 mobilenet_05 (0.5) | 4 mobilenet_2 (2.0)
+ * (widths 0.25 and 0.75 have 8 / 24-channel layers, no multiple of the 16-wide matrix tile, and are not offered).
+ * `flat` = the module's state_dict() order without num_batches_tracked: conv1.weight, bn1.{weight,bias,running_mean,running_var},
+ * then per block dw2_1, dw2_2, dw3_1, dw3_2, dw4_1, dw4_2, dw5_1 .. dw5_6, dw6: conv_dw.weight, bn_dw.*, conv_sep.weight, bn_sep.*,
+ * then fc_ori, fc_shape, fc_exp, fc_tex {weight, bias}.  BatchNorm is folded on the host (eps 1e-5).  After loading,
+ * syn_backbone_forward[_u8] run this network: stem, 13 fused depthwise + pointwise launches, pool + heads, every product exact
+ * fp32 (fp32-input MFMA), so syn_numerics_report has nothing to prove and syn_backbone_range_status / _calibrate return 0.
+ * They return the first 62 of the 102 outputs (ori 12 | shape 40 | exp 10: the reference's own cat order; the texture head is
+ * loaded but never computed); pool = the pooled feature, 1024 x width floats.  SYNERGY_HIP_FUSION / syn_set_schedule(h, .): 2 (default)
+ * the fused launches from 128 faces on and one depthwise + one pointwise launch per block below, where those are the faster ones; 1 the
+ * fused launches at every batch size; 0 the per-layer launches at every batch size (the cross-check schedule).
+ * syn_mobilenet1_flat_count / _flops_per_face return 0 for an id that is not 2, 3 or 4. */
+size_t syn_mobilenet1_flat_count(int arch);
+double syn_mobilenet1_flops_per_face(int arch);
+int syn_load_backbone_mobilenet1(syn_handle *h, int arch, const float *flat, size_t n_floats);
+
 /* ParamsPack (utils/params.py:10-35) + the register_buffer block (synergy3DMM.py:95-105).
  * HOST arrays: w_shp [3*n_vert,40], w_exp [3*n_vert,10], u [3*n_vert] (= u_shp+u_exp),
  * param_mean/param_std [>=62] (first 62 used), keypoints [3*n_lmk] flat indices into the
@@ -154,7 +172,7 @@ int syn_describe_constants(syn_handle *h, void *host_header, size_t bytes);
 /* Device-free twins of the hand-off: neither makes a HIP call, so a loader process (or a test) without a GPU can produce and
  * vet the blob.  syn_pack_constants_host writes, from HOST arrays (same meaning as syn_load_backbone / _resnet50 / syn_load_basis;
  * backbone_flat or the whole basis group may be NULL), exactly the bytes syn_export_constants produces after the same loads;
- * arch 0 = mobilenet_v2, 1 = resnet50.  syn_check_constants_host applies syn_import_constants' acceptance checks (magic, version,
+ * arch 0 = mobilenet_v2, 1 = resnet50, 2 / 3 / 4 = mobilenet_1 / _05 / _2.  syn_check_constants_host applies syn_import_constants' acceptance checks (magic, version,
  * sizes vs this library's network tables, payload within the buffer) to a host copy of a blob. */
 size_t syn_pack_constants_host_bytes(int arch, int have_backbone, int n_vert, int n_lmk);
 int syn_pack_constants_host(int arch, const float *backbone_flat, size_t n_floats, const float *w_shp, const float *w_exp,
@@ -500,7 +518,7 @@ int syn_load_synergy(syn_handle *h, const float *flat, size_t n);
  * must be ordered on one stream, and the FIRST call at a new largest B frees and reallocates it behind a device-wide synchronisation
  * -- it stalls every stream once and must not happen inside a stream capture (run the largest batch once before capturing).
  * SYN_ERR_NOT_LOADED before syn_load_synergy / syn_load_basis; SYN_ERR_INVALID for B <= 0 or NULL pointers or overlapping outputs or
- * a handle whose backbone is resnet50 (its pooled feature is 2048-d: the refinement is unavailable there). */
+ * a handle whose backbone is resnet50 or a MobileNetV1 (their pooled features are not 1280-d: the refinement is unavailable there). */
 int syn_refine_landmarks(syn_handle *h, const float *param /*[B 62] whitened*/, const float *pool /*[B 1280]*/, int B, int transform,
                          const float *roi /*nullable [B 5]*/, float *lmk_coarse /*nullable [B 3 68]*/, float *lmk_refined /*[B 3 68]*/,
                          float *global_feat /*nullable [B 1024]*/, void *stream);

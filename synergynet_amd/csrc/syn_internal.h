@@ -242,6 +242,25 @@ void launch_pool_fc_generic(const float *feat, const float *Wfc, const float *bi
                             int C, int n_out, int out_stride, hipStream_t s, const float *stat = nullptr, int n_stat = 0,
                             unsigned *guard_word = nullptr /* host-mapped word: set to 1 by a forward the range guard poisoned */);
 
+// ---- MobileNetV1 variants (mobilenet1_kernels.hip): mobilenet_1 / _05 / _2, every product exact fp32 ----
+// 3x3 / 2 stem + BN + ReLU: NCHW fp32 or HWC uint8 crops -> NHWC [B,60,60,C0]; w [27][C0] (row ci*9 + ky*3 + kx), C0 = 16 | 32 | 64
+void launch_mb1_stem(const float *img_nchw, const uint8_t *img_hwc_u8, const float *w, const float *scale, const float *shift,
+                     float *out, int C0, int B, hipStream_t s);
+// one block (depthwise 3x3 pad 1 stride 1|2 + BN + ReLU -> pointwise 1x1 + BN + ReLU) in one launch: X [B,Hin,Hin,K] -> Y [B,Hout,Hout,N];
+// Wd [9][K] tap-major, Wp [N][K] row-major; K % 16 == 0, N % 16 == 0
+void launch_mb1_block(const float *X, const float *Wd, const float *d_scale, const float *d_shift, const float *Wp,
+                      const float *p_scale, const float *p_shift, float *Y, int B, int Hin, int Hout, int K, int N, int stride,
+                      hipStream_t s);
+// the default schedule runs the fused launches from this many faces on and the per-layer launches below (synergy_abi.hip run_mobilenet1:
+// the one batch threshold of this backbone; at 32 faces the fused launches were measured slower, at 128 faster -- DESIGN 5.13)
+constexpr int kMb1FusedMinBatch = 128;
+int mb1_block_nt(int N);
+// the same block as two launches (the per-layer cross-check schedule)
+void launch_mb1_depthwise(const float *in, const float *w9xC, const float *scale, const float *shift, float *out, int B, int Hin,
+                          int Hout, int C, int stride, hipStream_t s);
+void launch_mb1_pointwise(const float *A, const float *W, const float *scale, const float *shift, float *C, int M, int K, int N,
+                          hipStream_t s);
+
 // ---- reconstruction -----------------------------------------------------------------
 // basis: pre-packed per 32-vertex tile in MFMA-operand lane order (see recon_kernels.hip):
 //   Bp[tile][coord x|y|z][chunk][lane][4], K = 52: 0..39 shape, 40..49 expression,

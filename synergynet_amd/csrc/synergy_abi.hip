@@ -274,6 +274,70 @@ const ResNet50 &resnet50() {
     return n;
 }
 
+// ---- MobileNetV1 (reference backbone_nets/mobilenetv1_backbone.py:47-140): conv1 + bn1 + ReLU, 13 DepthWiseBlocks (:21-44), average
+// pool, heads ori / shape / exp / tex concatenated in that order (:132-138).  arch ids 2 = mobilenet_1, 3 = mobilenet_05, 4 = mobilenet_2
+// (include/synergy_hip.h); widths 0.25 and 0.75 give 8 / 24 channels, no multiple of the 16-wide MFMA tile, and are not offered.
+constexpr int kArchMb1First = 2, kArchLast = 4;
+bool is_mb1(int arch) { return arch >= kArchMb1First && arch <= kArchLast; }
+const char *arch_name(int arch) {
+    static const char *const names[] = {"mobilenet_v2", "resnet50", "mobilenet_1", "mobilenet_05", "mobilenet_2"};
+    return arch >= 0 && arch <= kArchLast ? names[arch] : "?";
+}
+struct Mb1Block {
+    int cin, cout, stride, hin, hout;
+    size_t src_dw, src_pw;                                     // flat: conv_dw.weight, bn_dw x4, conv_sep.weight, bn_sep x4
+    size_t dst_wd, dst_dscale, dst_dshift, dst_wp, dst_pscale, dst_pshift;      // packed: [9][cin] | [cin] | [cin] | [cout][cin] | [cout] | [cout]
+};
+struct Mb1Net {
+    int c0 = 0, pool = 0;
+    std::vector<Mb1Block> blocks;
+    size_t flat_count = 0, packed_count = 0, src_fc = 0, dst_stem_w = 0, dst_stem_scale = 0, dst_stem_shift = 0, dst_fc_w = 0, dst_fc_b = 0;
+    size_t buf_io = 0, buf_dw = 0;                             // per-face floats: a block's input / output, a depthwise output
+    double flops = 0;
+    explicit Mb1Net(int num, int den) {                        // width = num / den
+        auto ch = [&](int c) { return c * num / den; };        // int(c * width): exact for the three widths
+        static const int tab[13][3] = {{32, 64, 1}, {64, 128, 2}, {128, 128, 1}, {128, 256, 2}, {256, 256, 1}, {256, 512, 2}, {512, 512, 1},
+                                       {512, 512, 1}, {512, 512, 1}, {512, 512, 1}, {512, 512, 1}, {512, 1024, 2}, {1024, 1024, 1}};      // dw2_1 .. dw6 (:66-82)
+        c0 = ch(32); pool = ch(1024);
+        size_t src = 0, dst = 0;
+        src += (size_t)c0 * 27 + 4 * (size_t)c0;
+        dst_stem_w = dst; dst += (size_t)27 * c0;
+        dst_stem_scale = dst; dst += c0;
+        dst_stem_shift = dst; dst += c0;
+        flops = 2.0 * 27 * c0 * 3600;
+        buf_io = (size_t)c0 * 3600;
+        int h = 60;
+        for (const auto &t : tab) {
+            Mb1Block b{};
+            b.cin = ch(t[0]); b.cout = ch(t[1]); b.stride = t[2]; b.hin = h; b.hout = (h + 2 - 3) / b.stride + 1;      // 15 -> 8
+            b.src_dw = src; src += (size_t)b.cin * 9 + 4 * (size_t)b.cin;
+            b.src_pw = src; src += (size_t)b.cout * b.cin + 4 * (size_t)b.cout;
+            b.dst_wd = dst; dst += (size_t)9 * b.cin;
+            b.dst_dscale = dst; dst += b.cin;
+            b.dst_dshift = dst; dst += b.cin;
+            b.dst_wp = dst; dst += (size_t)b.cout * b.cin;
+            b.dst_pscale = dst; dst += b.cout;
+            b.dst_pshift = dst; dst += b.cout;
+            flops += 2.0 * (9.0 * b.cin + (double)b.cin * b.cout) * b.hout * b.hout;
+            const size_t osz = (size_t)b.cout * b.hout * b.hout, dsz = (size_t)b.cin * b.hout * b.hout;
+            buf_io = osz > buf_io ? osz : buf_io;
+            buf_dw = dsz > buf_dw ? dsz : buf_dw;
+            blocks.push_back(b);
+            h = b.hout;
+        }
+        src_fc = src; src += (size_t)102 * pool + 102;
+        flat_count = src;
+        dst_fc_w = dst; dst += (size_t)64 * pool;              // rows 0..61 = ori | shape | exp; the texture head is loaded but never computed
+        dst_fc_b = dst; dst += 64;
+        packed_count = dst;
+        flops += 2.0 * pool * 102;                             // the network's own count (all four heads), as syn_resnet50_flops_per_face
+    }
+};
+const Mb1Net &mb1net(int arch) {
+    static const Mb1Net n1(1, 1), n05(1, 2), n2(2, 1);
+    return arch == 3 ? n05 : (arch == 4 ? n2 : n1);
+}
+
 struct ConstHeader {   // first 256 bytes of an exported constants buffer
     uint64_t magic;
     uint32_t version, has_backbone, has_basis, n_vert, n_lmk, nvp, nlp, arch;
@@ -305,7 +369,7 @@ struct SynOffsets {
 
 struct syn_handle {
     int device = 0;
-    int arch = 0;                  // 0 = mobilenet_v2 (reference default), 1 = resnet50 (BASELINE config 5)
+    int arch = 0;                  // 0 = mobilenet_v2 (reference default), 1 = resnet50 (BASELINE config 5), 2 / 3 / 4 = mobilenet_1 / _05 / _2
     float *d_backbone = nullptr;   // packed_count floats
     float *d_basis = nullptr;      // dense tiles | landmark tiles | mean[64] | std[64]
     size_t basis_floats = 0;
@@ -374,9 +438,12 @@ const unsigned *basis_f16_lmk(const syn_handle *h) { return basis_f16_dense(h) +
 
 size_t ws_floats_per_face() {
     const size_t mb = 2 * net().max_io + 2 * net().max_hidden, rn = 4 * resnet50().buf_big + 2 * resnet50().buf_mid;
-    return mb > rn ? mb : rn;      // one activation workspace serves either backbone
+    const size_t m1 = 2 * mb1net(4).buf_io + mb1net(4).buf_dw;      // the widest MobileNetV1 (equal to rn: the size does not change)
+    const size_t two = mb > rn ? mb : rn;
+    return two > m1 ? two : m1;    // one activation workspace serves every backbone
 }
-size_t backbone_floats(int arch) { return arch == 1 ? resnet50().packed_count : net().packed_count; }
+size_t backbone_floats(int arch) { return is_mb1(arch) ? mb1net(arch).packed_count : (arch == 1 ? resnet50().packed_count : net().packed_count); }
+size_t backbone_flat_floats(int arch) { return is_mb1(arch) ? mb1net(arch).flat_count : (arch == 1 ? resnet50().flat_count : net().flat_count); }
 
 // Both scratch regions only ever grow; growing synchronises the whole device first, so work in flight on another stream
 // (synergynet_amd/streams.py runs the reconstruction of batch i beside the backbone of batch i+1) never loses its buffer.
@@ -898,6 +965,53 @@ int run_resnet50(syn_handle *h, const float *img, const uint8_t *img8, int B, fl
     return SYN_OK;
 }
 
+// MobileNetV1 forward (MobileNet.forward, mobilenetv1_backbone.py:108-140).  Fused: one launch per block, the depthwise output never
+// leaves the CU (mobilenet1_kernels.hip mb1_block_kernel); per-layer: a depthwise and a pointwise launch per block.  Schedule
+// (SYNERGY_HIP_FUSION / syn_set_schedule): 2 (default) fused from kMb1FusedMinBatch faces on, per-layer below, where the fused
+// launches are the slower ones; 1 fused at every batch size; 0 per-layer at every batch size, the cross-check.  Every product is
+// exact fp32 in both, so there is no range verdict and no guard here.
+bool mb1_fused(const syn_handle *h, int B) { return h->fusion == 1 || (h->fusion >= 2 && B >= syn::kMb1FusedMinBatch); }
+// marks / mark_launch (profiling): one event after every launch; launch codes 0 = stem, 1 + 2 i = block i (fused, or its depthwise
+// half), 2 + 2 i = its pointwise half, 27 = pool + heads.
+int run_mobilenet1(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s,
+                   std::vector<hipEvent_t> *marks = nullptr, std::vector<int> *mark_launch = nullptr) {
+    const Mb1Net &n = mb1net(h->arch);
+    int rc = ensure_ws(h, B);
+    if (rc) return rc;
+    float *X = h->ws, *Y = X + (size_t)B * n.buf_io, *D = Y + (size_t)B * n.buf_io;
+    const float *P = h->d_backbone;
+    auto mark = [&](int code) {
+        if (!marks) return;
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, s);
+        marks->push_back(e);
+        mark_launch->push_back(code);
+    };
+    mark(-1);
+    syn::launch_mb1_stem(img, img8, P + n.dst_stem_w, P + n.dst_stem_scale, P + n.dst_stem_shift, X, n.c0, B, s);
+    mark(0);
+    for (size_t bi = 0; bi < n.blocks.size(); ++bi) {
+        const Mb1Block &b = n.blocks[bi];
+        if (mb1_fused(h, B)) {
+            syn::launch_mb1_block(X, P + b.dst_wd, P + b.dst_dscale, P + b.dst_dshift, P + b.dst_wp, P + b.dst_pscale, P + b.dst_pshift, Y, B,
+                                  b.hin, b.hout, b.cin, b.cout, b.stride, s);
+            mark(1 + 2 * (int)bi);
+        } else {
+            syn::launch_mb1_depthwise(X, P + b.dst_wd, P + b.dst_dscale, P + b.dst_dshift, D, B, b.hin, b.hout, b.cin, b.stride, s);
+            mark(1 + 2 * (int)bi);
+            syn::launch_mb1_pointwise(D, P + b.dst_wp, P + b.dst_pscale, P + b.dst_pshift, Y, B * b.hout * b.hout, b.cin, b.cout, s);
+            mark(2 + 2 * (int)bi);
+        }
+        float *t = X; X = Y; Y = t;
+    }
+    // avgpool + heads (:127-138); the SynergyNet wrapper takes [:, :62] = ori | shape | exp, the first 62 rows as packed
+    syn::launch_pool_fc_generic(X, P + n.dst_fc_w, P + n.dst_fc_b, param, pool, B, 16, n.pool, 62, 62, s);
+    mark(27);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 }  // namespace
 
 namespace syn {
@@ -982,7 +1096,10 @@ int syn_destroy(syn_handle *h) {
 size_t syn_backbone_flat_count(void) { return net().flat_count; }
 double syn_backbone_flops_per_face(void) { return net().flops; }
 double syn_pointwise_flops_per_face(void) { return net().pw_flops; }
-int syn_backbone_launch_count(syn_handle *) { return (int)net().layers.size() + 1; }
+int syn_backbone_launch_count(syn_handle *h) {
+    if (h && is_mb1(h->arch)) return h->fusion >= 1 ? 15 : 28;      // stem + 13 blocks (x 2 per-layer) + pool and heads; schedule 2 below kMb1FusedMinBatch faces: 28
+    return (int)net().layers.size() + 1;
+}
 
 // Host-only packing of the MobileNetV2 state (BN folding, MFMA lane order, bf16 x3 split): shared by syn_load_backbone and
 // syn_pack_constants_host, so a blob packed without a device is byte-identical to what a handle exports.
@@ -1554,6 +1671,10 @@ int syn_numerics_report(syn_handle *h, char *buf, size_t n) {
     char line[256];
     int n_fallback = 0;
     if (!h->d_backbone) out = "no backbone loaded\n";
+    else if (is_mb1(h->arch)) {
+        snprintf(line, sizeof line, "%s: every product is exact fp32 (fp32-input MFMA, fp32 depthwise): no fp16 operand, nothing to prove or guard\n", arch_name(h->arch));
+        out = line;
+    }
     else if (h->arch == 1) {
         for (int i = 0; i < 64; ++i) n_fallback += (h->resnet_w_unsafe[i >> 5] >> (i & 31)) & 1u;
         snprintf(line, sizeof line, "resnet50: %d convolution(s) fail the fp16x2 weight criterion -> fp32-MFMA kernel; activations (ReLU) have no static bound: "
@@ -1807,6 +1928,67 @@ int syn_load_backbone_resnet50(syn_handle *h, const float *flat, size_t n_floats
     return SYN_OK;
 }
 
+// ---- MobileNetV1: flat = the module's state_dict order without num_batches_tracked (synergynet_amd.synergy3DMM.mobilenet1_keys) ----
+size_t syn_mobilenet1_flat_count(int arch) { return is_mb1(arch) ? mb1net(arch).flat_count : 0; }
+double syn_mobilenet1_flops_per_face(int arch) { return is_mb1(arch) ? mb1net(arch).flops : 0.0; }
+
+static void pack_backbone_mobilenet1(int arch, const float *flat, std::vector<float> &pk) {
+    const Mb1Net &n = mb1net(arch);
+    pk.assign(n.packed_count, 0.f);
+    // BN folding: y = conv * scale + shift, scale = gamma / sqrt(var + 1e-5), shift = beta - mean * scale
+    auto fold = [&](const float *bn, int c, float *scale, float *shift) {      // bn = weight | bias | running_mean | running_var
+        for (int i = 0; i < c; ++i) {
+            const float sc = bn[i] / sqrtf(bn[3 * c + i] + 1e-5f);
+            scale[i] = sc;
+            shift[i] = bn[c + i] - bn[2 * c + i] * sc;
+        }
+    };
+    {   // conv1.weight [c0][3][3][3] -> [ci*9 + ky*3 + kx][c0]
+        const int c0 = n.c0;
+        for (int co = 0; co < c0; ++co)
+            for (int t = 0; t < 27; ++t) pk[n.dst_stem_w + (size_t)t * c0 + co] = flat[(size_t)co * 27 + t];
+        fold(flat + (size_t)c0 * 27, c0, pk.data() + n.dst_stem_scale, pk.data() + n.dst_stem_shift);
+    }
+    for (const Mb1Block &b : n.blocks) {
+        for (int c = 0; c < b.cin; ++c)                       // conv_dw.weight [cin][1][3][3] -> tap-major [9][cin]
+            for (int t = 0; t < 9; ++t) pk[b.dst_wd + (size_t)t * b.cin + c] = flat[b.src_dw + (size_t)c * 9 + t];
+        fold(flat + b.src_dw + (size_t)b.cin * 9, b.cin, pk.data() + b.dst_dscale, pk.data() + b.dst_dshift);
+        memcpy(pk.data() + b.dst_wp, flat + b.src_pw, sizeof(float) * (size_t)b.cout * b.cin);      // conv_sep.weight [cout][cin]: as the kernels read it
+        fold(flat + b.src_pw + (size_t)b.cout * b.cin, b.cout, pk.data() + b.dst_pscale, pk.data() + b.dst_pshift);
+    }
+    {   // heads: flat order fc_ori, fc_shape, fc_exp, fc_tex = the cat order (:132-138): rows 0..61 as they come; fc_tex is not packed
+        const float *src = flat + n.src_fc;
+        static const int hn[3] = {12, 40, 10};
+        int row = 0;
+        for (int k = 0; k < 3; ++k) {
+            memcpy(pk.data() + n.dst_fc_w + (size_t)row * n.pool, src, sizeof(float) * hn[k] * n.pool);
+            src += (size_t)hn[k] * n.pool;
+            memcpy(pk.data() + n.dst_fc_b + row, src, sizeof(float) * hn[k]);
+            src += hn[k];
+            row += hn[k];
+        }
+    }
+}
+
+int syn_load_backbone_mobilenet1(syn_handle *h, int arch, const float *flat, size_t n_floats) {
+    if (!h || !flat) return fail(SYN_ERR_INVALID, "syn_load_backbone_mobilenet1: NULL argument");
+    if (!is_mb1(arch)) return fail(SYN_ERR_INVALID, "syn_load_backbone_mobilenet1: arch=%d (2 mobilenet_1, 3 mobilenet_05, 4 mobilenet_2)", arch);
+    const Mb1Net &n = mb1net(arch);
+    if (n_floats != n.flat_count)
+        return fail(SYN_ERR_INVALID, "syn_load_backbone_mobilenet1: got %zu floats, %s has %zu", n_floats, arch_name(arch), n.flat_count);
+    std::vector<float> pk;
+    pack_backbone_mobilenet1(arch, flat, pk);
+    DeviceGuard g(h->device);
+    if (h->d_backbone) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->d_backbone)); h->d_backbone = nullptr; }
+    HIP_TRY(hipMalloc((void **)&h->d_backbone, n.packed_count * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->d_backbone, pk.data(), n.packed_count * sizeof(float), hipMemcpyHostToDevice));
+    h->arch = arch;
+    h->ri = RangeInfo{};
+    h->resnet_fp32 = 0; h->range_events = 0; h->guard_armed = 0; if (h->guard_word) { (void)hipDeviceSynchronize(); *(volatile unsigned *)h->guard_word = 0; }
+    h->resnet_w_unsafe[0] = h->resnet_w_unsafe[1] = h->resnet_w_unsafe[2] = 0;
+    return SYN_OK;
+}
+
 static void pack_basis(const float *w_shp, const float *w_exp, const float *u, const float *param_mean, const float *param_std,
                        const int64_t *keypoints, int n_lmk, int n_vert, std::vector<float> &pk) {
     const int nvp = round_up(n_vert, 32), nlp = round_up(n_lmk, 32);
@@ -1868,7 +2050,7 @@ int syn_load_basis(syn_handle *h, const float *w_shp, const float *w_exp, const 
 // arrays, and run the checks syn_import_constants makes on a host copy of a blob.  No HIP call is made: usable on a machine
 // without a GPU (a loader process, or tests/test_dist_cpu.py's gloo ranks).
 size_t syn_pack_constants_host_bytes(int arch, int have_backbone, int n_vert, int n_lmk) {
-    if (arch < 0 || arch > 1) return 0;
+    if (arch < 0 || arch > kArchLast) return 0;
     size_t fl = have_backbone ? backbone_floats(arch) : 0;
     if (n_vert > 0 && n_lmk > 0) fl += basis_float_count(round_up(n_vert, 32), round_up(n_lmk, 32));
     return sizeof(ConstHeader) + fl * sizeof(float);
@@ -1878,9 +2060,9 @@ int syn_pack_constants_host(int arch, const float *backbone_flat, size_t n_float
                             const float *param_mean, const float *param_std, const int64_t *keypoints, int n_lmk, int n_vert,
                             void *host_dst, size_t bytes) {
     if (!host_dst) return fail(SYN_ERR_INVALID, "syn_pack_constants_host: NULL destination");
-    if (arch < 0 || arch > 1) return fail(SYN_ERR_INVALID, "syn_pack_constants_host: arch=%d", arch);
+    if (arch < 0 || arch > kArchLast) return fail(SYN_ERR_INVALID, "syn_pack_constants_host: arch=%d", arch);
     const bool has_bb = backbone_flat != nullptr, has_basis = w_shp != nullptr;
-    if (has_bb && n_floats != (arch == 1 ? resnet50().flat_count : net().flat_count))
+    if (has_bb && n_floats != backbone_flat_floats(arch))
         return fail(SYN_ERR_INVALID, "syn_pack_constants_host: got %zu backbone floats", n_floats);
     if (has_basis) {
         if (!w_exp || !u || !param_mean || !param_std || !keypoints || n_vert <= 0 || n_lmk <= 0)
@@ -1892,7 +2074,11 @@ int syn_pack_constants_host(int arch, const float *backbone_flat, size_t n_float
     const size_t need = syn_pack_constants_host_bytes(arch, has_bb, has_basis ? n_vert : 0, has_basis ? n_lmk : 0);
     if (bytes < need) return fail(SYN_ERR_INVALID, "syn_pack_constants_host: buffer %zu < %zu bytes", bytes, need);
     std::vector<float> bb, bs;
-    if (has_bb) { if (arch == 1) pack_backbone_resnet50(backbone_flat, bb); else pack_backbone_mbv2(backbone_flat, bb); }
+    if (has_bb) {
+        if (is_mb1(arch)) pack_backbone_mobilenet1(arch, backbone_flat, bb);
+        else if (arch == 1) pack_backbone_resnet50(backbone_flat, bb);
+        else pack_backbone_mbv2(backbone_flat, bb);
+    }
     if (has_basis) pack_basis(w_shp, w_exp, u, param_mean, param_std, keypoints, n_lmk, n_vert, bs);
     ConstHeader hd{};
     hd.magic = kMagic; hd.version = kConstVersion;
@@ -1915,7 +2101,7 @@ int check_const_header(const ConstHeader &hd, size_t bytes, const char *who) {
     if (hd.version != kConstVersion) return fail(SYN_ERR_INVALID, "%s: constants blob version %u, this library packs version %u", who, hd.version, kConstVersion);
     if (hd.total_bytes > bytes) return fail(SYN_ERR_INVALID, "%s: header says %llu bytes, buffer has %zu", who,
                                             (unsigned long long)hd.total_bytes, bytes);
-    if (hd.has_backbone && (hd.arch > 1 || hd.backbone_floats != backbone_floats((int)hd.arch)))
+    if (hd.has_backbone && (hd.arch > (uint32_t)kArchLast || hd.backbone_floats != backbone_floats((int)hd.arch)))
         return fail(SYN_ERR_INVALID, "%s: backbone size mismatch", who);
     if (hd.has_basis && (hd.nvp % 32 || hd.nlp % 32 || hd.n_vert == 0 || hd.n_lmk == 0 || hd.n_vert > hd.nvp || hd.n_lmk > hd.nlp ||
                          hd.nvp - hd.n_vert >= 32 || hd.nlp - hd.n_lmk >= 32 || hd.basis_floats != basis_float_count(hd.nvp, hd.nlp)))
@@ -2100,7 +2286,7 @@ int syn_import_constants(syn_handle *h, const void *dev_src, size_t bytes, void 
         if (h->arch == 0) {          // the sender's verdict on its weights rides in the blob
             HIP_TRY(hipMemcpyAsync(&h->ri, d + net().dst_range * sizeof(float), sizeof h->ri, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
-        } else {
+        } else if (h->arch == 1) {
             HIP_TRY(hipMemcpyAsync(h->resnet_w_unsafe, d + resnet50().dst_range * sizeof(float), sizeof h->resnet_w_unsafe, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
@@ -2125,6 +2311,7 @@ int syn_backbone_forward(syn_handle *h, const float *img, int B, float *param, f
     if (B <= 0) return fail(SYN_ERR_INVALID, "syn_backbone_forward: B=%d", B);
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_backbone_forward: backbone weights not loaded");
     DeviceGuard g(h->device);
+    if (is_mb1(h->arch)) return run_mobilenet1(h, img, nullptr, B, param, pool, (hipStream_t)stream);
     if (h->arch == 1) return run_resnet50(h, img, nullptr, B, param, pool, (hipStream_t)stream);
     return run_backbone(h, img, nullptr, B, param, pool, (hipStream_t)stream);
 }
@@ -2134,6 +2321,7 @@ int syn_backbone_forward_u8(syn_handle *h, const uint8_t *img, int B, float *par
     if (B <= 0) return fail(SYN_ERR_INVALID, "syn_backbone_forward_u8: B=%d", B);
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_backbone_forward_u8: backbone weights not loaded");
     DeviceGuard g(h->device);
+    if (is_mb1(h->arch)) return run_mobilenet1(h, nullptr, img, B, param, pool, (hipStream_t)stream);
     if (h->arch == 1) return run_resnet50(h, nullptr, img, B, param, pool, (hipStream_t)stream);
     return run_backbone(h, nullptr, img, B, param, pool, (hipStream_t)stream);
 }
@@ -2148,6 +2336,34 @@ int syn_backbone_profile(syn_handle *h, const uint8_t *img_hwc, int B, int max_l
     HIP_TRY(hipMalloc((void **)&param, (size_t)B * 62 * sizeof(float)));
     std::vector<hipEvent_t> marks;
     std::vector<int> feats;
+    if (is_mb1(h->arch)) {          // launch codes of run_mobilenet1 in feature_of_launch
+        int rc = run_mobilenet1(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats);
+        int count = 0;
+        if (rc == SYN_OK) {
+            HIP_TRY(hipDeviceSynchronize());
+            const Mb1Net &n = mb1net(h->arch);
+            const bool fused = mb1_fused(h, B);
+            for (size_t i = 1; i < marks.size() && count < max_launches; ++i, ++count) {
+                float ms = 0.f;
+                (void)hipEventElapsedTime(&ms, marks[i - 1], marks[i]);
+                const int code = feats[i];
+                double fl;
+                if (code == 0) fl = 2.0 * 27 * n.c0 * 3600;
+                else if (code == 27) fl = 2.0 * n.pool * 62 + 16.0 * n.pool;
+                else {
+                    const Mb1Block &b = n.blocks[(code - 1) / 2];
+                    const double dw = 2.0 * 9 * b.cin * b.hout * b.hout, pw = 2.0 * b.cin * b.cout * b.hout * b.hout;
+                    fl = fused ? dw + pw : ((code & 1) ? dw : pw);
+                }
+                feature_of_launch[count] = code;
+                ms_of_launch[count] = ms;
+                flops_of_launch[count] = fl * B;
+            }
+        }
+        for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+        (void)hipFree(param);
+        return rc == SYN_OK ? count : rc;
+    }
     int rc = run_backbone(h, nullptr, img_hwc, B, param, nullptr, nullptr, -1, nullptr, -1, nullptr, &marks, &feats);
     int count = 0;
     if (rc == SYN_OK) {
@@ -2200,6 +2416,7 @@ int syn_backbone_profile(syn_handle *h, const uint8_t *img_hwc, int B, int max_l
 int syn_debug_profile_block(syn_handle *h, const float *img, int B, int feature, unsigned long long *out8) {
     if (!h || !img || !out8 || B <= 0) return fail(SYN_ERR_INVALID, "syn_debug_profile_block: bad argument");
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_debug_profile_block: backbone weights not loaded");
+    if (is_mb1(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_profile_block: this handle runs %s", arch_name(h->arch));
     DeviceGuard g(h->device);
     unsigned long long *d = nullptr;
     HIP_TRY(hipMalloc((void **)&d, 32 * sizeof(unsigned long long)));
@@ -2220,6 +2437,7 @@ int syn_debug_profile_block(syn_handle *h, const float *img, int B, int feature,
 int syn_debug_feature(syn_handle *h, const float *img, int B, int feature, float *out, void *stream) {
     if (!h || !img || !out || B <= 0 || feature < 0 || feature > 18) return fail(SYN_ERR_INVALID, "syn_debug_feature: bad argument");
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_debug_feature: backbone weights not loaded");
+    if (is_mb1(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_feature: this handle runs %s", arch_name(h->arch));
     DeviceGuard g(h->device);
     return run_backbone(h, img, nullptr, B, nullptr, nullptr, (hipStream_t)stream, feature, out);
 }
@@ -2234,7 +2452,7 @@ int syn_backbone_calibrate(syn_handle *h, const uint8_t *crops_u8, int B, float 
     if (B <= 0 || B > 256) return fail(SYN_ERR_INVALID, "syn_backbone_calibrate: B=%d (1 .. 256 crops)", B);
     if (!(tol > 0.f)) return fail(SYN_ERR_INVALID, "syn_backbone_calibrate: tol=%g", (double)tol);
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_backbone_calibrate: backbone weights not loaded");
-    if (h->arch != 0) return 0;                          // ResNet-50 is guarded at run time (syn_backbone_range_status)
+    if (h->arch != 0) return 0;                          // ResNet-50 is guarded at run time (syn_backbone_range_status); MobileNetV1 is exact fp32
     DeviceGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     const Net &n = net();
@@ -3146,8 +3364,9 @@ syn::SynTrunkW trunk_weights(const syn_handle *h, int which) {
 }
 
 int synergy_ready(const syn_handle *h, const char *who) {
-    if (h->arch == 1)
-        return fail(SYN_ERR_INVALID, "%s: the synergy refinement needs the 1280-d pooled feature of mobilenet_v2; this handle runs resnet50 (2048-d)", who);
+    if (h->arch != 0)
+        return fail(SYN_ERR_INVALID, "%s: the synergy refinement needs the 1280-d pooled feature of mobilenet_v2; this handle runs %s (%d-d)", who,
+                    arch_name(h->arch), is_mb1(h->arch) ? mb1net(h->arch).pool : 2048);
     if (!h->d_syn) return fail(SYN_ERR_NOT_LOADED, "%s: synergy weights not loaded (syn_load_synergy)", who);
     return SYN_OK;
 }

@@ -66,9 +66,9 @@ def pack_constants_host(pack=None, backbone_state=None, arch: str = 'mobilenet_v
 
     from . import abi
     from .params import ParamsPack
-    from .synergy3DMM import flatten_backbone
+    from .synergy3DMM import ARCH_NAMES, flatten_backbone
     lib = abi.lib()
-    a = {'mobilenet_v2': 0, 'resnet50': 1}[arch]
+    a = ARCH_NAMES.index(arch)
     flat = None
     if backbone_state is not None:
         sd = {k: v for k, v in backbone_state.items() if not k.endswith('num_batches_tracked')}

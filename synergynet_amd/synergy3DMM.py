@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from . import abi
 from .params import ParamsPack
-from .synth import HEADS, RESNET_HEADS, mbv2_layers, resnet50_convs
+from .synth import HEADS, MOBILENET1_HEADS, RESNET_HEADS, mbv2_layers, mobilenet1_blocks, resnet50_convs
 
 BACKBONE_PREFIX = 'I2P.backbone.'
 _BASIS_BUFFERS = ('param_mean', 'param_std', 'w_shp', 'u', 'w_exp', 'u_base', 'w_shp_base', 'w_exp_base')
@@ -44,6 +44,10 @@ def parse_param_62(param):
     return p, offset, alpha_shp, alpha_exp
 
 
+# backbone ids of the C ABI (include/synergy_hip.h; the `arch` word of the constants header), by position
+ARCH_NAMES = ('mobilenet_v2', 'resnet50', 'mobilenet_1', 'mobilenet_05', 'mobilenet_2')
+MOBILENET1_WIDTHS = {'mobilenet_1': 1.0, 'mobilenet_05': 0.5, 'mobilenet_2': 2.0}      # the widths whose channel counts are all multiples of 16
+
 _HDR_MAGIC = 0x53594e4833353558          # "SYNH355X" (csrc/synergy_abi.hip ConstHeader)
 _HDR_VERSION = 6                         # kConstVersion: bumped whenever the packed encoding changes
 
@@ -58,7 +62,7 @@ def parse_constants_header(raw: bytes) -> dict:
     magic, version, has_bb, has_basis, n_vert, n_lmk, nvp, nlp, arch, bb_fl, basis_fl, total = struct.unpack_from('<Q8I3Q', raw, 0)
     if magic != _HDR_MAGIC or version != _HDR_VERSION:
         raise ValueError('constants blob: bad magic/version')
-    if has_bb and arch > 1:
+    if has_bb and arch >= len(ARCH_NAMES):
         raise ValueError(f'constants blob: unknown backbone arch {arch}')
     if has_basis and not (0 < n_vert <= nvp and 0 < n_lmk <= nlp and nvp % 32 == 0 and nlp % 32 == 0):
         raise ValueError('constants blob: inconsistent basis sizes')
@@ -101,10 +105,34 @@ def resnet50_keys():
     return out
 
 
+def mobilenet1_keys(width: float = 1.0):
+    """(state_dict key, shape) of every MobileNetV1 tensor in the module's own state_dict() order (num_batches_tracked left out):
+    the order syn_load_backbone_mobilenet1 expects."""
+    bn = ('weight', 'bias', 'running_mean', 'running_var')
+    c0 = int(32 * width)
+    out = [('conv1.weight', (c0, 3, 3, 3))] + [('bn1.' + s, (c0,)) for s in bn]
+    for key, cin, cout, _ in mobilenet1_blocks(width):
+        out.append((key + '.conv_dw.weight', (cin, 1, 3, 3)))
+        out += [(key + '.bn_dw.' + s, (cin,)) for s in bn]
+        out.append((key + '.conv_sep.weight', (cout, cin, 1, 1)))
+        out += [(key + '.bn_sep.' + s, (cout,)) for s in bn]
+    for name, n in MOBILENET1_HEADS:
+        out.append((name + '.weight', (n, int(1024 * width))))
+        out.append((name + '.bias', (n,)))
+    return out
+
+
+def arch_keys(arch: str):
+    """The (key, shape) table of a backbone by name."""
+    if arch in MOBILENET1_WIDTHS:
+        return mobilenet1_keys(MOBILENET1_WIDTHS[arch])
+    return resnet50_keys() if arch == 'resnet50' else backbone_keys()
+
+
 def flatten_backbone(sd: dict, prefix: str = '', arch: str = 'mobilenet_v2') -> np.ndarray:
-    """state_dict -> the flat fp32 host array of syn_load_backbone[_resnet50] (include/synergy_hip.h)."""
+    """state_dict -> the flat fp32 host array of syn_load_backbone[_resnet50 | _mobilenet1] (include/synergy_hip.h)."""
     parts = []
-    for k, shape in (resnet50_keys() if arch == 'resnet50' else backbone_keys()):
+    for k, shape in arch_keys(arch):
         v = sd[prefix + k]
         v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
         if tuple(v.shape) != tuple(shape):
@@ -163,10 +191,11 @@ class SynergyNet(nn.Module):
                  face_detector=None, load_constants=True, arch='mobilenet_v2'):
         """arch: 'mobilenet_v2' (the reference's hard-coded choice, synergy3DMM.py:76) or 'resnet50' (BASELINE
         config 5; the reference's own wrapper cannot run it -- SURVEY F6 -- so the first 62 of ResNet's 102
-        outputs are taken, the adapter a maintainer would add)."""
+        outputs are taken, the adapter a maintainer would add), or the MobileNetV1 family 'mobilenet_1' / 'mobilenet_05' /
+        'mobilenet_2' (main_train.py --arch mobilenet_1; the same [:, :62] adapter, pool_dim = 1024 x width)."""
         super().__init__()
-        if arch not in ('mobilenet_v2', 'resnet50'):
-            raise RuntimeError("Please choose [mobilenet_v2, resnet50]")
+        if arch not in ARCH_NAMES:
+            raise RuntimeError(f"Please choose [{', '.join(ARCH_NAMES)}]")
         self.arch = arch
         if not torch.cuda.is_available():
             raise RuntimeError('synergynet_amd.SynergyNet needs a ROCm GPU (MI355X); there is no CPU path')
@@ -209,7 +238,7 @@ class SynergyNet(nn.Module):
         self._upload_basis()
 
         # --- backbone weights: key tree identical to the reference's I2P.backbone.* ---
-        for k, shape in (resnet50_keys() if arch == 'resnet50' else backbone_keys()):
+        for k, shape in arch_keys(arch):
             _register_by_key(self, BACKBONE_PREFIX + k, torch.zeros(shape, dtype=torch.float32))
         if backbone_state is not None:
             sd = {BACKBONE_PREFIX + k: torch.as_tensor(np.asarray(v)) for k, v in backbone_state.items()
@@ -257,7 +286,11 @@ class SynergyNet(nn.Module):
 
     def _upload_backbone(self):
         flat = flatten_backbone(self.state_dict(), BACKBONE_PREFIX, self.arch)
-        if self.arch == 'resnet50':
+        if self.arch in MOBILENET1_WIDTHS:
+            a = ARCH_NAMES.index(self.arch)
+            assert flat.size == self._lib.syn_mobilenet1_flat_count(a)
+            abi.check(self._lib.syn_load_backbone_mobilenet1(self._h, a, flat.ctypes.data_as(C.c_void_p), flat.size))
+        elif self.arch == 'resnet50':
             assert flat.size == self._lib.syn_resnet50_flat_count()
             abi.check(self._lib.syn_load_backbone_resnet50(self._h, flat.ctypes.data_as(C.c_void_p), flat.size))
         else:
@@ -415,7 +448,7 @@ class SynergyNet(nn.Module):
     def _follow_constants(self, hdr):
         if hdr['has_backbone']:
             # the blob decides which backbone the C handle now runs: follow it, or pool buffers would be sized for the wrong one
-            self.arch = ('mobilenet_v2', 'resnet50')[hdr['arch']]
+            self.arch = ARCH_NAMES[hdr['arch']]
             self._have_backbone = True
             self._range_checked = False
             self._range_events = 0          # the C side starts counting from 0 again on an import (a stale count here hid the next warning)
@@ -427,6 +460,8 @@ class SynergyNet(nn.Module):
     # ------------------------------------------------------------------ helpers
     @property
     def pool_dim(self):
+        if self.arch in MOBILENET1_WIDTHS:
+            return int(1024 * MOBILENET1_WIDTHS[self.arch])
         return 2048 if self.arch == 'resnet50' else 1280
 
     def _stream(self):
@@ -571,8 +606,8 @@ class SynergyNet(nn.Module):
 
     # ------------------------------------------------------------------ synergy refinement (MLP_for / MLP_rev)
     def _need_synergy(self):
-        if self.arch == 'resnet50':
-            raise RuntimeError('the synergy refinement needs the 1280-d pooled feature of mobilenet_v2; arch=resnet50 pools 2048')
+        if self.arch != 'mobilenet_v2':
+            raise RuntimeError(f'the synergy refinement needs the 1280-d pooled feature of mobilenet_v2; arch={self.arch} pools {self.pool_dim}')
         if not self.has_synergy:
             raise RuntimeError('synergy weights not loaded: the checkpoint carried no forwardDirection.* / reverseDirection.* keys '
                                '(load_synergy_state)')

@@ -185,6 +185,46 @@ def make_resnet50_state(seed: int = 2468) -> dict:
     return sd
 
 
+def mobilenet1_blocks(width: float = 1.0):
+    """Ordered (key, cin, cout, stride) of the 13 DepthWiseBlocks of the reference MobileNetV1, dw2_1 .. dw6
+    (backbone_nets/mobilenetv1_backbone.py:66-82), channels int(c * width).  At 120x120 the stem gives 60^2 and the stride-2
+    blocks dw2_2, dw3_2, dw4_2, dw5_6 give 30^2, 15^2, 8^2 (odd input, pad 1) and 4^2."""
+    table = [('dw2_1', 32, 64, 1), ('dw2_2', 64, 128, 2), ('dw3_1', 128, 128, 1), ('dw3_2', 128, 256, 2), ('dw4_1', 256, 256, 1),
+             ('dw4_2', 256, 512, 2)] + [(f'dw5_{i}', 512, 512, 1) for i in range(1, 6)] + [('dw5_6', 512, 1024, 2), ('dw6', 1024, 1024, 1)]
+    return [(k, int(ci * width), int(co * width), s) for k, ci, co, s in table]
+
+
+MOBILENET1_HEADS = [('fc_ori', 12), ('fc_shape', 40), ('fc_exp', 10), ('fc_tex', 40)]      # module order = cat order (:95-98, :132-138)
+
+
+def make_mobilenet1_state(seed: int = 1357, width: float = 1.0) -> dict:
+    """MobileNetV1 state_dict (numpy fp32, reference key names), the recipe of make_resnet50_state: conv weights N(0, 2 / fan_in)
+    (fan_in 27 stem, 9 depthwise, cin pointwise), randomised BN statistics, small heads.  Activations stay below ~11 through all 27
+    layers for widths 0.5, 1 and 2 and 83-88 % of the pooled features are non-zero."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+
+    def conv_bn(conv, bn, shape, fan_in):
+        cout = shape[0]
+        sd[conv + '.weight'] = (rng.standard_normal(shape) * np.sqrt(2.0 / fan_in)).astype(np.float32)
+        sd[bn + '.weight'] = rng.uniform(0.8, 1.2, cout).astype(np.float32)
+        sd[bn + '.bias'] = (rng.standard_normal(cout) * 0.1).astype(np.float32)
+        sd[bn + '.running_mean'] = (rng.standard_normal(cout) * 0.1).astype(np.float32)
+        sd[bn + '.running_var'] = rng.uniform(0.8, 1.25, cout).astype(np.float32)
+        sd[bn + '.num_batches_tracked'] = np.array(1000, dtype=np.int64)
+
+    c0 = int(32 * width)
+    conv_bn('conv1', 'bn1', (c0, 3, 3, 3), 27)
+    for key, cin, cout, _ in mobilenet1_blocks(width):
+        conv_bn(key + '.conv_dw', key + '.bn_dw', (cin, 1, 3, 3), 9)
+        conv_bn(key + '.conv_sep', key + '.bn_sep', (cout, cin, 1, 1), cin)
+    pool = int(1024 * width)
+    for name, n in MOBILENET1_HEADS:
+        sd[name + '.weight'] = (rng.standard_normal((n, pool)) * 0.02).astype(np.float32)
+        sd[name + '.bias'] = (rng.standard_normal(n) * 0.1).astype(np.float32)
+    return sd
+
+
 def _rotation(yaw, pitch, roll):
     cy, sy = np.cos(yaw), np.sin(yaw)
     cp, sp = np.cos(pitch), np.sin(pitch)

@@ -1,0 +1,68 @@
+"""Generate tests/golden/mobilenet1_outputs.npz by running the REAL reference MobileNetV1 modules (authoring container only).
+
+    python tests/golden/make_mobilenet1_golden.py
+
+Follows make_golden.py main_resnet50: the reference's own mobilenet_1() and mobilenet_05() (backbone_nets/mobilenetv1_backbone.py:232-245,
+torch-only, importable as-is) loaded with synth.make_mobilenet1_state(seed, width), run on synth.normalize_crops(synth.make_crops(2, seed)).
+Recorded per width (suffix _1 / _05): out102, pool, the seeds, and the module's state_dict() key names with their shapes."""
+import importlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.abspath(os.path.join(HERE, '..', '..')))
+sys.path.insert(0, os.path.abspath(os.path.join(HERE, '..')))
+
+from synergynet_amd import synth          # noqa: E402
+from oracle import ref_loader             # noqa: E402
+import mobilenet1_cases as mc             # noqa: E402
+
+
+def reference_module(width):
+    sys.path.insert(0, ref_loader.REF_ROOT)
+    try:
+        m = importlib.import_module('backbone_nets.mobilenetv1_backbone')
+    finally:
+        sys.path.remove(ref_loader.REF_ROOT)
+    return {1.0: m.mobilenet_1, 0.5: m.mobilenet_05, 2.0: m.mobilenet_2}[width]().eval()
+
+
+def run_reference(width, seed, x):
+    """(out102, pool, state_dict keys, shapes) of the reference module with the synthetic weights of `seed`."""
+    net = reference_module(width)
+    own = net.state_dict()
+    sd = synth.make_mobilenet1_state(seed, width)
+    net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})      # strict: the key sets are equal
+    feats = {}
+    net.avgpool.register_forward_hook(lambda mod, i, o: feats.__setitem__('pool', o.flatten(1)))
+    with torch.no_grad():
+        out = net(torch.from_numpy(x)).numpy()
+    keys = list(own.keys())
+    shapes = np.zeros((len(keys), 4), dtype=np.int64)
+    ndim = np.zeros(len(keys), dtype=np.int64)
+    for i, k in enumerate(keys):
+        s = tuple(own[k].shape)
+        ndim[i] = len(s)
+        shapes[i, :len(s)] = s
+    return out, feats['pool'].numpy(), np.array(keys), shapes, ndim
+
+
+def main():
+    torch.manual_seed(0)
+    x = synth.normalize_crops(synth.make_crops(2, seed=mc.CROPS_SEED))
+    rec = {'crops_seed': np.array(mc.CROPS_SEED)}
+    for width in (1.0, 0.5):
+        t = mc.TAG[width]
+        out, pool, keys, shapes, ndim = run_reference(width, mc.SEEDS[width], x)
+        rec.update({f'seed_{t}': np.array(mc.SEEDS[width]), f'out102_{t}': out, f'pool_{t}': pool, f'keys_{t}': keys,
+                    f'shapes_{t}': shapes, f'ndim_{t}': ndim})
+        print(f'width {width}: out[0,:4] = {out[0, :4]}, pool non-zero {float((pool != 0).mean()):.2f}')
+    np.savez_compressed(mc.GOLDEN, **rec)
+    print('wrote', mc.GOLDEN, os.path.getsize(mc.GOLDEN), 'bytes')
+
+
+if __name__ == '__main__':
+    main()
