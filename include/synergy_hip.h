@@ -543,6 +543,20 @@ int syn_backbone_launch_count(syn_handle *h);
 int syn_backbone_profile(syn_handle *h, const uint8_t *img_hwc, int B, int max_launches,
                          int *feature_of_launch, float *ms_of_launch, double *flops_of_launch);
 
+/* One layer of the loaded MobileNetV1 (arch 2 / 3 / 4) on activations the caller supplies, through the launches the forward itself uses
+ * (one helper derives the launch arguments for both) -- the hook tests/test_gpu_mobilenet1_layers.py judges every element of every layer with.
+ *   layer 0      stem: in = uint8 HWC [B,120,120,3] when in_u8 is set, fp32 CHW [B,3,120,120] otherwise; out = NHWC [B,60,60,c0].
+ *   layer 1..13  block layer - 1 (dw2_1 .. dw6): in = NHWC fp32 [B,hin,hin,cin], out = [B,hout,hout,cout].  fused = 1: the one-launch block;
+ *                fused = 0: the depthwise and then the pointwise launch, and a non-NULL aux receives the depthwise output [B,hout,hout,cin].
+ *   layer 14     pool + heads: in = [B,4,4,pool], out = [B,62], a non-NULL aux receives the pooled feature [B,pool] (fused is ignored).
+ * n_in / n_out / n_aux are ELEMENT counts of the three buffers (n_aux = 0 when aux is NULL).  Refused with SYN_ERR_INVALID and a message that
+ * names what was expected, before any launch and, for a NULL handle, before a device is touched: a count that differs from what the layer
+ * needs, a handle whose arch is not MobileNetV1, layer outside 0..14, B < 1 or B > 65536, fused other than 0 / 1, aux with fused = 1 on a block (the
+ * depthwise output never leaves the chip there) or on layer 0, in_u8 on a layer other than 0.  Asynchronous on `stream`; all pointers are device
+ * pointers.  c0 = 32 w, pool = 1024 w, block shapes as in DESIGN 5.13 (w = 1, 0.5, 2). */
+int syn_mobilenet1_layer(syn_handle *h, int layer, int fused, const void *in, int in_u8, int B, size_t n_in,
+                         float *out, size_t n_out, float *aux, size_t n_aux, void *stream);
+
 /* The dense reconstruction (transform = 1) into a pitched output with HIP events around its kernels, on the default stream;
  * synchronises.  ms2[0] = per-face prologue, ms2[1] = the contraction + pose epilogue + mesh stores -- the HBM-write-bound kernel
  * of the path (B * 3 * n_vert * 4 bytes).  Arguments as syn_reconstruct_pitched. */

@@ -971,6 +971,45 @@ int run_resnet50(syn_handle *h, const float *img, const uint8_t *img8, int B, fl
 // launches are the slower ones; 1 fused at every batch size; 0 per-layer at every batch size, the cross-check.  Every product is
 // exact fp32 in both, so there is no range verdict and no guard here.
 bool mb1_fused(const syn_handle *h, int B) { return h->fusion == 1 || (h->fusion >= 2 && B >= syn::kMb1FusedMinBatch); }
+// One layer of the forward, the ONLY place the MobileNetV1 launch arguments are derived from Mb1Net / Mb1Block: run_mobilenet1 walks
+// layers 0..14 through it and syn_mobilenet1_layer runs one of them, so the two cannot drift apart.  layer 0 = stem (in8 or in -> out
+// [B,60,60,c0]); 1..13 = block layer - 1 (in -> out; per-layer: the depthwise output goes through aux); 14 = pool + heads (in [B,4,4,pool]
+// -> out = param [B,62], aux = pool, nullable).  mark(code) is called after every launch with the launch codes below.
+template <class Mark>
+void mb1_launch_layer(const Mb1Net &n, const float *P, int layer, bool fused, const float *in, const uint8_t *in8, int B, float *out,
+                      float *aux, hipStream_t s, Mark &&mark) {
+    if (layer == 0) {
+        syn::launch_mb1_stem(in, in8, P + n.dst_stem_w, P + n.dst_stem_scale, P + n.dst_stem_shift, out, n.c0, B, s);
+        mark(0);
+    } else if (layer == 14) {
+        // avgpool + heads (:127-138); the SynergyNet wrapper takes [:, :62] = ori | shape | exp, the first 62 rows as packed
+        syn::launch_pool_fc_generic(in, P + n.dst_fc_w, P + n.dst_fc_b, out, aux, B, 16, n.pool, 62, 62, s);
+        mark(27);
+    } else {
+        const int bi = layer - 1;
+        const Mb1Block &b = n.blocks[bi];
+        if (fused) {
+            syn::launch_mb1_block(in, P + b.dst_wd, P + b.dst_dscale, P + b.dst_dshift, P + b.dst_wp, P + b.dst_pscale, P + b.dst_pshift, out, B,
+                                  b.hin, b.hout, b.cin, b.cout, b.stride, s);
+            mark(1 + 2 * bi);
+        } else {
+            syn::launch_mb1_depthwise(in, P + b.dst_wd, P + b.dst_dscale, P + b.dst_dshift, aux, B, b.hin, b.hout, b.cin, b.stride, s);
+            mark(1 + 2 * bi);
+            syn::launch_mb1_pointwise(aux, P + b.dst_wp, P + b.dst_pscale, P + b.dst_pshift, out, B * b.hout * b.hout, b.cin, b.cout, s);
+            mark(2 + 2 * bi);
+        }
+    }
+}
+// per-face element counts of a layer's input, output and aux (the depthwise output of a block, the pool of layer 14; 0 for the stem)
+void mb1_layer_counts(const Mb1Net &n, int layer, size_t *n_in, size_t *n_out, size_t *n_aux) {
+    if (layer == 0) { *n_in = (size_t)3 * 120 * 120; *n_out = (size_t)3600 * n.c0; *n_aux = 0; }
+    else if (layer == 14) { *n_in = (size_t)16 * n.pool; *n_out = 62; *n_aux = n.pool; }
+    else {
+        const Mb1Block &b = n.blocks[layer - 1];
+        *n_in = (size_t)b.hin * b.hin * b.cin; *n_out = (size_t)b.hout * b.hout * b.cout; *n_aux = (size_t)b.hout * b.hout * b.cin;
+    }
+}
+
 // marks / mark_launch (profiling): one event after every launch; launch codes 0 = stem, 1 + 2 i = block i (fused, or its depthwise
 // half), 2 + 2 i = its pointwise half, 27 = pool + heads.
 int run_mobilenet1(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s,
@@ -989,25 +1028,13 @@ int run_mobilenet1(syn_handle *h, const float *img, const uint8_t *img8, int B, 
         mark_launch->push_back(code);
     };
     mark(-1);
-    syn::launch_mb1_stem(img, img8, P + n.dst_stem_w, P + n.dst_stem_scale, P + n.dst_stem_shift, X, n.c0, B, s);
-    mark(0);
-    for (size_t bi = 0; bi < n.blocks.size(); ++bi) {
-        const Mb1Block &b = n.blocks[bi];
-        if (mb1_fused(h, B)) {
-            syn::launch_mb1_block(X, P + b.dst_wd, P + b.dst_dscale, P + b.dst_dshift, P + b.dst_wp, P + b.dst_pscale, P + b.dst_pshift, Y, B,
-                                  b.hin, b.hout, b.cin, b.cout, b.stride, s);
-            mark(1 + 2 * (int)bi);
-        } else {
-            syn::launch_mb1_depthwise(X, P + b.dst_wd, P + b.dst_dscale, P + b.dst_dshift, D, B, b.hin, b.hout, b.cin, b.stride, s);
-            mark(1 + 2 * (int)bi);
-            syn::launch_mb1_pointwise(D, P + b.dst_wp, P + b.dst_pscale, P + b.dst_pshift, Y, B * b.hout * b.hout, b.cin, b.cout, s);
-            mark(2 + 2 * (int)bi);
-        }
+    const bool fused = mb1_fused(h, B);
+    mb1_launch_layer(n, P, 0, fused, img, img8, B, X, nullptr, s, mark);
+    for (int layer = 1; layer <= 13; ++layer) {
+        mb1_launch_layer(n, P, layer, fused, X, nullptr, B, Y, D, s, mark);
         float *t = X; X = Y; Y = t;
     }
-    // avgpool + heads (:127-138); the SynergyNet wrapper takes [:, :62] = ori | shape | exp, the first 62 rows as packed
-    syn::launch_pool_fc_generic(X, P + n.dst_fc_w, P + n.dst_fc_b, param, pool, B, 16, n.pool, 62, 62, s);
-    mark(27);
+    mb1_launch_layer(n, P, 14, fused, X, nullptr, B, param, pool, s, mark);
     HIP_TRY(hipGetLastError());
     return SYN_OK;
 }
@@ -2407,6 +2434,43 @@ int syn_backbone_profile(syn_handle *h, const uint8_t *img_hwc, int B, int max_l
     for (hipEvent_t e : marks) (void)hipEventDestroy(e);
     (void)hipFree(param);
     return rc == SYN_OK ? count : rc;
+}
+
+// One layer of the loaded MobileNetV1 on caller-supplied activations (include/synergy_hip.h): the launches are those of run_mobilenet1
+// (mb1_launch_layer).  Everything is vetted before a device is touched; a per-layer block without aux keeps its depthwise output in the
+// handle's workspace, where run_mobilenet1 keeps it.
+int syn_mobilenet1_layer(syn_handle *h, int layer, int fused, const void *in, int in_u8, int B, size_t n_in, float *out, size_t n_out,
+                         float *aux, size_t n_aux, void *stream) {
+    if (!h || !in || !out) return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: NULL argument (handle, in and out are required)");
+    if (!is_mb1(h->arch))
+        return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: this handle runs %s, expected mobilenet_1, mobilenet_05 or mobilenet_2", arch_name(h->arch));
+    if (layer < 0 || layer > 14) return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: layer=%d, expected 0 (stem), 1..13 (blocks) or 14 (pool + heads)", layer);
+    if (B < 1 || B > 65536)          // the kernels index pixels (up to 3600 B) and pixel x channel quads in 32-bit integers
+        return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: B=%d, expected 1 <= B <= 65536", B);
+    if (fused != 0 && fused != 1) return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: fused=%d, expected 0 or 1", fused);
+    if (in_u8 && layer != 0) return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: in_u8 is set on layer %d, expected only on layer 0 (the stem)", layer);
+    const bool block = layer >= 1 && layer <= 13;
+    if (aux && layer == 0) return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: aux on layer 0, expected NULL (the stem has no second output)");
+    if (aux && block && fused)
+        return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: aux with fused=1 on layer %d, expected NULL (the fused launch keeps the depthwise output on chip)", layer);
+    const Mb1Net &n = mb1net(h->arch);
+    size_t f_in, f_out, f_aux;
+    mb1_layer_counts(n, layer, &f_in, &f_out, &f_aux);
+    if (n_in != f_in * B || n_out != f_out * B || (aux ? n_aux != f_aux * B : n_aux != 0))
+        return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: layer %d of %s at B=%d expected n_in=%zu n_out=%zu n_aux=%zu, got %zu %zu %zu", layer,
+                    arch_name(h->arch), B, f_in * B, f_out * B, aux ? f_aux * B : (size_t)0, n_in, n_out, n_aux);
+    if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_mobilenet1_layer: backbone weights not loaded");
+    DeviceGuard g(h->device);
+    float *second = aux;
+    if (block && !fused && !aux) {
+        int rc = ensure_ws(h, B);
+        if (rc) return rc;
+        second = h->ws + 2 * (size_t)B * n.buf_io;
+    }
+    mb1_launch_layer(n, h->d_backbone, layer, fused != 0, in_u8 ? nullptr : (const float *)in, in_u8 ? (const uint8_t *)in : nullptr, B, out,
+                     second, (hipStream_t)stream, [](int) {});
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
 }
 
 // Profiling hook, not part of include/synergy_hip.h: runs the backbone with the fused block of

@@ -271,13 +271,21 @@ def stage_real_detector_assets():
     """Copies the reference's trained detector weights (FaceBoxes/weights/FaceBoxesProd.pth, 4 MB) and its sample photographs
     (img/sample_*.jpg) into tests/golden/_assets/ -- data files, not source; the directory is git-ignored so they stay out of
     history, but it is not gpurun-ignored, so the real-data GPU test can run on the GPU box (where /root/reference is absent)."""
+    import filecmp
     import shutil
     if not os.path.isfile(os.path.join(ref_loader.REF_ROOT, 'FaceBoxes', 'weights', 'FaceBoxesProd.pth')):
         return False
     os.makedirs(ASSETS, exist_ok=True)
-    shutil.copyfile(os.path.join(ref_loader.REF_ROOT, 'FaceBoxes', 'weights', 'FaceBoxesProd.pth'), os.path.join(ASSETS, 'FaceBoxesProd.pth'))
-    for i in range(1, 5):
-        shutil.copyfile(os.path.join(ref_loader.REF_ROOT, 'img', f'sample_{i}.jpg'), os.path.join(ASSETS, f'sample_{i}.jpg'))
+    pairs = [(os.path.join(ref_loader.REF_ROOT, 'FaceBoxes', 'weights', 'FaceBoxesProd.pth'), os.path.join(ASSETS, 'FaceBoxesProd.pth'))]
+    pairs += [(os.path.join(ref_loader.REF_ROOT, 'img', f'sample_{i}.jpg'), os.path.join(ASSETS, f'sample_{i}.jpg')) for i in range(1, 5)]
+    for src, dst in pairs:
+        # a staged file is never seen half written: a test that reads it while another process stages again (a second build beside a
+        # running suite) used to meet a truncated checkpoint or JPEG.  Identical files are left alone, new ones are moved into place.
+        if os.path.isfile(dst) and filecmp.cmp(src, dst, shallow=False):
+            continue
+        tmp = f'{dst}.{os.getpid()}.tmp'
+        shutil.copyfile(src, tmp)
+        os.replace(tmp, dst)
     return True
 
 

@@ -2,9 +2,9 @@
 
     python tests/golden/make_mobilenet1_golden.py
 
-Follows make_golden.py main_resnet50: the reference's own mobilenet_1() and mobilenet_05() (backbone_nets/mobilenetv1_backbone.py:232-245,
+Follows make_golden.py main_resnet50: the reference's own mobilenet_1(), mobilenet_05() and mobilenet_2() (backbone_nets/mobilenetv1_backbone.py:232-245,
 torch-only, importable as-is) loaded with synth.make_mobilenet1_state(seed, width), run on synth.normalize_crops(synth.make_crops(2, seed)).
-Recorded per width (suffix _1 / _05): out102, pool, the seeds, and the module's state_dict() key names with their shapes."""
+Recorded per width (suffix _1 / _05 / _2): out102, pool, the seeds, and the module's state_dict() key names with their shapes."""
 import importlib
 import os
 import sys
@@ -54,7 +54,7 @@ def main():
     torch.manual_seed(0)
     x = synth.normalize_crops(synth.make_crops(2, seed=mc.CROPS_SEED))
     rec = {'crops_seed': np.array(mc.CROPS_SEED)}
-    for width in (1.0, 0.5):
+    for width in (1.0, 0.5, 2.0):
         t = mc.TAG[width]
         out, pool, keys, shapes, ndim = run_reference(width, mc.SEEDS[width], x)
         rec.update({f'seed_{t}': np.array(mc.SEEDS[width]), f'out102_{t}': out, f'pool_{t}': pool, f'keys_{t}': keys,

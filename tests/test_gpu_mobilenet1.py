@@ -63,7 +63,7 @@ def _want(arch, tag, x_norm, faces):
     return np.stack([_REF[arch, tag, i][0] for i in faces]), np.stack([_REF[arch, tag, i][1] for i in faces])
 
 
-@pytest.mark.parametrize('arch', ['mobilenet_1', 'mobilenet_05'])
+@pytest.mark.parametrize('arch', ['mobilenet_1', 'mobilenet_05', 'mobilenet_2'])
 def test_golden_parity(models, arch):
     import torch
     from synergynet_amd import synth

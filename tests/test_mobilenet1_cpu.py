@@ -23,7 +23,7 @@ def golden_crops(golden):
     return synth.normalize_crops(synth.make_crops(2, seed=int(golden['crops_seed'])))
 
 
-@pytest.mark.parametrize('width', [1.0, 0.5])
+@pytest.mark.parametrize('width', [1.0, 0.5, 2.0])
 def test_restatement_matches_the_reference_golden(golden, golden_crops, width):
     from synergynet_amd import synth
     t = mc.TAG[width]
@@ -55,7 +55,7 @@ def test_restatement_matches_the_live_reference_module(width):
     assert e_out < mc.TOL and e_pool < mc.TOL
 
 
-@pytest.mark.parametrize('width', [1.0, 0.5])
+@pytest.mark.parametrize('width', [1.0, 0.5, 2.0])
 def test_keys_equal_the_reference_state_dict(golden, width):
     from synergynet_amd import synth
     from synergynet_amd.synergy3DMM import mobilenet1_keys
@@ -116,7 +116,7 @@ def test_symbols_in_header_ctypes_table_and_library():
     lib = _lib()
     hdr = open(os.path.join(ROOT, 'include', 'synergy_hip.h')).read()
     declared = set(re.findall(r'\b(syn_[a-z0-9_]+)\s*\(', hdr))
-    for s in ('syn_mobilenet1_flat_count', 'syn_mobilenet1_flops_per_face', 'syn_load_backbone_mobilenet1'):
+    for s in ('syn_mobilenet1_flat_count', 'syn_mobilenet1_flops_per_face', 'syn_load_backbone_mobilenet1', 'syn_mobilenet1_layer'):
         assert s in declared and s in abi.EXPORTED_SYMBOLS and hasattr(lib, s)
     assert lib.syn_abi_version() == 1
     for a in (-1, 0, 1, 5):
@@ -124,6 +124,11 @@ def test_symbols_in_header_ctypes_table_and_library():
     # no device is touched before the arguments are vetted
     flat = np.zeros(8, np.float32)
     assert lib.syn_load_backbone_mobilenet1(None, 2, flat.ctypes.data_as(ctypes.c_void_p), 8) == abi.SYN_ERR_INVALID
+    # ... nor by the per-layer hook: a NULL handle is refused although the (host) pointers would otherwise reach a launch
+    buf = np.full(8, 7.0, np.float32)
+    p = buf.ctypes.data_as(ctypes.c_void_p)
+    assert lib.syn_mobilenet1_layer(None, 14, 0, p, 0, 1, 8, p, 8, None, 0, None) == abi.SYN_ERR_INVALID
+    assert b'syn_mobilenet1_layer' in lib.syn_last_error() and np.all(buf == 7.0)
 
 
 def test_constants_blob_round_trip_and_rejections():
@@ -168,3 +173,106 @@ def test_unsupported_widths_are_refused_before_a_gpu_is_needed(arch):
     from synergynet_amd import SynergyNet
     with pytest.raises(RuntimeError, match=r'Please choose \[.*mobilenet_1, mobilenet_05, mobilenet_2\]'):
         SynergyNet(arch=arch, load_constants=False)
+
+
+# ---- the integer probe of tests/test_gpu_mobilenet1_layers.py: two conditions on the reference alone ----
+def test_probe_running_var_makes_the_scale_gamma():
+    """fl32(v* + 1e-5f) == 1.0f, so the library's sqrtf gives 1 and scale == gamma exactly; asserted, not trusted"""
+    v = mc.V_STAR
+    assert v.dtype == np.float32 and np.float32(v + np.float32(1e-5)) == np.float32(1.0)
+    assert np.float32(np.float32(0.5) / np.sqrt(np.float32(v + np.float32(1e-5)))) == np.float32(0.5)
+    import torch
+    assert mc.V_STAR64 + 1e-5 == 1.0 and float(torch.sqrt(torch.tensor(mc.V_STAR64, dtype=torch.float64) + 1e-5)) == 1.0      # the reference's side
+    sd = mc.make_integer_state(mc.PROBE_SEED, 0.5)
+    assert all(np.all(a == mc.V_STAR64) and a.dtype == np.float64 for k, a in mc.reference_state(sd).items() if k.endswith('running_var'))
+    for k, a in sd.items():
+        if k.endswith('running_var'):
+            assert a.dtype == np.float32 and np.all(a == v)
+        elif k.endswith('running_mean'):
+            assert not a.any()
+        elif k.endswith('bn_dw.weight') or k.endswith('bn_sep.weight') or k == 'bn1.weight':
+            assert set(np.unique(a)) <= {0.5, 1.0, 2.0, -1.0}
+        elif k.endswith('.weight'):
+            assert set(np.unique(a)) == {-2.0, -1.0, 1.0, 2.0}              # conv and head weights: small integers, no zero
+        elif k.endswith('.bias'):
+            assert np.all(a == np.rint(a))
+
+
+@pytest.mark.parametrize('arch', ['mobilenet_1', 'mobilenet_05', 'mobilenet_2'])
+def test_probe_is_exact_in_fp32_and_not_hidden_by_relu(arch):
+    """For every layer and batch the GPU test uses.  1. Exactness: every stage's largest possible partial sum times the common
+    denominator of its terms is below 2^24, and the float64 reference is unchanged by a cast to fp32.  2. ReLU does not hide the
+    probe: at most 25 % of a map's elements are 0 and no channel is all 0; at least 1 % are 0, so the clamp itself is exercised
+    (pool and heads have no clamp: only the first two apply).  Conditions on the inputs, not tolerances."""
+    w = mc.WIDTHS[arch]
+    sd = mc.reference_state(mc.make_integer_state(mc.PROBE_SEED, w))
+    for layer in range(15):
+        for B in mc.probe_batches(w, layer):
+            x = mc.integer_input(layer, w, B)
+            assert np.all(x == np.rint(x)) and (x.dtype == np.uint8 if layer == 0 else (x.min() == -3 and x.max() == 3))
+            assert all(not np.array_equal(x[i], x[i + 1]) for i in range(B - 1))
+            ref = mc.layer_reference(sd, w, layer, mc.normalize_u8(x) if layer == 0 else x)
+            for name, m in mc.exactness_margin(sd, w, layer, x):
+                assert m < 2 ** 24, f'layer {layer} B={B} {name}: {m:.4g}'
+            outs = [('out', ref)] if layer == 0 else [('depthwise' if layer < 14 else 'pool', ref[0]), ('out', ref[1])]
+            for name, r in outs:
+                assert r.dtype == np.float64 and np.array_equal(r.astype(np.float32).astype(np.float64), r)
+                zeros = float((r == 0).mean())
+                assert zeros <= 0.25, f'layer {layer} B={B} {name}: {zeros:.3f} zeros'
+                assert (r != 0).reshape(-1, r.shape[-1]).any(axis=0).all(), f'layer {layer} B={B} {name}: a dead channel'
+                if layer < 14:
+                    assert zeros >= 0.01, f'layer {layer} B={B} {name}: {zeros:.4f} zeros'
+
+
+def test_probe_batches_cover_the_tiling_edges():
+    for w in (1.0, 0.5, 2.0):
+        hout = [s[2] for s in mc.layer_shapes(w)]
+        assert hout == [60, 60, 30, 30, 15, 15, 8, 8, 8, 8, 8, 8, 4, 4, 1]
+        assert [mc.probe_batches(w, l) for l in (0, 1, 2, 4, 5, 6, 12, 13, 14)] == [[1], [1], [1], [1, 3], [1, 3], [1, 5], [1, 5], [1, 5], [1, 5]]
+    from synergynet_amd import synth
+    for w in (1.0, 0.5, 2.0):
+        assert [(s[1], s[3]) for s in mc.layer_shapes(w)[1:14]] == [(ci, co) for _, ci, co, _ in synth.mobilenet1_blocks(w)]
+    assert mc.layer_shapes(0.5)[1][:4] == (60, 16, 60, 32) and mc.layer_shapes(2.0)[13] == (4, 2048, 4, 2048)
+
+
+def test_layer_references_chain_to_the_whole_network():
+    """layer_reference 0..14 fed into each other IS mobilenet1_forward in float64: the same operations, on NHWC-strided tensors, so the
+    sums may run in another order -- 1e-12, four decades above float64 rounding and five below anything fp32 can show"""
+    import torch
+    from synergynet_amd import synth
+    w = 0.5
+    sd = synth.make_mobilenet1_state(mc.SEEDS[w], w)
+    x = synth.normalize_crops(synth.make_crops(2, seed=11))
+    want, want_pool = mc.mobilenet1_forward(sd, x, w, torch.float64)
+    y = mc.layer_reference(sd, w, 0, x)
+    for layer in range(1, 14):
+        _, y = mc.layer_reference(sd, w, layer, y)
+    pool, out = mc.layer_reference(sd, w, 14, y)
+    assert pool.shape == want_pool.shape and out.shape == (2, 62)
+    assert mc.rel_max(pool, want_pool) < 1e-12 and mc.rel_max(out, want[:, :62]) < 1e-12
+
+
+def test_fp32_layers_stay_within_the_derived_bound():
+    """torch's own fp32 layers against the float64 reference, judged by layer_bound as the GPU test judges the kernels (real crops,
+    B = 1, every layer of mobilenet_05 here; all three widths were measured at 0.26 of the bound at the most)."""
+    import torch
+    from synergynet_amd import synth
+    w = 0.5
+    sd = synth.make_mobilenet1_state(mc.SEEDS[w], w)
+    prev, worst = synth.normalize_crops(synth.make_crops(1, seed=12)).astype(np.float64), 0.0
+    for layer in range(15):
+        x = prev.astype(np.float32)
+        ref, got, bound = mc.layer_reference(sd, w, layer, x), mc.layer_reference(sd, w, layer, x, torch.float32), mc.layer_bound(sd, w, layer, x)
+        if layer == 0:
+            pairs = [(got, ref, bound)]
+        elif layer < 14:
+            pairs = [(got[0], ref[0], bound[0]), (got[1], ref[1], bound[1]),
+                     (got[1], mc.pointwise_reference(sd, layer, got[0]), mc.pointwise_bound(sd, layer, got[0]))]
+        else:
+            pairs = [(got[0], ref[0], bound[0]), (got[1], mc.heads_reference(sd, got[0]), mc.heads_bound(sd, got[0]))]
+        for g, r, b in pairs:
+            assert g.dtype == np.float32 and b.shape == r.shape == g.shape and float((b > 0).mean()) > 0.7
+            worst = max(worst, mc.bound_ratio(g, r, b))
+        prev = ref if layer == 0 else ref[1]
+    print(f'torch fp32 against float64: max err / bound = {worst:.3f}')
+    assert worst < 1.0
