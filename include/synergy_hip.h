@@ -137,6 +137,25 @@ size_t syn_mobilenet1_flat_count(int arch);
 double syn_mobilenet1_flops_per_face(int arch);
 int syn_load_backbone_mobilenet1(syn_handle *h, int arch, const float *flat, size_t n_floats);
 
+/* The GhostNet backbone (reference backbone_nets/ghostnet_backbone.py:76-266, width 1.0; `--arch ghostnet` of main_train.py).
+ * Backbone id 6.  The whole id table:
+ *   0 mobilenet_v2 | 1 resnet50 | 2 mobilenet_1 | 3 mobilenet_05 | 4 mobilenet_2 | 5: never assigned | 6 ghostnet
+ * `flat` = the module's state_dict() order without num_batches_tracked (synergynet_amd.synergy3DMM.ghostnet_keys): conv_stem.weight, bn1.*,
+ * then per bottleneck blocks.S.I: ghost1.{primary_conv.0.weight, primary_conv.1.*, cheap_operation.0.weight, cheap_operation.1.*},
+ * [conv_dw.weight, bn_dw.* when stride 2], [se.conv_reduce.{weight,bias}, se.conv_expand.{weight,bias}], ghost2.{...},
+ * [shortcut.0.weight, shortcut.1.*, shortcut.2.weight, shortcut.3.* when in != out or stride 2]; blocks.9.0.conv.weight, blocks.9.0.bn1.*,
+ * conv_head.{weight,bias}, classifier_ori / _shape / _exp / _texture {weight, bias}.  BatchNorm is folded on the host in fp32 (eps 1e-5).
+ * After loading, syn_backbone_forward[_u8] run this network, every product exact fp32 (fp32-input MFMA, fp32 depthwise and SE means):
+ * syn_numerics_report has nothing to prove, syn_backbone_range_status / _calibrate return 0.  They return the first 62 of the 102
+ * outputs (ori 12 | shape 40 | exp 10; classifier_texture is loaded but never computed); pool = the 1280 outputs of conv_head + ReLU
+ * (act2), what the heads consume -- 1280 wide like mobilenet_v2's, so syn_refine_landmarks and the synergy forward accept this arch.
+ * SYNERGY_HIP_FUSION / syn_set_schedule(h, .): 0 = one launch per layer (104 launches, the cross-check); 1 = every GhostModule on a
+ * 15x15, 8x8 or 4x4 map as one launch (79 launches); 2 (default) = as 1.  syn_ghostnet_flops_per_face = 2 x 45 802 556 MAC, the
+ * module with all four heads. */
+size_t syn_ghostnet_flat_count(void);
+double syn_ghostnet_flops_per_face(void);
+int syn_load_backbone_ghostnet(syn_handle *h, const float *flat, size_t n_floats);
+
 /* ParamsPack (utils/params.py:10-35) + the register_buffer block (synergy3DMM.py:95-105).
  * HOST arrays: w_shp [3*n_vert,40], w_exp [3*n_vert,10], u [3*n_vert] (= u_shp+u_exp),
  * param_mean/param_std [>=62] (first 62 used), keypoints [3*n_lmk] flat indices into the
@@ -172,7 +191,7 @@ int syn_describe_constants(syn_handle *h, void *host_header, size_t bytes);
 /* Device-free twins of the hand-off: neither makes a HIP call, so a loader process (or a test) without a GPU can produce and
  * vet the blob.  syn_pack_constants_host writes, from HOST arrays (same meaning as syn_load_backbone / _resnet50 / syn_load_basis;
  * backbone_flat or the whole basis group may be NULL), exactly the bytes syn_export_constants produces after the same loads;
- * arch 0 = mobilenet_v2, 1 = resnet50, 2 / 3 / 4 = mobilenet_1 / _05 / _2.  syn_check_constants_host applies syn_import_constants' acceptance checks (magic, version,
+ * arch 0 = mobilenet_v2, 1 = resnet50, 2 / 3 / 4 = mobilenet_1 / _05 / _2, 6 = ghostnet (5 was never assigned and is refused).  syn_check_constants_host applies syn_import_constants' acceptance checks (magic, version,
  * sizes vs this library's network tables, payload within the buffer) to a host copy of a blob. */
 size_t syn_pack_constants_host_bytes(int arch, int have_backbone, int n_vert, int n_lmk);
 int syn_pack_constants_host(int arch, const float *backbone_flat, size_t n_floats, const float *w_shp, const float *w_exp,
@@ -518,7 +537,8 @@ int syn_load_synergy(syn_handle *h, const float *flat, size_t n);
  * must be ordered on one stream, and the FIRST call at a new largest B frees and reallocates it behind a device-wide synchronisation
  * -- it stalls every stream once and must not happen inside a stream capture (run the largest batch once before capturing).
  * SYN_ERR_NOT_LOADED before syn_load_synergy / syn_load_basis; SYN_ERR_INVALID for B <= 0 or NULL pointers or overlapping outputs or
- * a handle whose backbone is resnet50 or a MobileNetV1 (their pooled features are not 1280-d: the refinement is unavailable there). */
+ * a handle whose backbone is resnet50 or a MobileNetV1 (their pooled features are not 1280-d: the refinement is unavailable there;
+ * ghostnet's is 1280-d and is accepted). */
 int syn_refine_landmarks(syn_handle *h, const float *param /*[B 62] whitened*/, const float *pool /*[B 1280]*/, int B, int transform,
                          const float *roi /*nullable [B 5]*/, float *lmk_coarse /*nullable [B 3 68]*/, float *lmk_refined /*[B 3 68]*/,
                          float *global_feat /*nullable [B 1024]*/, void *stream);
@@ -556,6 +576,20 @@ int syn_backbone_profile(syn_handle *h, const uint8_t *img_hwc, int B, int max_l
  * pointers.  c0 = 32 w, pool = 1024 w, block shapes as in DESIGN 5.13 (w = 1, 0.5, 2). */
 int syn_mobilenet1_layer(syn_handle *h, int layer, int fused, const void *in, int in_u8, int B, size_t n_in,
                          float *out, size_t n_out, float *aux, size_t n_aux, void *stream);
+
+/* One block of the loaded GhostNet (arch 6) on activations the caller supplies, through exactly the launches the forward uses for that
+ * block (one helper derives the launch arguments for both) -- the hook tests/test_gpu_ghostnet.py judges every block with.
+ *   block 0..15  bottleneck blocks.0.0 .. blocks.8.3: in = NHWC fp32 [B,hin,hin,cin], out = [B,hout,hout,cout]; on a block with
+ *                squeeze-and-excite (3, 4, 9, 10, 11, 13, 15) a non-NULL aux receives the gate [B,mid]
+ *   block 16     blocks.9.0 (ConvBnAct): in = [B,4,4,160], out = [B,4,4,960]
+ *   block 17     pool + conv_head + ReLU + heads: in = [B,4,4,960], out = [B,62], a non-NULL aux receives the pooled feature [B,1280]
+ * fused = 1: the GhostModules of the block that have a fused launch use it; fused = 0: one launch per layer.  n_in / n_out / n_aux are
+ * ELEMENT counts (n_aux = 0 when aux is NULL).  Refused with SYN_ERR_INVALID and a message that names what was expected, before any
+ * launch, with `out` untouched: a count that differs from what the block needs, a handle whose arch is not ghostnet, block outside
+ * 0..17, B < 1 or B > 65536, fused other than 0 / 1, aux on a block that has neither gate nor pool.  Asynchronous on `stream`; all
+ * pointers are device pointers; the block's intermediates live in the handle's workspace (one stream at a time, as the forward). */
+int syn_ghostnet_block(syn_handle *h, int block, int fused, const float *in_nhwc, int B, size_t n_in,
+                       float *out, size_t n_out, float *aux, size_t n_aux, void *stream);
 
 /* The dense reconstruction (transform = 1) into a pitched output with HIP events around its kernels, on the default stream;
  * synchronises.  ms2[0] = per-face prologue, ms2[1] = the contraction + pose epilogue + mesh stores -- the HBM-write-bound kernel

@@ -45,6 +45,9 @@ _SIGS = {
     'syn_mobilenet1_flat_count': (C.c_size_t, [C.c_int]),
     'syn_mobilenet1_flops_per_face': (C.c_double, [C.c_int]),
     'syn_load_backbone_mobilenet1': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    'syn_ghostnet_flat_count': (C.c_size_t, []),
+    'syn_ghostnet_flops_per_face': (C.c_double, []),
+    'syn_load_backbone_ghostnet': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     'syn_load_basis': (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int, C.c_int]),
     'syn_constants_bytes': (C.c_size_t, [C.c_void_p]),
     'syn_export_constants': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -106,6 +109,8 @@ _SIGS = {
     'syn_backbone_profile': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'syn_mobilenet1_layer': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_size_t, C.c_void_p]),
+    'syn_ghostnet_block': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
     'syn_reconstruct_profile': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'syn_backbone_flops_per_face': (C.c_double, []),
     'syn_pointwise_flops_per_face': (C.c_double, []),

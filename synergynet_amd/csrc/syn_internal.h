@@ -261,6 +261,26 @@ void launch_mb1_depthwise(const float *in, const float *w9xC, const float *scale
 void launch_mb1_pointwise(const float *A, const float *W, const float *scale, const float *shift, float *C, int M, int K, int N,
                           hipStream_t s);
 
+// ---- GhostNet (ghostnet_kernels.hip): every product exact fp32; all pitches, offsets, K and N are multiples of 4 ----
+// C[m][n] = act(scale[n] * sum_k A[m][k] gate[m / HW][k] W[n][k] + shift[n]); A rows of pitch lda, C rows of pitch ldc (pass C + offset to
+// write a channel slice); scale NULL = 1 (a convolution with a bias); gate NULL = none; act 0 none | 1 ReLU | 2 hard sigmoid
+void launch_gn_pointwise(const float *A, int lda, const float *W, const float *scale, const float *shift, const float *gate, int HW,
+                         float *C, int ldc, int M, int K, int N, int act, hipStream_t s);
+// depthwise ks x ks (3 | 5), stride 1 | 2, pad ks / 2, w [ks*ks][C] tap-major, + BN (+ ReLU) (+ res); in / out / res point at the first
+// channel of their slices; pass_out (nullable, stride 1): out-pitched copy of the input pixel + pass_res (nullable, res-pitched)
+void launch_gn_depthwise(const float *in, int ldi, const float *w, const float *scale, const float *shift, float *out, int ldo,
+                         const float *res, int ldr, float *pass_out, const float *pass_res, int B, int Hin, int Hout, int C, int ks,
+                         int stride, int relu, hipStream_t s);
+// per-face channel means of in [B][HW] rows of pitch ld -> out [B][C]
+void launch_gn_mean(const float *in, int ld, float *out, int B, int HW, int C, hipStream_t s);
+// a whole GhostModule: X [B][H*H] rows of pitch ldx, K channels (* gate [B][K]) -> Y [B][H*H][2 N1] = primary | cheap (+ res, pitch ldr)
+bool gn_ghost_exists(int H);        // H = 15, 8, 4: a whole face fits the LDS tile
+constexpr int kGnTwoFacesMinBatch = 1024;      // 8x8 maps: two faces per workgroup from this many faces on, one below
+int gn_ghost_faces(int H, int B);   // faces per workgroup of the fused module
+void launch_gn_ghost(const float *X, int ldx, const float *gate, const float *Wp, const float *p_scale, const float *p_shift,
+                     const float *Wd, const float *d_scale, const float *d_shift, const float *res, int ldr, float *Y, int B, int H,
+                     int K, int N1, int relu, hipStream_t s);
+
 // ---- reconstruction -----------------------------------------------------------------
 // basis: pre-packed per 32-vertex tile in MFMA-operand lane order (see recon_kernels.hip):
 //   Bp[tile][coord x|y|z][chunk][lane][4], K = 52: 0..39 shape, 40..49 expression,

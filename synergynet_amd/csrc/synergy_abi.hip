@@ -279,9 +279,20 @@ const ResNet50 &resnet50() {
 // (include/synergy_hip.h); widths 0.25 and 0.75 give 8 / 24 channels, no multiple of the 16-wide MFMA tile, and are not offered.
 constexpr int kArchMb1First = 2, kArchLast = 4;
 bool is_mb1(int arch) { return arch >= kArchMb1First && arch <= kArchLast; }
+// The whole id table: 0 mobilenet_v2 | 1 resnet50 | 2 mobilenet_1 | 3 mobilenet_05 | 4 mobilenet_2 | 5: never assigned | 6 ghostnet.
+constexpr int kArchGhost = 6;
+bool is_gn(int arch) { return arch == kArchGhost; }
+bool arch_known(int arch) { return (arch >= 0 && arch <= kArchLast) || arch == kArchGhost; }
 const char *arch_name(int arch) {
-    static const char *const names[] = {"mobilenet_v2", "resnet50", "mobilenet_1", "mobilenet_05", "mobilenet_2"};
-    return arch >= 0 && arch <= kArchLast ? names[arch] : "?";
+    switch (arch) {
+    case 0: return "mobilenet_v2";
+    case 1: return "resnet50";
+    case 2: return "mobilenet_1";
+    case 3: return "mobilenet_05";
+    case 4: return "mobilenet_2";
+    case kArchGhost: return "ghostnet";
+    default: return "?";
+    }
 }
 struct Mb1Block {
     int cin, cout, stride, hin, hout;
@@ -336,6 +347,118 @@ struct Mb1Net {
 const Mb1Net &mb1net(int arch) {
     static const Mb1Net n1(1, 1), n05(1, 2), n2(2, 1);
     return arch == 3 ? n05 : (arch == 4 ? n2 : n1);
+}
+
+// ---- GhostNet (reference backbone_nets/ghostnet_backbone.py:76-266, width 1.0), arch id 6.  conv_stem + bn1 + ReLU, 16 GhostBottlenecks
+// (blocks.0.0 .. blocks.8.3), blocks.9.0 = ConvBnAct 160 -> 960, global pool, conv_head 960 -> 1280 (bias) + ReLU, four heads.
+// A GhostModule(c -> o) = primary 1x1 c -> o / 2 + BN (+ ReLU), cheap = depthwise 3x3 on primary + BN (+ ReLU), cat(primary, cheap);
+// every o here is even, so the reference's [:, :oup] slice (:99) drops nothing -- GnNet() refuses a table where that is not so.
+struct GnConv { int cin = 0, cout = 0; size_t src = 0, dst_w = 0, dst_scale = 0, dst_shift = 0; };      // flat: weight [cout][cin], bn x4
+struct GnDw { int c = 0, k = 0; size_t src = 0, dst_w = 0, dst_scale = 0, dst_shift = 0; };             // flat: weight [c][1][k][k], bn x4; packed [k*k][c]
+struct GnBlock {
+    int cin, mid, cout, k, stride, se, hin, hout;
+    bool conv_sc;
+    GnConv g1p, g2p, scp;                                      // ghost1 / ghost2 primary, shortcut 1x1
+    GnDw g1d, g2d, dw, scd;                                    // ghost1 / ghost2 cheap, the stride-2 conv_dw, shortcut depthwise
+    size_t src_se, dst_rw, dst_rb, dst_ew, dst_eb;             // se.conv_reduce {weight [se][mid], bias}, se.conv_expand {weight [mid][se], bias}
+};
+struct GnNet {
+    static constexpr int kBlocks = 16, kStem = 16, kLast = 960, kPool = 1280;
+    std::vector<GnBlock> blocks;
+    GnConv last;                                               // blocks.9.0
+    size_t flat_count = 0, packed_count = 0, dst_stem_w = 0, dst_stem_scale = 0, dst_stem_shift = 0;
+    size_t src_head = 0, dst_head_w = 0, dst_head_b = 0, src_fc = 0, dst_fc_w = 0, dst_fc_b = 0;
+    // per-face floats of the workspace regions: block input / output (x 2), ghost1 output, conv_dw output, ghost2 primary, shortcut
+    // depthwise and 1x1 outputs, and the small vectors (SE mean | reduced | gate; pooled 960 | 1280)
+    size_t buf_io = 0, buf_g1 = 0, buf_d = 0, buf_t = 0, buf_s = 0, buf_r = 0, buf_small = 2304;
+    double macs = 0, flops = 0;
+    size_t ws_per_face() const { return 2 * buf_io + buf_g1 + buf_d + buf_t + buf_s + buf_r + buf_small; }
+    GnNet() {
+        static const int tab[kBlocks][6] = {      // in, mid, out, k, stride, SE reduced channels (cfgs :240-265 through _make_divisible)
+            {16, 16, 16, 3, 1, 0},    {16, 48, 24, 3, 2, 0},     {24, 72, 24, 3, 1, 0},     {24, 72, 40, 5, 2, 20},
+            {40, 120, 40, 5, 1, 32},  {40, 240, 80, 3, 2, 0},    {80, 200, 80, 3, 1, 0},    {80, 184, 80, 3, 1, 0},
+            {80, 184, 80, 3, 1, 0},   {80, 480, 112, 3, 1, 120}, {112, 672, 112, 3, 1, 168}, {112, 672, 160, 5, 2, 168},
+            {160, 960, 160, 5, 1, 0}, {160, 960, 160, 5, 1, 240}, {160, 960, 160, 5, 1, 0}, {160, 960, 160, 5, 1, 240}};
+        size_t src = 0, dst = 0;
+        auto conv = [&](int cin, int cout, int hw) {
+            GnConv c; c.cin = cin; c.cout = cout;
+            c.src = src; src += (size_t)cout * cin + 4 * (size_t)cout;
+            c.dst_w = dst; dst += (size_t)cout * cin;
+            c.dst_scale = dst; dst += cout;
+            c.dst_shift = dst; dst += cout;
+            macs += (double)cin * cout * hw;
+            return c;
+        };
+        auto dwc = [&](int c, int k, int hw) {
+            GnDw d; d.c = c; d.k = k;
+            d.src = src; src += (size_t)c * k * k + 4 * (size_t)c;
+            d.dst_w = dst; dst += (size_t)c * k * k;
+            d.dst_scale = dst; dst += c;
+            d.dst_shift = dst; dst += c;
+            macs += (double)c * k * k * hw;
+            return d;
+        };
+        auto up = [](size_t &m, size_t v) { m = v > m ? v : m; };
+        src += (size_t)kStem * 27 + 4 * (size_t)kStem;
+        dst_stem_w = dst; dst += (size_t)27 * kStem;
+        dst_stem_scale = dst; dst += kStem;
+        dst_stem_shift = dst; dst += kStem;
+        macs = 27.0 * kStem * 3600;
+        buf_io = (size_t)kStem * 3600;
+        int h = 60;
+        for (const auto &t : tab) {
+            GnBlock b{};
+            b.cin = t[0]; b.mid = t[1]; b.cout = t[2]; b.k = t[3]; b.stride = t[4]; b.se = t[5];
+            b.hin = h; b.hout = (h - 1) / b.stride + 1;        // pad k / 2: 60 -> 30 -> 15 -> 8 -> 4
+            b.conv_sc = !(b.cin == b.cout && b.stride == 1);
+            if (b.mid % 8 || b.cout % 8 || b.cin % 4 || b.se % 4) {      // halves of the concatenation must be whole float4s
+                fprintf(stderr, "GnNet: block with channels %d / %d / %d / %d cannot be packed\n", b.cin, b.mid, b.cout, b.se);
+                abort();
+            }
+            const int hw = b.hin * b.hin, hw2 = b.hout * b.hout;
+            b.g1p = conv(b.cin, b.mid / 2, hw);
+            b.g1d = dwc(b.mid / 2, 3, hw);
+            if (b.stride == 2) b.dw = dwc(b.mid, b.k, hw2);
+            if (b.se) {
+                b.src_se = src; src += 2 * (size_t)b.se * b.mid + b.se + b.mid;
+                b.dst_rw = dst; dst += (size_t)b.se * b.mid;
+                b.dst_rb = dst; dst += b.se;
+                b.dst_ew = dst; dst += (size_t)b.se * b.mid;
+                b.dst_eb = dst; dst += b.mid;
+                macs += 2.0 * b.se * b.mid;
+            }
+            b.g2p = conv(b.mid, b.cout / 2, hw2);
+            b.g2d = dwc(b.cout / 2, 3, hw2);
+            if (b.conv_sc) {
+                b.scd = dwc(b.cin, b.k, hw2);
+                b.scp = conv(b.cin, b.cout, hw2);
+            }
+            up(buf_io, (size_t)b.cout * hw2);
+            up(buf_g1, (size_t)b.mid * hw);
+            up(buf_d, (size_t)b.mid * hw2);
+            up(buf_t, (size_t)(b.cout / 2) * hw2);
+            up(buf_s, (size_t)b.cin * hw2);
+            up(buf_r, (size_t)b.cout * hw2);
+            blocks.push_back(b);
+            h = b.hout;
+        }
+        last = conv(160, kLast, 16);
+        src_head = src; src += (size_t)kPool * kLast + kPool;
+        dst_head_w = dst; dst += (size_t)kPool * kLast;
+        dst_head_b = dst; dst += kPool;
+        macs += (double)kPool * kLast;
+        src_fc = src; src += (size_t)102 * kPool + 102;
+        dst_fc_w = dst; dst += (size_t)64 * kPool;             // rows 0..61 = ori | shape | exp; classifier_texture is loaded but never computed
+        dst_fc_b = dst; dst += 64;
+        macs += 102.0 * kPool;                                 // the module's own count, all four heads
+        flat_count = src;
+        packed_count = dst;
+        flops = 2.0 * macs;
+    }
+};
+const GnNet &gnnet() {
+    static const GnNet n;
+    return n;
 }
 
 struct ConstHeader {   // first 256 bytes of an exported constants buffer
@@ -439,11 +562,12 @@ const unsigned *basis_f16_lmk(const syn_handle *h) { return basis_f16_dense(h) +
 size_t ws_floats_per_face() {
     const size_t mb = 2 * net().max_io + 2 * net().max_hidden, rn = 4 * resnet50().buf_big + 2 * resnet50().buf_mid;
     const size_t m1 = 2 * mb1net(4).buf_io + mb1net(4).buf_dw;      // the widest MobileNetV1 (equal to rn: the size does not change)
-    const size_t two = mb > rn ? mb : rn;
-    return two > m1 ? two : m1;    // one activation workspace serves every backbone
+    const size_t two = mb > rn ? mb : rn, gn = gnnet().ws_per_face();      // (GhostNet needs less than half of rn: the size does not change)
+    const size_t three = two > m1 ? two : m1;
+    return three > gn ? three : gn;    // one activation workspace serves every backbone
 }
-size_t backbone_floats(int arch) { return is_mb1(arch) ? mb1net(arch).packed_count : (arch == 1 ? resnet50().packed_count : net().packed_count); }
-size_t backbone_flat_floats(int arch) { return is_mb1(arch) ? mb1net(arch).flat_count : (arch == 1 ? resnet50().flat_count : net().flat_count); }
+size_t backbone_floats(int arch) { return is_gn(arch) ? gnnet().packed_count : is_mb1(arch) ? mb1net(arch).packed_count : (arch == 1 ? resnet50().packed_count : net().packed_count); }
+size_t backbone_flat_floats(int arch) { return is_gn(arch) ? gnnet().flat_count : is_mb1(arch) ? mb1net(arch).flat_count : (arch == 1 ? resnet50().flat_count : net().flat_count); }
 
 // Both scratch regions only ever grow; growing synchronises the whole device first, so work in flight on another stream
 // (synergynet_amd/streams.py runs the reconstruction of batch i beside the backbone of batch i+1) never loses its buffer.
@@ -1039,6 +1163,150 @@ int run_mobilenet1(syn_handle *h, const float *img, const uint8_t *img8, int B, 
     return SYN_OK;
 }
 
+// ---- GhostNet forward (GhostNet.forward, ghostnet_backbone.py:214-233) ----
+// Schedule (SYNERGY_HIP_FUSION / syn_set_schedule): 0 = one launch per layer; 1 = every GhostModule whose map is 15^2, 8^2 or 4^2 as one
+// gn_ghost launch (25 of the 32 modules: blocks.3.0's ghost2 onward; the 60^2 and 30^2 modules have no fused kernel and stay per-layer);
+// 2 (default) = as 1.  Both sum every output in the same order.
+bool gn_fused(const syn_handle *h) { return h->fusion >= 1; }      // no batch threshold: measured faster at 1, 32, 128 and 1024 faces
+struct GnWs { float *g1, *d, *t, *s, *r, *small; };           // a block's intermediates, B faces each (GnNet::buf_*)
+GnWs gn_ws(const GnNet &n, float *base, int B) {
+    GnWs w;
+    w.g1 = base;
+    w.d = w.g1 + (size_t)B * n.buf_g1;
+    w.t = w.d + (size_t)B * n.buf_d;
+    w.s = w.t + (size_t)B * n.buf_t;
+    w.r = w.s + (size_t)B * n.buf_s;
+    w.small = w.r + (size_t)B * n.buf_r;
+    return w;
+}
+// One block of the forward, the ONLY place the GhostNet launch arguments are derived: run_ghostnet walks blocks 0..17 through it and
+// syn_ghostnet_block runs one of them.  block 0..15 = bottleneck (in [B,hin,hin,cin] -> out [B,hout,hout,cout]; aux, nullable, = the SE gate
+// [B,mid] of an SE block), 16 = ConvBnAct (in [B,4,4,160] -> out [B,4,4,960]), 17 = pool + conv_head + heads (in [B,4,4,960] -> out = param
+// [B,62], aux, nullable, = the pooled feature [B,1280]).  mark(code, flops per face) is called after every launch; code = 100 (block + 1) +
+// step: 0 ghost1 (primary, or the fused module), 1 ghost1 cheap, 2 conv_dw, 3 SE mean, 4 SE reduce, 5 SE expand, 6 shortcut depthwise,
+// 7 shortcut 1x1, 8 ghost2 (primary, or fused), 9 ghost2 cheap; 1700 ConvBnAct; 1800 pool, 1801 conv_head, 1802 heads.
+template <class Mark>
+void gn_launch_block(const GnNet &n, const float *P, int block, bool fused, const float *in, int B, float *out, float *aux, const GnWs &w,
+                     hipStream_t s, Mark &&mark) {
+    auto pw = [&](const GnConv &c, const float *A, int lda, const float *gate, int HW, float *C, int ldc, int act) {
+        syn::launch_gn_pointwise(A, lda, P + c.dst_w, P + c.dst_scale, P + c.dst_shift, gate, HW, C, ldc, B * HW, c.cin, c.cout, act, s);
+    };
+    auto dw = [&](const GnDw &d, const float *A, int lda, float *C, int ldc, const float *res, int ldr, float *pass_out, const float *pass_res,
+                  int Hin, int Hout, int stride, int relu) {
+        syn::launch_gn_depthwise(A, lda, P + d.dst_w, P + d.dst_scale, P + d.dst_shift, C, ldc, res, ldr, pass_out, pass_res, B, Hin, Hout, d.c, d.k,
+                                 stride, relu, s);
+    };
+    auto ghost = [&](const GnConv &c, const GnDw &d, const float *A, int lda, const float *gate, const float *res, int ldr, float *Y, int H,
+                     int relu) {
+        syn::launch_gn_ghost(A, lda, gate, P + c.dst_w, P + c.dst_scale, P + c.dst_shift, P + d.dst_w, P + d.dst_scale, P + d.dst_shift, res, ldr, Y,
+                             B, H, c.cin, c.cout, relu, s);
+    };
+    if (block == 16) {
+        pw(n.last, in, 160, nullptr, 16, out, GnNet::kLast, 1);
+        mark(1700, 2.0 * 160 * GnNet::kLast * 16);
+        return;
+    }
+    if (block == 17) {
+        float *mean = w.small, *pool = aux ? aux : w.small + (size_t)B * GnNet::kLast;
+        syn::launch_gn_mean(in, GnNet::kLast, mean, B, 16, GnNet::kLast, s);
+        mark(1800, 16.0 * GnNet::kLast);
+        syn::launch_gn_pointwise(mean, GnNet::kLast, P + n.dst_head_w, nullptr, P + n.dst_head_b, nullptr, 1, pool, GnNet::kPool, B, GnNet::kLast,
+                                 GnNet::kPool, 1, s);
+        mark(1801, 2.0 * GnNet::kLast * GnNet::kPool);
+        // the SynergyNet wrapper takes [:, :62] = ori | shape | exp, the first 62 rows as packed; a 1-pixel "pool" passes the feature through
+        syn::launch_pool_fc_generic(pool, P + n.dst_fc_w, P + n.dst_fc_b, out, nullptr, B, 1, GnNet::kPool, 62, 62, s);
+        mark(1802, 2.0 * GnNet::kPool * 62);
+        return;
+    }
+    const GnBlock &b = n.blocks[block];
+    const int code = 100 * (block + 1), H = b.hin, H2 = b.hout, HW = H * H, HW2 = H2 * H2, m1 = b.mid / 2, o1 = b.cout / 2;
+    const double f_g1 = 2.0 * HW * (b.cin * m1), f_g1d = 2.0 * HW * 9 * m1, f_g2 = 2.0 * HW2 * ((double)b.mid * o1), f_g2d = 2.0 * HW2 * 9 * o1;
+    // ghost1: in -> g1 [B,H,H,mid], ReLU
+    if (fused && syn::gn_ghost_exists(H)) {
+        ghost(b.g1p, b.g1d, in, b.cin, nullptr, nullptr, 0, w.g1, H, 1);
+        mark(code + 0, f_g1 + f_g1d);
+    } else {
+        pw(b.g1p, in, b.cin, nullptr, HW, w.g1, b.mid, 1);
+        mark(code + 0, f_g1);
+        dw(b.g1d, w.g1, b.mid, w.g1 + m1, b.mid, nullptr, 0, nullptr, nullptr, H, H, 1, 1);
+        mark(code + 1, f_g1d);
+    }
+    const float *cur = w.g1;
+    if (b.stride == 2) {          // conv_dw + bn_dw, no ReLU
+        dw(b.dw, w.g1, b.mid, w.d, b.mid, nullptr, 0, nullptr, nullptr, H, H2, 2, 0);
+        mark(code + 2, 2.0 * HW2 * b.k * b.k * b.mid);
+        cur = w.d;
+    }
+    const float *gate = nullptr;
+    if (b.se) {                   // the gate is applied where ghost2 loads its operand: the gated tensor is never stored
+        float *mean = w.small, *red = mean + (size_t)B * b.mid, *gt = aux ? aux : red + (size_t)B * b.se;
+        syn::launch_gn_mean(cur, b.mid, mean, B, HW2, b.mid, s);
+        mark(code + 3, (double)HW2 * b.mid);
+        syn::launch_gn_pointwise(mean, b.mid, P + b.dst_rw, nullptr, P + b.dst_rb, nullptr, 1, red, b.se, B, b.mid, b.se, 1, s);
+        mark(code + 4, 2.0 * b.mid * b.se);
+        syn::launch_gn_pointwise(red, b.se, P + b.dst_ew, nullptr, P + b.dst_eb, nullptr, 1, gt, b.mid, B, b.se, b.mid, 2, s);
+        mark(code + 5, 2.0 * b.mid * b.se);
+        gate = gt;
+    }
+    const float *res = in;
+    int ldr = b.cin;
+    if (b.conv_sc) {              // depthwise k x k with the block's stride + BN, 1x1 + BN, no ReLU
+        dw(b.scd, in, b.cin, w.s, b.cin, nullptr, 0, nullptr, nullptr, H, H2, b.stride, 0);
+        mark(code + 6, 2.0 * HW2 * b.k * b.k * b.cin);
+        pw(b.scp, w.s, b.cin, nullptr, HW2, w.r, b.cout, 0);
+        mark(code + 7, 2.0 * HW2 * b.cin * b.cout);
+        res = w.r;
+        ldr = b.cout;
+    }
+    // ghost2: cur (* gate) -> out [B,H2,H2,cout], no ReLU, + shortcut.  `cheap` reads `primary` WITHOUT the shortcut, so per-layer the
+    // primary goes to a scratch tensor and the depthwise launch stores both halves.
+    if (fused && syn::gn_ghost_exists(H2)) {
+        ghost(b.g2p, b.g2d, cur, b.mid, gate, res, ldr, out, H2, 0);
+        mark(code + 8, f_g2 + f_g2d);
+    } else {
+        pw(b.g2p, cur, b.mid, gate, HW2, w.t, o1, 0);
+        mark(code + 8, f_g2);
+        dw(b.g2d, w.t, o1, out + o1, b.cout, res + o1, ldr, out, res, H2, H2, 1, 0);
+        mark(code + 9, f_g2d);
+    }
+}
+int gn_launch_count(const GnNet &n, bool fused) {
+    int c = 1 + 1 + 3;            // stem, ConvBnAct, pool + conv_head + heads
+    for (const GnBlock &b : n.blocks)
+        c += (fused && syn::gn_ghost_exists(b.hin) ? 1 : 2) + (b.stride == 2) + (b.se ? 3 : 0) + (b.conv_sc ? 2 : 0) + (fused && syn::gn_ghost_exists(b.hout) ? 1 : 2);
+    return c;
+}
+
+int run_ghostnet(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s,
+                 std::vector<hipEvent_t> *marks = nullptr, std::vector<int> *mark_launch = nullptr, std::vector<double> *mark_flops = nullptr) {
+    const GnNet &n = gnnet();
+    int rc = ensure_ws(h, B);
+    if (rc) return rc;
+    float *X = h->ws, *Y = X + (size_t)B * n.buf_io;
+    const GnWs w = gn_ws(n, Y + (size_t)B * n.buf_io, B);
+    const float *P = h->d_backbone;
+    auto mark = [&](int code, double flops) {
+        if (!marks) return;
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, s);
+        marks->push_back(e);
+        mark_launch->push_back(code);
+        mark_flops->push_back(flops);
+    };
+    mark(-1, 0.0);
+    const bool fused = gn_fused(h);
+    syn::launch_mb1_stem(img, img8, P + n.dst_stem_w, P + n.dst_stem_scale, P + n.dst_stem_shift, X, GnNet::kStem, B, s);
+    mark(0, 2.0 * 27 * GnNet::kStem * 3600);
+    for (int block = 0; block <= 16; ++block) {
+        gn_launch_block(n, P, block, fused, X, B, Y, nullptr, w, s, mark);
+        float *t = X; X = Y; Y = t;
+    }
+    gn_launch_block(n, P, 17, fused, X, B, param, pool, w, s, mark);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 }  // namespace
 
 namespace syn {
@@ -1124,6 +1392,7 @@ size_t syn_backbone_flat_count(void) { return net().flat_count; }
 double syn_backbone_flops_per_face(void) { return net().flops; }
 double syn_pointwise_flops_per_face(void) { return net().pw_flops; }
 int syn_backbone_launch_count(syn_handle *h) {
+    if (h && is_gn(h->arch)) return gn_launch_count(gnnet(), gn_fused(h));      // 79 with the fused modules, 104 per layer
     if (h && is_mb1(h->arch)) return h->fusion >= 1 ? 15 : 28;      // stem + 13 blocks (x 2 per-layer) + pool and heads; schedule 2 below kMb1FusedMinBatch faces: 28
     return (int)net().layers.size() + 1;
 }
@@ -1698,7 +1967,7 @@ int syn_numerics_report(syn_handle *h, char *buf, size_t n) {
     char line[256];
     int n_fallback = 0;
     if (!h->d_backbone) out = "no backbone loaded\n";
-    else if (is_mb1(h->arch)) {
+    else if (is_mb1(h->arch) || is_gn(h->arch)) {
         snprintf(line, sizeof line, "%s: every product is exact fp32 (fp32-input MFMA, fp32 depthwise): no fp16 operand, nothing to prove or guard\n", arch_name(h->arch));
         out = line;
     }
@@ -2016,6 +2285,85 @@ int syn_load_backbone_mobilenet1(syn_handle *h, int arch, const float *flat, siz
     return SYN_OK;
 }
 
+// ---- GhostNet: flat = the module's state_dict order without num_batches_tracked (synergynet_amd.synergy3DMM.ghostnet_keys) ----
+size_t syn_ghostnet_flat_count(void) { return gnnet().flat_count; }
+double syn_ghostnet_flops_per_face(void) { return gnnet().flops; }
+
+static void pack_backbone_ghostnet(const float *flat, std::vector<float> &pk) {
+    const GnNet &n = gnnet();
+    pk.assign(n.packed_count, 0.f);
+    // BN folding in fp32: scale = gamma / sqrt(var + 1e-5), shift = beta - mean * scale
+    auto fold = [&](const float *bn, int c, size_t scale, size_t shift) {      // bn = weight | bias | running_mean | running_var
+        for (int i = 0; i < c; ++i) {
+            const float sc = bn[i] / sqrtf(bn[3 * c + i] + 1e-5f);
+            pk[scale + i] = sc;
+            pk[shift + i] = bn[c + i] - bn[2 * c + i] * sc;
+        }
+    };
+    auto conv = [&](const GnConv &c) {                         // [cout][cin]: as the kernels read it
+        memcpy(pk.data() + c.dst_w, flat + c.src, sizeof(float) * (size_t)c.cout * c.cin);
+        fold(flat + c.src + (size_t)c.cout * c.cin, c.cout, c.dst_scale, c.dst_shift);
+    };
+    auto dwc = [&](const GnDw &d) {                            // [c][1][k][k] -> tap-major [k*k][c]
+        const int kk = d.k * d.k;
+        for (int c = 0; c < d.c; ++c)
+            for (int t = 0; t < kk; ++t) pk[d.dst_w + (size_t)t * d.c + c] = flat[d.src + (size_t)c * kk + t];
+        fold(flat + d.src + (size_t)d.c * kk, d.c, d.dst_scale, d.dst_shift);
+    };
+    {   // conv_stem.weight [16][3][3][3] -> [ci*9 + ky*3 + kx][16] (launch_mb1_stem's layout)
+        const int c0 = GnNet::kStem;
+        for (int co = 0; co < c0; ++co)
+            for (int t = 0; t < 27; ++t) pk[n.dst_stem_w + (size_t)t * c0 + co] = flat[(size_t)co * 27 + t];
+        fold(flat + (size_t)c0 * 27, c0, n.dst_stem_scale, n.dst_stem_shift);
+    }
+    for (const GnBlock &b : n.blocks) {
+        conv(b.g1p); dwc(b.g1d);
+        if (b.stride == 2) dwc(b.dw);
+        if (b.se) {
+            const float *src = flat + b.src_se;
+            const size_t wn = (size_t)b.se * b.mid;
+            memcpy(pk.data() + b.dst_rw, src, sizeof(float) * wn);
+            memcpy(pk.data() + b.dst_rb, src + wn, sizeof(float) * b.se);
+            memcpy(pk.data() + b.dst_ew, src + wn + b.se, sizeof(float) * wn);
+            memcpy(pk.data() + b.dst_eb, src + 2 * wn + b.se, sizeof(float) * b.mid);
+        }
+        conv(b.g2p); dwc(b.g2d);
+        if (b.conv_sc) { dwc(b.scd); conv(b.scp); }
+    }
+    conv(n.last);
+    memcpy(pk.data() + n.dst_head_w, flat + n.src_head, sizeof(float) * (size_t)GnNet::kPool * GnNet::kLast);
+    memcpy(pk.data() + n.dst_head_b, flat + n.src_head + (size_t)GnNet::kPool * GnNet::kLast, sizeof(float) * GnNet::kPool);
+    {   // heads: flat order classifier_ori, _shape, _exp, _texture = the cat order (:227-231): rows 0..61 as they come; _texture is not packed
+        const float *src = flat + n.src_fc;
+        static const int hn[3] = {12, 40, 10};
+        int row = 0;
+        for (int k = 0; k < 3; ++k) {
+            memcpy(pk.data() + n.dst_fc_w + (size_t)row * GnNet::kPool, src, sizeof(float) * hn[k] * GnNet::kPool);
+            src += (size_t)hn[k] * GnNet::kPool;
+            memcpy(pk.data() + n.dst_fc_b + row, src, sizeof(float) * hn[k]);
+            src += hn[k];
+            row += hn[k];
+        }
+    }
+}
+
+int syn_load_backbone_ghostnet(syn_handle *h, const float *flat, size_t n_floats) {
+    if (!h || !flat) return fail(SYN_ERR_INVALID, "syn_load_backbone_ghostnet: NULL argument");
+    const GnNet &n = gnnet();
+    if (n_floats != n.flat_count) return fail(SYN_ERR_INVALID, "syn_load_backbone_ghostnet: got %zu floats, ghostnet has %zu", n_floats, n.flat_count);
+    std::vector<float> pk;
+    pack_backbone_ghostnet(flat, pk);
+    DeviceGuard g(h->device);
+    if (h->d_backbone) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->d_backbone)); h->d_backbone = nullptr; }
+    HIP_TRY(hipMalloc((void **)&h->d_backbone, n.packed_count * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->d_backbone, pk.data(), n.packed_count * sizeof(float), hipMemcpyHostToDevice));
+    h->arch = kArchGhost;
+    h->ri = RangeInfo{};
+    h->resnet_fp32 = 0; h->range_events = 0; h->guard_armed = 0; if (h->guard_word) { (void)hipDeviceSynchronize(); *(volatile unsigned *)h->guard_word = 0; }
+    h->resnet_w_unsafe[0] = h->resnet_w_unsafe[1] = h->resnet_w_unsafe[2] = 0;
+    return SYN_OK;
+}
+
 static void pack_basis(const float *w_shp, const float *w_exp, const float *u, const float *param_mean, const float *param_std,
                        const int64_t *keypoints, int n_lmk, int n_vert, std::vector<float> &pk) {
     const int nvp = round_up(n_vert, 32), nlp = round_up(n_lmk, 32);
@@ -2077,7 +2425,7 @@ int syn_load_basis(syn_handle *h, const float *w_shp, const float *w_exp, const 
 // arrays, and run the checks syn_import_constants makes on a host copy of a blob.  No HIP call is made: usable on a machine
 // without a GPU (a loader process, or tests/test_dist_cpu.py's gloo ranks).
 size_t syn_pack_constants_host_bytes(int arch, int have_backbone, int n_vert, int n_lmk) {
-    if (arch < 0 || arch > kArchLast) return 0;
+    if (!arch_known(arch)) return 0;
     size_t fl = have_backbone ? backbone_floats(arch) : 0;
     if (n_vert > 0 && n_lmk > 0) fl += basis_float_count(round_up(n_vert, 32), round_up(n_lmk, 32));
     return sizeof(ConstHeader) + fl * sizeof(float);
@@ -2087,7 +2435,7 @@ int syn_pack_constants_host(int arch, const float *backbone_flat, size_t n_float
                             const float *param_mean, const float *param_std, const int64_t *keypoints, int n_lmk, int n_vert,
                             void *host_dst, size_t bytes) {
     if (!host_dst) return fail(SYN_ERR_INVALID, "syn_pack_constants_host: NULL destination");
-    if (arch < 0 || arch > kArchLast) return fail(SYN_ERR_INVALID, "syn_pack_constants_host: arch=%d", arch);
+    if (!arch_known(arch)) return fail(SYN_ERR_INVALID, "syn_pack_constants_host: arch=%d", arch);
     const bool has_bb = backbone_flat != nullptr, has_basis = w_shp != nullptr;
     if (has_bb && n_floats != backbone_flat_floats(arch))
         return fail(SYN_ERR_INVALID, "syn_pack_constants_host: got %zu backbone floats", n_floats);
@@ -2102,7 +2450,8 @@ int syn_pack_constants_host(int arch, const float *backbone_flat, size_t n_float
     if (bytes < need) return fail(SYN_ERR_INVALID, "syn_pack_constants_host: buffer %zu < %zu bytes", bytes, need);
     std::vector<float> bb, bs;
     if (has_bb) {
-        if (is_mb1(arch)) pack_backbone_mobilenet1(arch, backbone_flat, bb);
+        if (is_gn(arch)) pack_backbone_ghostnet(backbone_flat, bb);
+        else if (is_mb1(arch)) pack_backbone_mobilenet1(arch, backbone_flat, bb);
         else if (arch == 1) pack_backbone_resnet50(backbone_flat, bb);
         else pack_backbone_mbv2(backbone_flat, bb);
     }
@@ -2128,7 +2477,7 @@ int check_const_header(const ConstHeader &hd, size_t bytes, const char *who) {
     if (hd.version != kConstVersion) return fail(SYN_ERR_INVALID, "%s: constants blob version %u, this library packs version %u", who, hd.version, kConstVersion);
     if (hd.total_bytes > bytes) return fail(SYN_ERR_INVALID, "%s: header says %llu bytes, buffer has %zu", who,
                                             (unsigned long long)hd.total_bytes, bytes);
-    if (hd.has_backbone && (hd.arch > (uint32_t)kArchLast || hd.backbone_floats != backbone_floats((int)hd.arch)))
+    if (hd.has_backbone && (!arch_known((int)hd.arch) || hd.backbone_floats != backbone_floats((int)hd.arch)))
         return fail(SYN_ERR_INVALID, "%s: backbone size mismatch", who);
     if (hd.has_basis && (hd.nvp % 32 || hd.nlp % 32 || hd.n_vert == 0 || hd.n_lmk == 0 || hd.n_vert > hd.nvp || hd.n_lmk > hd.nlp ||
                          hd.nvp - hd.n_vert >= 32 || hd.nlp - hd.n_lmk >= 32 || hd.basis_floats != basis_float_count(hd.nvp, hd.nlp)))
@@ -2338,6 +2687,7 @@ int syn_backbone_forward(syn_handle *h, const float *img, int B, float *param, f
     if (B <= 0) return fail(SYN_ERR_INVALID, "syn_backbone_forward: B=%d", B);
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_backbone_forward: backbone weights not loaded");
     DeviceGuard g(h->device);
+    if (is_gn(h->arch)) return run_ghostnet(h, img, nullptr, B, param, pool, (hipStream_t)stream);
     if (is_mb1(h->arch)) return run_mobilenet1(h, img, nullptr, B, param, pool, (hipStream_t)stream);
     if (h->arch == 1) return run_resnet50(h, img, nullptr, B, param, pool, (hipStream_t)stream);
     return run_backbone(h, img, nullptr, B, param, pool, (hipStream_t)stream);
@@ -2348,6 +2698,7 @@ int syn_backbone_forward_u8(syn_handle *h, const uint8_t *img, int B, float *par
     if (B <= 0) return fail(SYN_ERR_INVALID, "syn_backbone_forward_u8: B=%d", B);
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_backbone_forward_u8: backbone weights not loaded");
     DeviceGuard g(h->device);
+    if (is_gn(h->arch)) return run_ghostnet(h, nullptr, img, B, param, pool, (hipStream_t)stream);
     if (is_mb1(h->arch)) return run_mobilenet1(h, nullptr, img, B, param, pool, (hipStream_t)stream);
     if (h->arch == 1) return run_resnet50(h, nullptr, img, B, param, pool, (hipStream_t)stream);
     return run_backbone(h, nullptr, img, B, param, pool, (hipStream_t)stream);
@@ -2363,6 +2714,24 @@ int syn_backbone_profile(syn_handle *h, const uint8_t *img_hwc, int B, int max_l
     HIP_TRY(hipMalloc((void **)&param, (size_t)B * 62 * sizeof(float)));
     std::vector<hipEvent_t> marks;
     std::vector<int> feats;
+    if (is_gn(h->arch)) {           // launch codes of gn_launch_block in feature_of_launch
+        std::vector<double> fl;
+        int rc = run_ghostnet(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats, &fl);
+        int count = 0;
+        if (rc == SYN_OK) {
+            HIP_TRY(hipDeviceSynchronize());
+            for (size_t i = 1; i < marks.size() && count < max_launches; ++i, ++count) {
+                float ms = 0.f;
+                (void)hipEventElapsedTime(&ms, marks[i - 1], marks[i]);
+                feature_of_launch[count] = feats[i];
+                ms_of_launch[count] = ms;
+                flops_of_launch[count] = fl[i] * B;
+            }
+        }
+        for (hipEvent_t e : marks) (void)hipEventDestroy(e);
+        (void)hipFree(param);
+        return rc == SYN_OK ? count : rc;
+    }
     if (is_mb1(h->arch)) {          // launch codes of run_mobilenet1 in feature_of_launch
         int rc = run_mobilenet1(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats);
         int count = 0;
@@ -2473,6 +2842,37 @@ int syn_mobilenet1_layer(syn_handle *h, int layer, int fused, const void *in, in
     return SYN_OK;
 }
 
+// One block of the loaded GhostNet on caller-supplied activations (include/synergy_hip.h): the launches are those of run_ghostnet
+// (gn_launch_block), the intermediates live in the handle's workspace where run_ghostnet keeps them.  Everything is vetted before a launch.
+int syn_ghostnet_block(syn_handle *h, int block, int fused, const float *in, int B, size_t n_in, float *out, size_t n_out, float *aux,
+                       size_t n_aux, void *stream) {
+    if (!h || !in || !out) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: NULL argument (handle, in and out are required)");
+    if (!is_gn(h->arch)) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: this handle runs %s, expected ghostnet", arch_name(h->arch));
+    if (block < 0 || block > 17) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: block=%d, expected 0..15 (bottlenecks), 16 (ConvBnAct) or 17 (pool + conv_head + heads)", block);
+    if (B < 1 || B > 65536) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: B=%d, expected 1 <= B <= 65536", B);      // 32-bit pixel indices
+    if (fused != 0 && fused != 1) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: fused=%d, expected 0 or 1", fused);
+    const GnNet &n = gnnet();
+    size_t f_in, f_out, f_aux;
+    if (block == 16) { f_in = 16 * 160; f_out = 16 * (size_t)GnNet::kLast; f_aux = 0; }
+    else if (block == 17) { f_in = 16 * (size_t)GnNet::kLast; f_out = 62; f_aux = GnNet::kPool; }
+    else {
+        const GnBlock &b = n.blocks[block];
+        f_in = (size_t)b.hin * b.hin * b.cin; f_out = (size_t)b.hout * b.hout * b.cout; f_aux = b.se ? b.mid : 0;
+    }
+    if (aux && !f_aux) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: aux on block %d, expected NULL (no SE gate and no pool there)", block);
+    if (n_in != f_in * B || n_out != f_out * B || (aux ? n_aux != f_aux * B : n_aux != 0))
+        return fail(SYN_ERR_INVALID, "syn_ghostnet_block: block %d at B=%d expected n_in=%zu n_out=%zu n_aux=%zu, got %zu %zu %zu", block, B, f_in * B,
+                    f_out * B, aux ? f_aux * B : (size_t)0, n_in, n_out, n_aux);
+    if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_ghostnet_block: backbone weights not loaded");
+    DeviceGuard g(h->device);
+    int rc = ensure_ws(h, B);
+    if (rc) return rc;
+    const GnWs w = gn_ws(n, h->ws + 2 * (size_t)B * n.buf_io, B);
+    gn_launch_block(n, h->d_backbone, block, fused != 0, in, B, out, aux, w, (hipStream_t)stream, [](int, double) {});
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 // Profiling hook, not part of include/synergy_hip.h: runs the backbone with the fused block of
 // .features[feature] instrumented; out8 (host) = summed s_memtime ticks of wave 0 per stage
 // {stage0, expand, barrier, depthwise, barrier, project, epilogue} and the workgroup count.
@@ -2480,7 +2880,7 @@ int syn_mobilenet1_layer(syn_handle *h, int layer, int fused, const void *in, in
 int syn_debug_profile_block(syn_handle *h, const float *img, int B, int feature, unsigned long long *out8) {
     if (!h || !img || !out8 || B <= 0) return fail(SYN_ERR_INVALID, "syn_debug_profile_block: bad argument");
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_debug_profile_block: backbone weights not loaded");
-    if (is_mb1(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_profile_block: this handle runs %s", arch_name(h->arch));
+    if (is_mb1(h->arch) || is_gn(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_profile_block: this handle runs %s", arch_name(h->arch));
     DeviceGuard g(h->device);
     unsigned long long *d = nullptr;
     HIP_TRY(hipMalloc((void **)&d, 32 * sizeof(unsigned long long)));
@@ -2501,7 +2901,7 @@ int syn_debug_profile_block(syn_handle *h, const float *img, int B, int feature,
 int syn_debug_feature(syn_handle *h, const float *img, int B, int feature, float *out, void *stream) {
     if (!h || !img || !out || B <= 0 || feature < 0 || feature > 18) return fail(SYN_ERR_INVALID, "syn_debug_feature: bad argument");
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_debug_feature: backbone weights not loaded");
-    if (is_mb1(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_feature: this handle runs %s", arch_name(h->arch));
+    if (is_mb1(h->arch) || is_gn(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_feature: this handle runs %s", arch_name(h->arch));
     DeviceGuard g(h->device);
     return run_backbone(h, img, nullptr, B, nullptr, nullptr, (hipStream_t)stream, feature, out);
 }
@@ -3428,8 +3828,8 @@ syn::SynTrunkW trunk_weights(const syn_handle *h, int which) {
 }
 
 int synergy_ready(const syn_handle *h, const char *who) {
-    if (h->arch != 0)
-        return fail(SYN_ERR_INVALID, "%s: the synergy refinement needs the 1280-d pooled feature of mobilenet_v2; this handle runs %s (%d-d)", who,
+    if (h->arch != 0 && !is_gn(h->arch))          // ghostnet's pooled feature (the 1280 outputs of conv_head + ReLU) has the same width
+        return fail(SYN_ERR_INVALID, "%s: the synergy refinement needs the 1280-d pooled feature of mobilenet_v2 or ghostnet; this handle runs %s (%d-d)", who,
                     arch_name(h->arch), is_mb1(h->arch) ? mb1net(h->arch).pool : 2048);
     if (!h->d_syn) return fail(SYN_ERR_NOT_LOADED, "%s: synergy weights not loaded (syn_load_synergy)", who);
     return SYN_OK;

@@ -66,9 +66,9 @@ def pack_constants_host(pack=None, backbone_state=None, arch: str = 'mobilenet_v
 
     from . import abi
     from .params import ParamsPack
-    from .synergy3DMM import ARCH_NAMES, flatten_backbone
+    from .synergy3DMM import ARCH_IDS, flatten_backbone
     lib = abi.lib()
-    a = ARCH_NAMES.index(arch)
+    a = ARCH_IDS[arch]
     flat = None
     if backbone_state is not None:
         sd = {k: v for k, v in backbone_state.items() if not k.endswith('num_batches_tracked')}

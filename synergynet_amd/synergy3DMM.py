@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from . import abi
 from .params import ParamsPack
-from .synth import HEADS, MOBILENET1_HEADS, RESNET_HEADS, mbv2_layers, mobilenet1_blocks, resnet50_convs
+from .synth import GHOSTNET_HEADS, HEADS, MOBILENET1_HEADS, RESNET_HEADS, ghostnet_blocks, mbv2_layers, mobilenet1_blocks, resnet50_convs
 
 BACKBONE_PREFIX = 'I2P.backbone.'
 _BASIS_BUFFERS = ('param_mean', 'param_std', 'w_shp', 'u', 'w_exp', 'u_base', 'w_shp_base', 'w_exp_base')
@@ -44,8 +44,11 @@ def parse_param_62(param):
     return p, offset, alpha_shp, alpha_exp
 
 
-# backbone ids of the C ABI (include/synergy_hip.h; the `arch` word of the constants header), by position
-ARCH_NAMES = ('mobilenet_v2', 'resnet50', 'mobilenet_1', 'mobilenet_05', 'mobilenet_2')
+# backbone ids of the C ABI (include/synergy_hip.h; the `arch` word of the constants header).  5: never assigned.
+ARCH_IDS = {'mobilenet_v2': 0, 'resnet50': 1, 'mobilenet_1': 2, 'mobilenet_05': 3, 'mobilenet_2': 4, 'ghostnet': 6}
+ARCH_BY_ID = {i: n for n, i in ARCH_IDS.items()}
+ARCH_NAMES = ('mobilenet_v2', 'resnet50', 'mobilenet_1', 'mobilenet_05', 'mobilenet_2')      # ids 0..4 by position (kept for callers that index it)
+_ARCH_CHOICES = ('mobilenet_v2', 'resnet50', 'ghostnet', 'mobilenet_1', 'mobilenet_05', 'mobilenet_2')      # as the refusal message lists them
 MOBILENET1_WIDTHS = {'mobilenet_1': 1.0, 'mobilenet_05': 0.5, 'mobilenet_2': 2.0}      # the widths whose channel counts are all multiples of 16
 
 _HDR_MAGIC = 0x53594e4833353558          # "SYNH355X" (csrc/synergy_abi.hip ConstHeader)
@@ -62,7 +65,7 @@ def parse_constants_header(raw: bytes) -> dict:
     magic, version, has_bb, has_basis, n_vert, n_lmk, nvp, nlp, arch, bb_fl, basis_fl, total = struct.unpack_from('<Q8I3Q', raw, 0)
     if magic != _HDR_MAGIC or version != _HDR_VERSION:
         raise ValueError('constants blob: bad magic/version')
-    if has_bb and arch >= len(ARCH_NAMES):
+    if has_bb and arch not in ARCH_BY_ID:
         raise ValueError(f'constants blob: unknown backbone arch {arch}')
     if has_basis and not (0 < n_vert <= nvp and 0 < n_lmk <= nlp and nvp % 32 == 0 and nlp % 32 == 0):
         raise ValueError('constants blob: inconsistent basis sizes')
@@ -122,17 +125,62 @@ def mobilenet1_keys(width: float = 1.0):
     return out
 
 
+def ghostnet_keys():
+    """(state_dict key, shape) of every GhostNet tensor in the module's own state_dict() order (num_batches_tracked left out): the
+    order syn_load_backbone_ghostnet expects.  Written from the block table (synth.ghostnet_blocks), not from the module."""
+    bn = ('weight', 'bias', 'running_mean', 'running_var')
+    out = []
+
+    def conv_bn(conv, norm, shape):
+        out.append((conv + '.weight', shape))
+        out.extend((norm + '.' + s, (shape[0],)) for s in bn)
+
+    def ghost(key, cin, cout):
+        assert cout % 2 == 0, f'{key}: GhostModule({cin} -> {cout}) with an odd width: the [:, :oup] slice would drop a channel'
+        conv_bn(key + '.primary_conv.0', key + '.primary_conv.1', (cout // 2, cin, 1, 1))
+        conv_bn(key + '.cheap_operation.0', key + '.cheap_operation.1', (cout // 2, 1, 3, 3))
+
+    conv_bn('conv_stem', 'bn1', (16, 3, 3, 3))
+    for key, cin, mid, cout, k, stride, se in ghostnet_blocks():
+        ghost(key + '.ghost1', cin, mid)
+        if stride == 2:
+            conv_bn(key + '.conv_dw', key + '.bn_dw', (mid, 1, k, k))
+        if se:
+            out += [(key + '.se.conv_reduce.weight', (se, mid, 1, 1)), (key + '.se.conv_reduce.bias', (se,)),
+                    (key + '.se.conv_expand.weight', (mid, se, 1, 1)), (key + '.se.conv_expand.bias', (mid,))]
+        ghost(key + '.ghost2', mid, cout)
+        if cin != cout or stride != 1:
+            conv_bn(key + '.shortcut.0', key + '.shortcut.1', (cin, 1, k, k))
+            conv_bn(key + '.shortcut.2', key + '.shortcut.3', (cout, cin, 1, 1))
+    conv_bn('blocks.9.0.conv', 'blocks.9.0.bn1', (960, 160, 1, 1))
+    out += [('conv_head.weight', (1280, 960, 1, 1)), ('conv_head.bias', (1280,))]
+    for name, n in GHOSTNET_HEADS:
+        out += [(name + '.weight', (n, 1280)), (name + '.bias', (n,))]
+    return out
+
+
 def arch_keys(arch: str):
     """The (key, shape) table of a backbone by name."""
+    if arch == 'ghostnet':
+        return ghostnet_keys()
     if arch in MOBILENET1_WIDTHS:
         return mobilenet1_keys(MOBILENET1_WIDTHS[arch])
     return resnet50_keys() if arch == 'resnet50' else backbone_keys()
 
 
 def flatten_backbone(sd: dict, prefix: str = '', arch: str = 'mobilenet_v2') -> np.ndarray:
-    """state_dict -> the flat fp32 host array of syn_load_backbone[_resnet50 | _mobilenet1] (include/synergy_hip.h)."""
+    """state_dict -> the flat fp32 host array of syn_load_backbone[_resnet50 | _mobilenet1 | _ghostnet] (include/synergy_hip.h).
+    For ghostnet the keys under `prefix` must be exactly the module's: a missing or an unexpected key is refused, like a wrong shape."""
     parts = []
-    for k, shape in arch_keys(arch):
+    table = arch_keys(arch)
+    if arch == 'ghostnet':          # strict: exactly the module's tensors
+        have = {k[len(prefix):] for k in sd if k.startswith(prefix) and not k.endswith('num_batches_tracked')}
+        want = {k for k, _ in table}
+        if have - want:
+            raise RuntimeError(f'ghostnet state_dict: unexpected keys {sorted(have - want)[:4]}')
+        if want - have:
+            raise RuntimeError(f'ghostnet state_dict: missing keys {sorted(want - have)[:4]}')
+    for k, shape in table:
         v = sd[prefix + k]
         v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
         if tuple(v.shape) != tuple(shape):
@@ -192,10 +240,12 @@ class SynergyNet(nn.Module):
         """arch: 'mobilenet_v2' (the reference's hard-coded choice, synergy3DMM.py:76) or 'resnet50' (BASELINE
         config 5; the reference's own wrapper cannot run it -- SURVEY F6 -- so the first 62 of ResNet's 102
         outputs are taken, the adapter a maintainer would add), or the MobileNetV1 family 'mobilenet_1' / 'mobilenet_05' /
-        'mobilenet_2' (main_train.py --arch mobilenet_1; the same [:, :62] adapter, pool_dim = 1024 x width)."""
+        'mobilenet_2' (main_train.py --arch mobilenet_1; the same [:, :62] adapter, pool_dim = 1024 x width), or 'ghostnet'
+        (main_train.py --arch ghostnet; the reference's module returns only the [B,102] tensor, so its own wrapper cannot run it: here the
+        pooled feature is the 1280-vector after conv_head + ReLU that the heads consume, and the synergy refinement accepts it)."""
         super().__init__()
-        if arch not in ARCH_NAMES:
-            raise RuntimeError(f"Please choose [{', '.join(ARCH_NAMES)}]")
+        if arch not in ARCH_IDS:
+            raise RuntimeError(f"Please choose [{', '.join(_ARCH_CHOICES)}]")
         self.arch = arch
         if not torch.cuda.is_available():
             raise RuntimeError('synergynet_amd.SynergyNet needs a ROCm GPU (MI355X); there is no CPU path')
@@ -286,8 +336,11 @@ class SynergyNet(nn.Module):
 
     def _upload_backbone(self):
         flat = flatten_backbone(self.state_dict(), BACKBONE_PREFIX, self.arch)
-        if self.arch in MOBILENET1_WIDTHS:
-            a = ARCH_NAMES.index(self.arch)
+        if self.arch == 'ghostnet':
+            assert flat.size == self._lib.syn_ghostnet_flat_count()
+            abi.check(self._lib.syn_load_backbone_ghostnet(self._h, flat.ctypes.data_as(C.c_void_p), flat.size))
+        elif self.arch in MOBILENET1_WIDTHS:
+            a = ARCH_IDS[self.arch]
             assert flat.size == self._lib.syn_mobilenet1_flat_count(a)
             abi.check(self._lib.syn_load_backbone_mobilenet1(self._h, a, flat.ctypes.data_as(C.c_void_p), flat.size))
         elif self.arch == 'resnet50':
@@ -448,7 +501,7 @@ class SynergyNet(nn.Module):
     def _follow_constants(self, hdr):
         if hdr['has_backbone']:
             # the blob decides which backbone the C handle now runs: follow it, or pool buffers would be sized for the wrong one
-            self.arch = ARCH_NAMES[hdr['arch']]
+            self.arch = ARCH_BY_ID[hdr['arch']]
             self._have_backbone = True
             self._range_checked = False
             self._range_events = 0          # the C side starts counting from 0 again on an import (a stale count here hid the next warning)
@@ -606,8 +659,8 @@ class SynergyNet(nn.Module):
 
     # ------------------------------------------------------------------ synergy refinement (MLP_for / MLP_rev)
     def _need_synergy(self):
-        if self.arch != 'mobilenet_v2':
-            raise RuntimeError(f'the synergy refinement needs the 1280-d pooled feature of mobilenet_v2; arch={self.arch} pools {self.pool_dim}')
+        if self.arch not in ('mobilenet_v2', 'ghostnet'):
+            raise RuntimeError(f'the synergy refinement needs the 1280-d pooled feature of mobilenet_v2 or ghostnet; arch={self.arch} pools {self.pool_dim}')
         if not self.has_synergy:
             raise RuntimeError('synergy weights not loaded: the checkpoint carried no forwardDirection.* / reverseDirection.* keys '
                                '(load_synergy_state)')

@@ -225,6 +225,74 @@ def make_mobilenet1_state(seed: int = 1357, width: float = 1.0) -> dict:
     return sd
 
 
+def ghostnet_blocks():
+    """Ordered (key, in, mid, out, k, stride, se) of the 16 GhostBottlenecks of the reference GhostNet at width 1.0
+    (backbone_nets/ghostnet_backbone.py:240-265 through _make_divisible(., 4)); se = the reduced channels of the squeeze-and-excite,
+    0 where the block has none.  At 120x120 the stem gives 60^2 and the stride-2 blocks 1.0, 3.0, 5.0, 7.0 give 30^2, 15^2, 8^2, 4^2."""
+    return [('blocks.0.0', 16, 16, 16, 3, 1, 0), ('blocks.1.0', 16, 48, 24, 3, 2, 0), ('blocks.2.0', 24, 72, 24, 3, 1, 0),
+            ('blocks.3.0', 24, 72, 40, 5, 2, 20), ('blocks.4.0', 40, 120, 40, 5, 1, 32), ('blocks.5.0', 40, 240, 80, 3, 2, 0),
+            ('blocks.6.0', 80, 200, 80, 3, 1, 0), ('blocks.6.1', 80, 184, 80, 3, 1, 0), ('blocks.6.2', 80, 184, 80, 3, 1, 0),
+            ('blocks.6.3', 80, 480, 112, 3, 1, 120), ('blocks.6.4', 112, 672, 112, 3, 1, 168), ('blocks.7.0', 112, 672, 160, 5, 2, 168),
+            ('blocks.8.0', 160, 960, 160, 5, 1, 0), ('blocks.8.1', 160, 960, 160, 5, 1, 240), ('blocks.8.2', 160, 960, 160, 5, 1, 0),
+            ('blocks.8.3', 160, 960, 160, 5, 1, 240)]
+
+
+GHOSTNET_HEADS = [('classifier_ori', 12), ('classifier_shape', 40), ('classifier_exp', 10), ('classifier_texture', 40)]      # module order = cat order
+
+
+def make_ghostnet_state(seed: int = 2031) -> dict:
+    """GhostNet state_dict (numpy fp32, reference key names).  Conv weights N(0, g / fan_in) with g = 2 in front of a ReLU and 1
+    elsewhere (ghost2, shortcuts, SE, the stride-2 conv_dw); BN gamma U(0.8, 1.2) but U(0.3, 0.6) in ghost2, so the residual sums do
+    not grow; beta, running_mean 0.1 N; running_var U(0.8, 1.25); conv biases 0.1 N; heads 0.02 N, head biases 0.1 N.  Block outputs
+    stay below ~6.5, about half of the pooled features are non-zero and the SE gates sit inside (0.05, 0.95)."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+
+    def conv(key, shape, g, bias=False):
+        fan_in = shape[1] * shape[2] * shape[3]
+        sd[key + '.weight'] = (rng.standard_normal(shape) * np.sqrt(g / fan_in)).astype(np.float32)
+        if bias:
+            sd[key + '.bias'] = (rng.standard_normal(shape[0]) * 0.1).astype(np.float32)
+
+    def bn(key, c, lo=0.8, hi=1.2):
+        sd[key + '.weight'] = rng.uniform(lo, hi, c).astype(np.float32)
+        sd[key + '.bias'] = (rng.standard_normal(c) * 0.1).astype(np.float32)
+        sd[key + '.running_mean'] = (rng.standard_normal(c) * 0.1).astype(np.float32)
+        sd[key + '.running_var'] = rng.uniform(0.8, 1.25, c).astype(np.float32)
+        sd[key + '.num_batches_tracked'] = np.array(1000, dtype=np.int64)
+
+    def ghost(key, cin, cout, relu):
+        g, (lo, hi) = (2.0, (0.8, 1.2)) if relu else (1.0, (0.3, 0.6))
+        conv(key + '.primary_conv.0', (cout // 2, cin, 1, 1), g)
+        bn(key + '.primary_conv.1', cout // 2, lo, hi)
+        conv(key + '.cheap_operation.0', (cout // 2, 1, 3, 3), g)
+        bn(key + '.cheap_operation.1', cout // 2, lo, hi)
+
+    conv('conv_stem', (16, 3, 3, 3), 2.0)
+    bn('bn1', 16)
+    for key, cin, mid, cout, k, stride, se in ghostnet_blocks():
+        ghost(key + '.ghost1', cin, mid, True)
+        if stride == 2:
+            conv(key + '.conv_dw', (mid, 1, k, k), 1.0)
+            bn(key + '.bn_dw', mid)
+        if se:
+            conv(key + '.se.conv_reduce', (se, mid, 1, 1), 1.0, bias=True)
+            conv(key + '.se.conv_expand', (mid, se, 1, 1), 1.0, bias=True)
+        ghost(key + '.ghost2', mid, cout, False)
+        if cin != cout or stride != 1:
+            conv(key + '.shortcut.0', (cin, 1, k, k), 1.0)
+            bn(key + '.shortcut.1', cin)
+            conv(key + '.shortcut.2', (cout, cin, 1, 1), 1.0)
+            bn(key + '.shortcut.3', cout)
+    conv('blocks.9.0.conv', (960, 160, 1, 1), 2.0)
+    bn('blocks.9.0.bn1', 960)
+    conv('conv_head', (1280, 960, 1, 1), 2.0, bias=True)
+    for name, n in GHOSTNET_HEADS:
+        sd[name + '.weight'] = (rng.standard_normal((n, 1280)) * 0.02).astype(np.float32)
+        sd[name + '.bias'] = (rng.standard_normal(n) * 0.1).astype(np.float32)
+    return sd
+
+
 def _rotation(yaw, pitch, roll):
     cy, sy = np.cos(yaw), np.sin(yaw)
     cp, sp = np.cos(pitch), np.sin(pitch)
