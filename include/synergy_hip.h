@@ -156,6 +156,25 @@ size_t syn_ghostnet_flat_count(void);
 double syn_ghostnet_flops_per_face(void);
 int syn_load_backbone_ghostnet(syn_handle *h, const float *flat, size_t n_floats);
 
+/* The ResNeSt-50 backbone (reference backbone_nets/ResNeSt/resnest.py:33-41, resnet.py, splat.py; `--arch resnest50` of main_train.py:
+ * radix 2, cardinality 1, deep stem of width 32, avg_down, avd after the split-attention convolution).  Backbone id 8.  The whole id table:
+ *   0 mobilenet_v2 | 1 resnet50 | 2 mobilenet_1 | 3 mobilenet_05 | 4 mobilenet_2 | 5: never assigned | 6 ghostnet | 7: never assigned | 8 resnest50
+ * `flat` = the module's state_dict() order without num_batches_tracked (synergynet_amd.synergy3DMM.resnest50_keys): conv1.0.weight,
+ * conv1.1.*, conv1.3.weight, conv1.4.*, conv1.6.weight, bn1.*, then per bottleneck layerL.I: conv1.weight, bn1.*, conv2.conv.weight,
+ * conv2.bn0.*, conv2.fc1.{weight,bias}, conv2.bn1.*, conv2.fc2.{weight,bias}, conv3.weight, bn3.*, [downsample.1.weight, downsample.2.*
+ * when I == 0]; fc_ori / fc_shape / fc_exp / fc_tex {weight, bias}.  fc_tex is KEPT in flat, so a checkpoint flattens as it is:
+ * 25 707 814 floats; the module never calls it and it is not packed.  BatchNorm is folded on the host in fp32 (eps 1e-5).
+ * After loading, syn_backbone_forward[_u8] run this network, every product exact fp32 (fp32-input MFMA; means, gate, softmax and pools in
+ * fp32 VALU in a fixed order): syn_numerics_report has nothing to prove, syn_backbone_range_status / _calibrate return 0.  param = the
+ * module's 62 outputs (ori 12 | shape 40 | exp 10), pool = the 2048 channel means: not 1280 wide, so syn_refine_landmarks refuses this arch.
+ * SYNERGY_HIP_FUSION / syn_set_schedule(h, .): 0 = per-layer (95 launches: the split-attention sum, its 3x3 / 2 average and the
+ * downsample's 2x2 / 2 average are stored, one launch each); 1 = fused (74 launches: conv3, and the downsample convolution of layer2.0 /
+ * 3.0, build those operands once per workgroup in LDS; they never reach HBM); 2 (default) = as 1.  The schedules are bit-identical.
+ * syn_resnest50_flops_per_face = 2 x 1 637 330 432 MAC: every product of the module's forward (Conv2d and Linear; fc_tex never runs). */
+size_t syn_resnest50_flat_count(void);
+double syn_resnest50_flops_per_face(void);
+int syn_load_backbone_resnest50(syn_handle *h, const float *flat, size_t n_floats);
+
 /* ParamsPack (utils/params.py:10-35) + the register_buffer block (synergy3DMM.py:95-105).
  * HOST arrays: w_shp [3*n_vert,40], w_exp [3*n_vert,10], u [3*n_vert] (= u_shp+u_exp),
  * param_mean/param_std [>=62] (first 62 used), keypoints [3*n_lmk] flat indices into the
@@ -191,7 +210,7 @@ int syn_describe_constants(syn_handle *h, void *host_header, size_t bytes);
 /* Device-free twins of the hand-off: neither makes a HIP call, so a loader process (or a test) without a GPU can produce and
  * vet the blob.  syn_pack_constants_host writes, from HOST arrays (same meaning as syn_load_backbone / _resnet50 / syn_load_basis;
  * backbone_flat or the whole basis group may be NULL), exactly the bytes syn_export_constants produces after the same loads;
- * arch 0 = mobilenet_v2, 1 = resnet50, 2 / 3 / 4 = mobilenet_1 / _05 / _2, 6 = ghostnet (5 was never assigned and is refused).  syn_check_constants_host applies syn_import_constants' acceptance checks (magic, version,
+ * arch 0 = mobilenet_v2, 1 = resnet50, 2 / 3 / 4 = mobilenet_1 / _05 / _2, 6 = ghostnet, 8 = resnest50 (5 and 7 were never assigned and are refused).  syn_check_constants_host applies syn_import_constants' acceptance checks (magic, version,
  * sizes vs this library's network tables, payload within the buffer) to a host copy of a blob. */
 size_t syn_pack_constants_host_bytes(int arch, int have_backbone, int n_vert, int n_lmk);
 int syn_pack_constants_host(int arch, const float *backbone_flat, size_t n_floats, const float *w_shp, const float *w_exp,
@@ -590,6 +609,20 @@ int syn_mobilenet1_layer(syn_handle *h, int layer, int fused, const void *in, in
  * pointers are device pointers; the block's intermediates live in the handle's workspace (one stream at a time, as the forward). */
 int syn_ghostnet_block(syn_handle *h, int block, int fused, const float *in_nhwc, int B, size_t n_in,
                        float *out, size_t n_out, float *aux, size_t n_aux, void *stream);
+
+/* One block of the loaded ResNeSt-50 (arch 8) on activations the caller supplies, through exactly the launches the forward uses for that
+ * block (one helper derives the launch arguments for both) -- the hook tests/test_gpu_resnest.py judges every block with.
+ *   block 0      stem (three 3x3 convolutions) + max pool: in = normalised fp32 crops [B,120,120,3] (HWC), out = [B,30,30,64]
+ *   block 1..16  bottlenecks layer1.0 .. layer4.2: in = NHWC fp32 [B,hin,hin,cin], out = [B,hout,hout,4C]; a non-NULL aux receives the
+ *                attention [B,2C] in fc2's order (radix half 0 | radix half 1)
+ *   block 17     pool + heads: in = [B,4,4,2048], out = [B,62], a non-NULL aux receives the pool [B,2048]
+ * fused = 1: conv3 (and the downsample convolution of layer2.0 / 3.0) build their operands in LDS; fused = 0: one launch per layer.
+ * n_in / n_out / n_aux are ELEMENT counts (n_aux = 0 when aux is NULL).  Refused with SYN_ERR_INVALID and a message that names what was
+ * expected, before any launch, with `out` untouched: a count that differs from what the block needs, a handle whose arch is not
+ * resnest50, block outside 0..17, B < 1 or B > 65536, fused other than 0 / 1, aux on block 0.  Asynchronous on `stream`; all pointers
+ * are device pointers; the block's intermediates live in the handle's workspace (one stream at a time, as the forward). */
+int syn_resnest50_block(syn_handle *h, int block, int fused, const float *in_nhwc, int B, size_t n_in,
+                        float *out, size_t n_out, float *aux, size_t n_aux, void *stream);
 
 /* The dense reconstruction (transform = 1) into a pitched output with HIP events around its kernels, on the default stream;
  * synchronises.  ms2[0] = per-face prologue, ms2[1] = the contraction + pose epilogue + mesh stores -- the HBM-write-bound kernel

@@ -48,6 +48,9 @@ _SIGS = {
     'syn_ghostnet_flat_count': (C.c_size_t, []),
     'syn_ghostnet_flops_per_face': (C.c_double, []),
     'syn_load_backbone_ghostnet': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    'syn_resnest50_flat_count': (C.c_size_t, []),
+    'syn_resnest50_flops_per_face': (C.c_double, []),
+    'syn_load_backbone_resnest50': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     'syn_load_basis': (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int, C.c_int]),
     'syn_constants_bytes': (C.c_size_t, [C.c_void_p]),
     'syn_export_constants': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -111,6 +114,8 @@ _SIGS = {
                                        C.c_size_t, C.c_void_p]),
     'syn_ghostnet_block': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
+    'syn_resnest50_block': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
     'syn_reconstruct_profile': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'syn_backbone_flops_per_face': (C.c_double, []),
     'syn_pointwise_flops_per_face': (C.c_double, []),

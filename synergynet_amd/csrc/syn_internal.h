@@ -281,6 +281,33 @@ void launch_gn_ghost(const float *X, int ldx, const float *gate, const float *Wp
                      const float *Wd, const float *d_scale, const float *d_shift, const float *res, int ldr, float *Y, int B, int H,
                      int K, int N1, int relu, hipStream_t s);
 
+// ---- ResNeSt-50 (resnest_kernels.hip): every product exact fp32; K % 16 == 0, N % 32 == 0 ----
+// the pixel operand of launch_rs_gemm: a stored tensor | att0 U0 + att1 U1 | its 3x3 / 2 pad-1 average (/ 9) | the 2x2 / 2 ceil-mode
+// average of a stored tensor (divisor = samples inside)
+enum RsOp { kRsPlain = 0, kRsCombine = 1, kRsAvd = 2, kRsDsPool = 3 };
+// stem convolution 1 (3x3 / 2, 3 -> 32) + BN + ReLU -> NHWC [B,60,60,32]: uint8 HWC crops (normalised inside) or fp32 crops, NCHW
+// (img_hwc == 0) or HWC; w [27][32] (row ci*9 + ky*3 + kx)
+void launch_rs_stem(const float *img, const uint8_t *img_hwc_u8, int img_hwc, const float *w, const float *scale, const float *shift,
+                    float *out, int B, hipStream_t s);
+// Y [B,Ho,Ho,N] = act(scale * (op . W^T) + shift (+ res [B,Ho,Ho,N])); W [N][K].  kRsPlain: A rows of pitch lda; kRsCombine: A = U
+// [B,Ho,Ho,2K]; kRsAvd: A = U [B,Hin,Hin,2K]; kRsDsPool: A = X [B,Hin,Hin,K]; att [B][2K] (combine and avd only).  The three built
+// operands go through an LDS tile and need rs_tail_exists(K, N) (K <= 512: the downsample of layer4.0, K = 1024, has no fused launch)
+bool rs_tail_exists(int K, int N);
+constexpr int kRsTailGroups = 1024;      // the fused tail splits its channels over workgroups until the grid has this many (4 per CU)
+void launch_rs_gemm(int op, const float *A, int lda, const float *att, const float *W, const float *scale, const float *shift,
+                    const float *res, float *Y, int B, int Hin, int Ho, int K, int N, int relu, hipStream_t s);
+// 3x3 / 1 pad 1, `groups` groups, + BN + ReLU: X [B,H,H] rows of pitch ldx (group q reads channels q Cg ..), W [groups Ng][9][Cg]
+// tap-major, Y [B,H,H,groups Ng]
+void launch_rs_conv3x3(const float *X, int ldx, const float *W, const float *scale, const float *shift, float *Y, int B, int H, int Cg,
+                       int Ng, int groups, hipStream_t s);
+// the split-attention gate: U [B,HW,2C] -> att [B][2C]; W1t [C][I], s1 / h1 [I] (BN folded with fc1's bias), W2t [I][2C], b2 [2C]
+void launch_rs_gate(const float *U, const float *W1t, const float *s1, const float *h1, const float *W2t, const float *b2, float *att,
+                    int B, int HW, int C, int I, hipStream_t s);
+// the per-layer schedule's stored operands: V = att0 U0 + att1 U1 [B,HW,C]; the avd pool of V; the downsample pool of X
+void launch_rs_combine(const float *U, const float *att, float *V, int B, int HW, int C, hipStream_t s);
+void launch_rs_avd(const float *V, float *out, int B, int Hin, int Ho, int C, hipStream_t s);
+void launch_rs_dspool(const float *X, float *out, int B, int Hin, int Ho, int C, hipStream_t s);
+
 // ---- reconstruction -----------------------------------------------------------------
 // basis: pre-packed per 32-vertex tile in MFMA-operand lane order (see recon_kernels.hip):
 //   Bp[tile][coord x|y|z][chunk][lane][4], K = 52: 0..39 shape, 40..49 expression,

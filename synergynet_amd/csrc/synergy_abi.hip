@@ -279,10 +279,12 @@ const ResNet50 &resnet50() {
 // (include/synergy_hip.h); widths 0.25 and 0.75 give 8 / 24 channels, no multiple of the 16-wide MFMA tile, and are not offered.
 constexpr int kArchMb1First = 2, kArchLast = 4;
 bool is_mb1(int arch) { return arch >= kArchMb1First && arch <= kArchLast; }
-// The whole id table: 0 mobilenet_v2 | 1 resnet50 | 2 mobilenet_1 | 3 mobilenet_05 | 4 mobilenet_2 | 5: never assigned | 6 ghostnet.
-constexpr int kArchGhost = 6;
+// The whole id table: 0 mobilenet_v2 | 1 resnet50 | 2 mobilenet_1 | 3 mobilenet_05 | 4 mobilenet_2 | 5: never assigned | 6 ghostnet |
+// 7: never assigned | 8 resnest50.
+constexpr int kArchGhost = 6, kArchResnest = 8;
 bool is_gn(int arch) { return arch == kArchGhost; }
-bool arch_known(int arch) { return (arch >= 0 && arch <= kArchLast) || arch == kArchGhost; }
+bool is_rs(int arch) { return arch == kArchResnest; }
+bool arch_known(int arch) { return (arch >= 0 && arch <= kArchLast) || arch == kArchGhost || arch == kArchResnest; }
 const char *arch_name(int arch) {
     switch (arch) {
     case 0: return "mobilenet_v2";
@@ -291,6 +293,7 @@ const char *arch_name(int arch) {
     case 3: return "mobilenet_05";
     case 4: return "mobilenet_2";
     case kArchGhost: return "ghostnet";
+    case kArchResnest: return "resnest50";
     default: return "?";
     }
 }
@@ -461,6 +464,104 @@ const GnNet &gnnet() {
     return n;
 }
 
+// ---- ResNeSt-50 (reference backbone_nets/ResNeSt/resnest.py:33-41, resnet.py:29-324, splat.py:11-98), arch id 8.  Deep stem (three 3x3
+// convolutions 3 -> 32 / 2, 32 -> 32, 32 -> 64), bn1 + ReLU, max pool, 3 + 4 + 6 + 3 bottlenecks of group width C = 64 / 128 / 256 / 512,
+// global mean, four heads.  A bottleneck: conv1 1x1 -> C, conv2.conv 3x3 groups 2 -> 2C = U, the split-attention gate, V = att0 U0 +
+// att1 U1, [3x3 / 2 average on layerN.0, N >= 2], conv3 1x1 -> 4C, + residual ([2x2 / 2 ceil-mode average], 1x1, BN on layerN.0), ReLU.
+struct RsConv { int cin = 0, cout = 0; size_t src = 0, dst_w = 0, dst_scale = 0, dst_shift = 0; };      // flat: weight [cout][cin(,1,1)], bn x4
+struct RsConv3 { int cg = 0, ng = 0, groups = 1; size_t src = 0, dst_w = 0, dst_scale = 0, dst_shift = 0; };   // flat: weight [groups ng][cg][3][3], bn x4; packed [n][9][cg]
+struct RsBlock {
+    int cin, C, cout, inter, hin, hout;
+    bool avd, down;                                            // the 3x3 / 2 average (and the 2x2 / 2 downsample pool); a downsample branch
+    RsConv c1, c3, ds;
+    RsConv3 c2;
+    size_t src_fc = 0, dst_w1t = 0, dst_s1 = 0, dst_h1 = 0, dst_w2t = 0, dst_b2 = 0;      // flat: fc1 {weight [I][C], bias}, bn1 x4, fc2 {weight [2C][I], bias}
+    // per-face floats of the block's intermediates: conv1 output, U, V, the pooled V, the pooled input, the downsample output
+    size_t n_t1() const { return (size_t)hin * hin * C; }
+    size_t n_u() const { return 2 * n_t1(); }
+    size_t n_pa() const { return avd ? (size_t)hout * hout * C : 0; }
+    size_t n_pd() const { return avd ? (size_t)hout * hout * cin : 0; }
+    size_t n_r() const { return down ? (size_t)hout * hout * cout : 0; }
+    size_t scratch() const { return 2 * n_t1() + n_u() + n_pa() + n_pd() + n_r() + 2 * (size_t)C; }
+};
+struct RsNet {
+    static constexpr int kBlocks = 16, kStem = 32, kPool = 2048;
+    std::vector<RsBlock> blocks;
+    RsConv3 stem2, stem3;
+    size_t flat_count = 0, packed_count = 0, dst_stem_w = 0, dst_stem_scale = 0, dst_stem_shift = 0, src_fc = 0, dst_fc_w = 0, dst_fc_b = 0;
+    size_t buf_io = 0, buf_scratch = 0;                        // per-face floats: block input / output (x 2), a block's intermediates
+    double macs = 0, flops = 0;
+    size_t ws_per_face() const { return 2 * buf_io + buf_scratch; }
+    RsNet() {
+        static const int layers[4][2] = {{64, 3}, {128, 4}, {256, 6}, {512, 3}};      // group width, blocks
+        size_t src = 0, dst = 0;
+        auto conv = [&](int cin, int cout, int hw) {
+            RsConv c; c.cin = cin; c.cout = cout;
+            c.src = src; src += (size_t)cout * cin + 4 * (size_t)cout;
+            c.dst_w = dst; dst += (size_t)cout * cin;
+            c.dst_scale = dst; dst += cout;
+            c.dst_shift = dst; dst += cout;
+            macs += (double)cin * cout * hw;
+            return c;
+        };
+        auto conv3 = [&](int cg, int ng, int groups, int hw) {
+            RsConv3 c; c.cg = cg; c.ng = ng; c.groups = groups;
+            const size_t nw = (size_t)groups * ng * cg * 9, n = (size_t)groups * ng;
+            c.src = src; src += nw + 4 * n;
+            c.dst_w = dst; dst += nw;
+            c.dst_scale = dst; dst += n;
+            c.dst_shift = dst; dst += n;
+            macs += (double)nw * hw;
+            return c;
+        };
+        auto up = [](size_t &m, size_t v) { m = v > m ? v : m; };
+        src += (size_t)kStem * 27 + 4 * (size_t)kStem;
+        dst_stem_w = dst; dst += (size_t)27 * kStem;
+        dst_stem_scale = dst; dst += kStem;
+        dst_stem_shift = dst; dst += kStem;
+        macs = 27.0 * kStem * 3600;
+        stem2 = conv3(kStem, kStem, 1, 3600);
+        stem3 = conv3(kStem, 2 * kStem, 1, 3600);              // its BatchNorm is the model's bn1
+        buf_io = (size_t)2 * kStem * 3600;
+        buf_scratch = (size_t)2 * kStem * 3600 + 2 * (size_t)kStem * 3600;      // the stem: conv1, conv2 and conv3 outputs
+        int h = 30, cin = 64;
+        for (int l = 0; l < 4; ++l)
+            for (int i = 0; i < layers[l][1]; ++i) {
+                RsBlock b{};
+                b.cin = cin; b.C = layers[l][0]; b.cout = 4 * b.C; b.inter = b.C / 2 > 32 ? b.C / 2 : 32;
+                b.avd = l > 0 && i == 0; b.down = i == 0;
+                b.hin = h; b.hout = b.avd ? (h + 1) / 2 : h;   // 30 -> 15 -> 8 -> 4, by both pools
+                const int hw = b.hin * b.hin, hw2 = b.hout * b.hout;
+                b.c1 = conv(b.cin, b.C, hw);
+                b.c2 = conv3(b.C / 2, b.C, 2, hw);
+                b.src_fc = src; src += (size_t)b.inter * b.C + b.inter + 4 * (size_t)b.inter + 2 * (size_t)b.C * b.inter + 2 * (size_t)b.C;
+                b.dst_w1t = dst; dst += (size_t)b.inter * b.C;
+                b.dst_s1 = dst; dst += b.inter;
+                b.dst_h1 = dst; dst += b.inter;
+                b.dst_w2t = dst; dst += 2 * (size_t)b.C * b.inter;
+                b.dst_b2 = dst; dst += 2 * (size_t)b.C;
+                macs += 3.0 * b.C * b.inter;
+                b.c3 = conv(b.C, b.cout, hw2);
+                if (b.down) b.ds = conv(b.cin, b.cout, hw2);
+                up(buf_io, (size_t)b.cout * hw2);
+                up(buf_scratch, b.scratch());
+                blocks.push_back(b);
+                h = b.hout; cin = b.cout;
+            }
+        src_fc = src; src += (size_t)102 * kPool + 102;
+        dst_fc_w = dst; dst += (size_t)64 * kPool;             // rows 0..61 = ori | shape | exp; fc_tex is in flat (a checkpoint has it) but is not packed
+        dst_fc_b = dst; dst += 64;
+        macs += 62.0 * kPool;                                  // the module's forward never calls fc_tex
+        flat_count = src;
+        packed_count = dst;
+        flops = 2.0 * macs;
+    }
+};
+const RsNet &rsnet() {
+    static const RsNet n;
+    return n;
+}
+
 struct ConstHeader {   // first 256 bytes of an exported constants buffer
     uint64_t magic;
     uint32_t version, has_backbone, has_basis, n_vert, n_lmk, nvp, nlp, arch;
@@ -563,11 +664,12 @@ size_t ws_floats_per_face() {
     const size_t mb = 2 * net().max_io + 2 * net().max_hidden, rn = 4 * resnet50().buf_big + 2 * resnet50().buf_mid;
     const size_t m1 = 2 * mb1net(4).buf_io + mb1net(4).buf_dw;      // the widest MobileNetV1 (equal to rn: the size does not change)
     const size_t two = mb > rn ? mb : rn, gn = gnnet().ws_per_face();      // (GhostNet needs less than half of rn: the size does not change)
-    const size_t three = two > m1 ? two : m1;
-    return three > gn ? three : gn;    // one activation workspace serves every backbone
+    const size_t three = two > m1 ? two : m1, rs = rsnet().ws_per_face();      // (ResNeSt-50 needs 1 123 456 floats, below rn's 1 152 000: likewise)
+    const size_t four = three > gn ? three : gn;
+    return four > rs ? four : rs;    // one activation workspace serves every backbone
 }
-size_t backbone_floats(int arch) { return is_gn(arch) ? gnnet().packed_count : is_mb1(arch) ? mb1net(arch).packed_count : (arch == 1 ? resnet50().packed_count : net().packed_count); }
-size_t backbone_flat_floats(int arch) { return is_gn(arch) ? gnnet().flat_count : is_mb1(arch) ? mb1net(arch).flat_count : (arch == 1 ? resnet50().flat_count : net().flat_count); }
+size_t backbone_floats(int arch) { return is_rs(arch) ? rsnet().packed_count : is_gn(arch) ? gnnet().packed_count : is_mb1(arch) ? mb1net(arch).packed_count : (arch == 1 ? resnet50().packed_count : net().packed_count); }
+size_t backbone_flat_floats(int arch) { return is_rs(arch) ? rsnet().flat_count : is_gn(arch) ? gnnet().flat_count : is_mb1(arch) ? mb1net(arch).flat_count : (arch == 1 ? resnet50().flat_count : net().flat_count); }
 
 // Both scratch regions only ever grow; growing synchronises the whole device first, so work in flight on another stream
 // (synergynet_amd/streams.py runs the reconstruction of batch i beside the backbone of batch i+1) never loses its buffer.
@@ -1307,6 +1409,126 @@ int run_ghostnet(syn_handle *h, const float *img, const uint8_t *img8, int B, fl
     return SYN_OK;
 }
 
+// ---- ResNeSt-50 forward (ResNet.forward, ResNeSt/resnet.py:298-324) ----
+// Schedule (SYNERGY_HIP_FUSION / syn_set_schedule): 0 = per-layer: V = att0 U0 + att1 U1, its 3x3 / 2 average and the downsample's
+// 2x2 / 2 average are stored, one launch each, and conv3 / the downsample convolution read them; 1 = fused: conv3 (and the downsample
+// convolution of layer2.0 / 3.0) build those operands once per workgroup in LDS; 2 (default) = as 1.  Both call the same device functions for the operands and the same GEMM loop: bit-identical results.
+bool rs_fused(const syn_handle *h) { return h->fusion >= 1; }      // no batch threshold: measured faster at 1, 32, 128 and 1024 faces
+// One block of the forward, the ONLY place the ResNeSt launch arguments are derived: run_resnest50 walks blocks 0..17 through it and
+// syn_resnest50_block runs one of them.  block 0 = stem + max pool (in8 uint8 HWC crops, or in = fp32 crops, NCHW when in_hwc == 0 and
+// HWC otherwise, normalised -> out [B,30,30,64]); 1..16 = the bottlenecks layer1.0 .. layer4.2 (in [B,hin,hin,cin] -> out
+// [B,hout,hout,4C]; aux, nullable, = the attention [B,2C] in fc2's order); 17 = pool + heads (in [B,4,4,2048] -> out = param [B,62],
+// aux, nullable, = the pool [B,2048]).  scr = B x RsNet::buf_scratch floats.  mark(code, flops per face) is called after every launch;
+// code: 0 / 1 / 2 the stem convolutions, 3 the max pool; 100 block + step with step 0 conv1, 1 conv2.conv, 2 gate, 3 downsample pool,
+// 4 downsample convolution, 5 combine, 6 avd pool, 7 conv3 (per-layer) or the fused tail; 1700 pool + heads.
+template <class Mark>
+void rs_launch_block(const RsNet &n, const float *P, int block, bool fused, const float *in, const uint8_t *in8, int in_hwc, int B,
+                     float *out, float *aux, float *scr, hipStream_t s, Mark &&mark) {
+    auto gemm = [&](int op, const RsConv &c, const float *A, const float *att, const float *res, float *Y, int Hin, int Ho, int relu) {
+        syn::launch_rs_gemm(op, A, c.cin, att, P + c.dst_w, P + c.dst_scale, P + c.dst_shift, res, Y, B, Hin, Ho, c.cin, c.cout, relu, s);
+    };
+    auto conv3 = [&](const RsConv3 &c, const float *X, float *Y, int H) {
+        syn::launch_rs_conv3x3(X, c.cg * c.groups, P + c.dst_w, P + c.dst_scale, P + c.dst_shift, Y, B, H, c.cg, c.ng, c.groups, s);
+    };
+    if (block == 0) {
+        float *s1 = scr, *s2 = s1 + (size_t)B * 3600 * RsNet::kStem, *s3 = s2 + (size_t)B * 3600 * RsNet::kStem;
+        syn::launch_rs_stem(in, in8, in_hwc, P + n.dst_stem_w, P + n.dst_stem_scale, P + n.dst_stem_shift, s1, B, s);
+        mark(0, 2.0 * 27 * RsNet::kStem * 3600);
+        conv3(n.stem2, s1, s2, 60);
+        mark(1, 2.0 * 9 * RsNet::kStem * RsNet::kStem * 3600);
+        conv3(n.stem3, s2, s3, 60);
+        mark(2, 2.0 * 9 * RsNet::kStem * 2 * RsNet::kStem * 3600);
+        syn::launch_maxpool3x3s2(s3, out, B, 60, 30, 2 * RsNet::kStem, s);
+        mark(3, 0.0);
+        return;
+    }
+    if (block == 17) {
+        // global mean + heads (:309-320); the SynergyNet wrapper's 62 = ori | shape | exp, the rows as packed
+        syn::launch_pool_fc_generic(in, P + n.dst_fc_w, P + n.dst_fc_b, out, aux, B, 16, RsNet::kPool, 62, 62, s);
+        mark(1700, 2.0 * RsNet::kPool * 62);
+        return;
+    }
+    const RsBlock &b = n.blocks[block - 1];
+    const int code = 100 * block, H = b.hin, H2 = b.hout, HW = H * H, HW2 = H2 * H2;
+    float *t1 = scr, *u = t1 + B * b.n_t1(), *v = u + B * b.n_u(), *pa = v + B * b.n_t1(), *pd = pa + B * b.n_pa(), *r = pd + B * b.n_pd();
+    float *att = aux ? aux : r + B * b.n_r();
+    gemm(syn::kRsPlain, b.c1, in, nullptr, nullptr, t1, H, H, 1);
+    mark(code + 0, 2.0 * HW * b.cin * b.C);
+    conv3(b.c2, t1, u, H);
+    mark(code + 1, 2.0 * HW * 9 * (b.C / 2) * 2 * b.C);
+    syn::launch_rs_gate(u, P + b.dst_w1t, P + b.dst_s1, P + b.dst_h1, P + b.dst_w2t, P + b.dst_b2, att, B, HW, b.C, b.inter, s);
+    mark(code + 2, 2.0 * 3 * b.C * b.inter);
+    const float *res = in;
+    if (b.down) {
+        const double f_ds = 2.0 * HW2 * b.cin * b.cout;
+        if (b.avd && fused && syn::rs_tail_exists(b.cin, b.cout)) gemm(syn::kRsDsPool, b.ds, in, nullptr, nullptr, r, H, H2, 0);
+        else if (b.avd) {
+            syn::launch_rs_dspool(in, pd, B, H, H2, b.cin, s);
+            mark(code + 3, 0.0);
+            gemm(syn::kRsPlain, b.ds, pd, nullptr, nullptr, r, H2, H2, 0);
+        } else gemm(syn::kRsPlain, b.ds, in, nullptr, nullptr, r, H, H2, 0);      // layer1.0: AvgPool2d(1, 1) is the identity
+        mark(code + 4, f_ds);
+        res = r;
+    }
+    const double f_c3 = 2.0 * HW2 * b.C * b.cout;
+    if (fused) gemm(b.avd ? syn::kRsAvd : syn::kRsCombine, b.c3, u, att, res, out, H, H2, 1);
+    else {
+        syn::launch_rs_combine(u, att, v, B, HW, b.C, s);
+        mark(code + 5, 0.0);
+        const float *a = v;
+        if (b.avd) {
+            syn::launch_rs_avd(v, pa, B, H, H2, b.C, s);
+            mark(code + 6, 0.0);
+            a = pa;
+        }
+        gemm(syn::kRsPlain, b.c3, a, nullptr, res, out, H2, H2, 1);
+    }
+    mark(code + 7, f_c3);
+}
+int rs_launch_count(const RsNet &n, bool fused) {
+    int c = 4 + 1;                // the stem's three convolutions and the max pool; pool + heads
+    for (const RsBlock &b : n.blocks)
+        c += (fused ? 4 : 5) + (b.down ? 1 : 0) + (b.avd && !fused ? 1 : 0) + (b.avd && !(fused && syn::rs_tail_exists(b.cin, b.cout)) ? 1 : 0);
+    return c;                     // 74 fused (layer4.0's downsample pool, K = 1024, stays a launch of its own), 95 per layer
+}
+// per-face element counts of a hook block's input, output and aux
+void rs_block_counts(const RsNet &n, int block, size_t *n_in, size_t *n_out, size_t *n_aux) {
+    if (block == 0) { *n_in = (size_t)3 * 120 * 120; *n_out = (size_t)900 * 64; *n_aux = 0; }
+    else if (block == 17) { *n_in = (size_t)16 * RsNet::kPool; *n_out = 62; *n_aux = RsNet::kPool; }
+    else {
+        const RsBlock &b = n.blocks[block - 1];
+        *n_in = (size_t)b.hin * b.hin * b.cin; *n_out = (size_t)b.hout * b.hout * b.cout; *n_aux = 2 * (size_t)b.C;
+    }
+}
+
+int run_resnest50(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s,
+                  std::vector<hipEvent_t> *marks = nullptr, std::vector<int> *mark_launch = nullptr, std::vector<double> *mark_flops = nullptr) {
+    const RsNet &n = rsnet();
+    int rc = ensure_ws(h, B);
+    if (rc) return rc;
+    float *X = h->ws, *Y = X + (size_t)B * n.buf_io, *scr = Y + (size_t)B * n.buf_io;
+    const float *P = h->d_backbone;
+    auto mark = [&](int code, double flops) {
+        if (!marks) return;
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, s);
+        marks->push_back(e);
+        mark_launch->push_back(code);
+        mark_flops->push_back(flops);
+    };
+    mark(-1, 0.0);
+    const bool fused = rs_fused(h);
+    rs_launch_block(n, P, 0, fused, img, img8, 0, B, X, nullptr, scr, s, mark);
+    for (int block = 1; block <= 16; ++block) {
+        rs_launch_block(n, P, block, fused, X, nullptr, 0, B, Y, nullptr, scr, s, mark);
+        float *t = X; X = Y; Y = t;
+    }
+    rs_launch_block(n, P, 17, fused, X, nullptr, 0, B, param, pool, scr, s, mark);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 }  // namespace
 
 namespace syn {
@@ -1392,6 +1614,7 @@ size_t syn_backbone_flat_count(void) { return net().flat_count; }
 double syn_backbone_flops_per_face(void) { return net().flops; }
 double syn_pointwise_flops_per_face(void) { return net().pw_flops; }
 int syn_backbone_launch_count(syn_handle *h) {
+    if (h && is_rs(h->arch)) return rs_launch_count(rsnet(), rs_fused(h));      // 74 with the fused tail, 95 per layer
     if (h && is_gn(h->arch)) return gn_launch_count(gnnet(), gn_fused(h));      // 79 with the fused modules, 104 per layer
     if (h && is_mb1(h->arch)) return h->fusion >= 1 ? 15 : 28;      // stem + 13 blocks (x 2 per-layer) + pool and heads; schedule 2 below kMb1FusedMinBatch faces: 28
     return (int)net().layers.size() + 1;
@@ -1967,7 +2190,7 @@ int syn_numerics_report(syn_handle *h, char *buf, size_t n) {
     char line[256];
     int n_fallback = 0;
     if (!h->d_backbone) out = "no backbone loaded\n";
-    else if (is_mb1(h->arch) || is_gn(h->arch)) {
+    else if (is_mb1(h->arch) || is_gn(h->arch) || is_rs(h->arch)) {
         snprintf(line, sizeof line, "%s: every product is exact fp32 (fp32-input MFMA, fp32 depthwise): no fp16 operand, nothing to prove or guard\n", arch_name(h->arch));
         out = line;
     }
@@ -2364,6 +2587,89 @@ int syn_load_backbone_ghostnet(syn_handle *h, const float *flat, size_t n_floats
     return SYN_OK;
 }
 
+// ---- ResNeSt-50: flat = the module's state_dict order without num_batches_tracked (synergynet_amd.synergy3DMM.resnest50_keys) ----
+size_t syn_resnest50_flat_count(void) { return rsnet().flat_count; }
+double syn_resnest50_flops_per_face(void) { return rsnet().flops; }
+
+static void pack_backbone_resnest50(const float *flat, std::vector<float> &pk) {
+    const RsNet &n = rsnet();
+    pk.assign(n.packed_count, 0.f);
+    // BN folding in fp32: scale = gamma / sqrt(var + 1e-5), shift = beta - mean * scale
+    auto fold = [&](const float *bn, int c, size_t scale, size_t shift) {      // bn = weight | bias | running_mean | running_var
+        for (int i = 0; i < c; ++i) {
+            const float sc = bn[i] / sqrtf(bn[3 * c + i] + 1e-5f);
+            pk[scale + i] = sc;
+            pk[shift + i] = bn[c + i] - bn[2 * c + i] * sc;
+        }
+    };
+    auto conv = [&](const RsConv &c) {                         // [cout][cin]: as the kernels read it
+        memcpy(pk.data() + c.dst_w, flat + c.src, sizeof(float) * (size_t)c.cout * c.cin);
+        fold(flat + c.src + (size_t)c.cout * c.cin, c.cout, c.dst_scale, c.dst_shift);
+    };
+    auto conv3 = [&](const RsConv3 &c) {                       // [n][cg][3][3] -> [n][tap][cg]
+        const int nn = c.groups * c.ng;
+        for (int o = 0; o < nn; ++o)
+            for (int ci = 0; ci < c.cg; ++ci)
+                for (int t = 0; t < 9; ++t) pk[c.dst_w + ((size_t)o * 9 + t) * c.cg + ci] = flat[c.src + ((size_t)o * c.cg + ci) * 9 + t];
+        fold(flat + c.src + (size_t)nn * c.cg * 9, nn, c.dst_scale, c.dst_shift);
+    };
+    {   // conv1.0.weight [32][3][3][3] -> [ci*9 + ky*3 + kx][32]
+        const int c0 = RsNet::kStem;
+        for (int co = 0; co < c0; ++co)
+            for (int t = 0; t < 27; ++t) pk[n.dst_stem_w + (size_t)t * c0 + co] = flat[(size_t)co * 27 + t];
+        fold(flat + (size_t)c0 * 27, c0, n.dst_stem_scale, n.dst_stem_shift);
+    }
+    conv3(n.stem2);
+    conv3(n.stem3);
+    for (const RsBlock &b : n.blocks) {
+        conv(b.c1);
+        conv3(b.c2);
+        const int C = b.C, I = b.inter;
+        const float *w1 = flat + b.src_fc, *b1 = w1 + (size_t)I * C, *bn = b1 + I, *w2 = bn + 4 * (size_t)I, *b2 = w2 + 2 * (size_t)C * I;
+        for (int j = 0; j < I; ++j) {
+            for (int k = 0; k < C; ++k) pk[b.dst_w1t + (size_t)k * I + j] = w1[(size_t)j * C + k];
+            const float sc = bn[j] / sqrtf(bn[3 * I + j] + 1e-5f);
+            pk[b.dst_s1 + j] = sc;
+            pk[b.dst_h1 + j] = (b1[j] - bn[2 * I + j]) * sc + bn[I + j];      // BN(dot + bias)
+        }
+        for (int o = 0; o < 2 * C; ++o) {
+            for (int k = 0; k < I; ++k) pk[b.dst_w2t + (size_t)k * 2 * C + o] = w2[(size_t)o * I + k];
+            pk[b.dst_b2 + o] = b2[o];
+        }
+        conv(b.c3);
+        if (b.down) conv(b.ds);
+    }
+    {   // heads: flat order fc_ori, fc_shape, fc_exp, fc_tex; the cat (:320) is ori | shape | exp: rows 0..61 as they come; fc_tex is not packed
+        const float *src = flat + n.src_fc;
+        static const int hn[3] = {12, 40, 10};
+        int row = 0;
+        for (int k = 0; k < 3; ++k) {
+            memcpy(pk.data() + n.dst_fc_w + (size_t)row * RsNet::kPool, src, sizeof(float) * hn[k] * RsNet::kPool);
+            src += (size_t)hn[k] * RsNet::kPool;
+            memcpy(pk.data() + n.dst_fc_b + row, src, sizeof(float) * hn[k]);
+            src += hn[k];
+            row += hn[k];
+        }
+    }
+}
+
+int syn_load_backbone_resnest50(syn_handle *h, const float *flat, size_t n_floats) {
+    if (!h || !flat) return fail(SYN_ERR_INVALID, "syn_load_backbone_resnest50: NULL argument");
+    const RsNet &n = rsnet();
+    if (n_floats != n.flat_count) return fail(SYN_ERR_INVALID, "syn_load_backbone_resnest50: got %zu floats, resnest50 has %zu", n_floats, n.flat_count);
+    std::vector<float> pk;
+    pack_backbone_resnest50(flat, pk);
+    DeviceGuard g(h->device);
+    if (h->d_backbone) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->d_backbone)); h->d_backbone = nullptr; }
+    HIP_TRY(hipMalloc((void **)&h->d_backbone, n.packed_count * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->d_backbone, pk.data(), n.packed_count * sizeof(float), hipMemcpyHostToDevice));
+    h->arch = kArchResnest;
+    h->ri = RangeInfo{};
+    h->resnet_fp32 = 0; h->range_events = 0; h->guard_armed = 0; if (h->guard_word) { (void)hipDeviceSynchronize(); *(volatile unsigned *)h->guard_word = 0; }
+    h->resnet_w_unsafe[0] = h->resnet_w_unsafe[1] = h->resnet_w_unsafe[2] = 0;
+    return SYN_OK;
+}
+
 static void pack_basis(const float *w_shp, const float *w_exp, const float *u, const float *param_mean, const float *param_std,
                        const int64_t *keypoints, int n_lmk, int n_vert, std::vector<float> &pk) {
     const int nvp = round_up(n_vert, 32), nlp = round_up(n_lmk, 32);
@@ -2450,7 +2756,8 @@ int syn_pack_constants_host(int arch, const float *backbone_flat, size_t n_float
     if (bytes < need) return fail(SYN_ERR_INVALID, "syn_pack_constants_host: buffer %zu < %zu bytes", bytes, need);
     std::vector<float> bb, bs;
     if (has_bb) {
-        if (is_gn(arch)) pack_backbone_ghostnet(backbone_flat, bb);
+        if (is_rs(arch)) pack_backbone_resnest50(backbone_flat, bb);
+        else if (is_gn(arch)) pack_backbone_ghostnet(backbone_flat, bb);
         else if (is_mb1(arch)) pack_backbone_mobilenet1(arch, backbone_flat, bb);
         else if (arch == 1) pack_backbone_resnet50(backbone_flat, bb);
         else pack_backbone_mbv2(backbone_flat, bb);
@@ -2687,6 +2994,7 @@ int syn_backbone_forward(syn_handle *h, const float *img, int B, float *param, f
     if (B <= 0) return fail(SYN_ERR_INVALID, "syn_backbone_forward: B=%d", B);
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_backbone_forward: backbone weights not loaded");
     DeviceGuard g(h->device);
+    if (is_rs(h->arch)) return run_resnest50(h, img, nullptr, B, param, pool, (hipStream_t)stream);
     if (is_gn(h->arch)) return run_ghostnet(h, img, nullptr, B, param, pool, (hipStream_t)stream);
     if (is_mb1(h->arch)) return run_mobilenet1(h, img, nullptr, B, param, pool, (hipStream_t)stream);
     if (h->arch == 1) return run_resnet50(h, img, nullptr, B, param, pool, (hipStream_t)stream);
@@ -2698,6 +3006,7 @@ int syn_backbone_forward_u8(syn_handle *h, const uint8_t *img, int B, float *par
     if (B <= 0) return fail(SYN_ERR_INVALID, "syn_backbone_forward_u8: B=%d", B);
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_backbone_forward_u8: backbone weights not loaded");
     DeviceGuard g(h->device);
+    if (is_rs(h->arch)) return run_resnest50(h, nullptr, img, B, param, pool, (hipStream_t)stream);
     if (is_gn(h->arch)) return run_ghostnet(h, nullptr, img, B, param, pool, (hipStream_t)stream);
     if (is_mb1(h->arch)) return run_mobilenet1(h, nullptr, img, B, param, pool, (hipStream_t)stream);
     if (h->arch == 1) return run_resnet50(h, nullptr, img, B, param, pool, (hipStream_t)stream);
@@ -2714,9 +3023,10 @@ int syn_backbone_profile(syn_handle *h, const uint8_t *img_hwc, int B, int max_l
     HIP_TRY(hipMalloc((void **)&param, (size_t)B * 62 * sizeof(float)));
     std::vector<hipEvent_t> marks;
     std::vector<int> feats;
-    if (is_gn(h->arch)) {           // launch codes of gn_launch_block in feature_of_launch
+    if (is_gn(h->arch) || is_rs(h->arch)) {           // launch codes of gn_launch_block / rs_launch_block in feature_of_launch
         std::vector<double> fl;
-        int rc = run_ghostnet(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats, &fl);
+        int rc = is_rs(h->arch) ? run_resnest50(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats, &fl)
+                                : run_ghostnet(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats, &fl);
         int count = 0;
         if (rc == SYN_OK) {
             HIP_TRY(hipDeviceSynchronize());
@@ -2873,6 +3183,31 @@ int syn_ghostnet_block(syn_handle *h, int block, int fused, const float *in, int
     return SYN_OK;
 }
 
+// One block of the loaded ResNeSt-50 on caller-supplied activations (include/synergy_hip.h): the launches are those of run_resnest50
+// (rs_launch_block), the intermediates live in the handle's workspace where run_resnest50 keeps them.  Everything is vetted before a launch.
+int syn_resnest50_block(syn_handle *h, int block, int fused, const float *in, int B, size_t n_in, float *out, size_t n_out, float *aux,
+                        size_t n_aux, void *stream) {
+    if (!h || !in || !out) return fail(SYN_ERR_INVALID, "syn_resnest50_block: NULL argument (handle, in and out are required)");
+    if (!is_rs(h->arch)) return fail(SYN_ERR_INVALID, "syn_resnest50_block: this handle runs %s, expected resnest50", arch_name(h->arch));
+    if (block < 0 || block > 17) return fail(SYN_ERR_INVALID, "syn_resnest50_block: block=%d, expected 0 (stem + max pool), 1..16 (bottlenecks) or 17 (pool + heads)", block);
+    if (B < 1 || B > 65536) return fail(SYN_ERR_INVALID, "syn_resnest50_block: B=%d, expected 1 <= B <= 65536", B);      // 32-bit pixel indices
+    if (fused != 0 && fused != 1) return fail(SYN_ERR_INVALID, "syn_resnest50_block: fused=%d, expected 0 or 1", fused);
+    const RsNet &n = rsnet();
+    size_t f_in, f_out, f_aux;
+    rs_block_counts(n, block, &f_in, &f_out, &f_aux);
+    if (aux && !f_aux) return fail(SYN_ERR_INVALID, "syn_resnest50_block: aux on block %d, expected NULL (no attention and no pool there)", block);
+    if (n_in != f_in * B || n_out != f_out * B || (aux ? n_aux != f_aux * B : n_aux != 0))
+        return fail(SYN_ERR_INVALID, "syn_resnest50_block: block %d at B=%d expected n_in=%zu n_out=%zu n_aux=%zu, got %zu %zu %zu", block, B, f_in * B,
+                    f_out * B, aux ? f_aux * B : (size_t)0, n_in, n_out, n_aux);
+    if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_resnest50_block: backbone weights not loaded");
+    DeviceGuard g(h->device);
+    int rc = ensure_ws(h, B);
+    if (rc) return rc;
+    rs_launch_block(n, h->d_backbone, block, fused != 0, in, nullptr, 1, B, out, aux, h->ws + 2 * (size_t)B * n.buf_io, (hipStream_t)stream, [](int, double) {});
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 // Profiling hook, not part of include/synergy_hip.h: runs the backbone with the fused block of
 // .features[feature] instrumented; out8 (host) = summed s_memtime ticks of wave 0 per stage
 // {stage0, expand, barrier, depthwise, barrier, project, epilogue} and the workgroup count.
@@ -2880,7 +3215,7 @@ int syn_ghostnet_block(syn_handle *h, int block, int fused, const float *in, int
 int syn_debug_profile_block(syn_handle *h, const float *img, int B, int feature, unsigned long long *out8) {
     if (!h || !img || !out8 || B <= 0) return fail(SYN_ERR_INVALID, "syn_debug_profile_block: bad argument");
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_debug_profile_block: backbone weights not loaded");
-    if (is_mb1(h->arch) || is_gn(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_profile_block: this handle runs %s", arch_name(h->arch));
+    if (is_mb1(h->arch) || is_gn(h->arch) || is_rs(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_profile_block: this handle runs %s", arch_name(h->arch));
     DeviceGuard g(h->device);
     unsigned long long *d = nullptr;
     HIP_TRY(hipMalloc((void **)&d, 32 * sizeof(unsigned long long)));
@@ -2901,7 +3236,7 @@ int syn_debug_profile_block(syn_handle *h, const float *img, int B, int feature,
 int syn_debug_feature(syn_handle *h, const float *img, int B, int feature, float *out, void *stream) {
     if (!h || !img || !out || B <= 0 || feature < 0 || feature > 18) return fail(SYN_ERR_INVALID, "syn_debug_feature: bad argument");
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_debug_feature: backbone weights not loaded");
-    if (is_mb1(h->arch) || is_gn(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_feature: this handle runs %s", arch_name(h->arch));
+    if (is_mb1(h->arch) || is_gn(h->arch) || is_rs(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_feature: this handle runs %s", arch_name(h->arch));
     DeviceGuard g(h->device);
     return run_backbone(h, img, nullptr, B, nullptr, nullptr, (hipStream_t)stream, feature, out);
 }

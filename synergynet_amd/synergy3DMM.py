@@ -28,7 +28,8 @@ import torch.nn as nn
 
 from . import abi
 from .params import ParamsPack
-from .synth import GHOSTNET_HEADS, HEADS, MOBILENET1_HEADS, RESNET_HEADS, ghostnet_blocks, mbv2_layers, mobilenet1_blocks, resnet50_convs
+from .synth import (GHOSTNET_HEADS, HEADS, MOBILENET1_HEADS, RESNEST_HEADS, RESNET_HEADS, ghostnet_blocks, mbv2_layers, mobilenet1_blocks,
+                    resnest50_blocks, resnet50_convs)
 
 BACKBONE_PREFIX = 'I2P.backbone.'
 _BASIS_BUFFERS = ('param_mean', 'param_std', 'w_shp', 'u', 'w_exp', 'u_base', 'w_shp_base', 'w_exp_base')
@@ -44,11 +45,11 @@ def parse_param_62(param):
     return p, offset, alpha_shp, alpha_exp
 
 
-# backbone ids of the C ABI (include/synergy_hip.h; the `arch` word of the constants header).  5: never assigned.
-ARCH_IDS = {'mobilenet_v2': 0, 'resnet50': 1, 'mobilenet_1': 2, 'mobilenet_05': 3, 'mobilenet_2': 4, 'ghostnet': 6}
+# backbone ids of the C ABI (include/synergy_hip.h; the `arch` word of the constants header).  5 and 7: never assigned.
+ARCH_IDS = {'mobilenet_v2': 0, 'resnet50': 1, 'mobilenet_1': 2, 'mobilenet_05': 3, 'mobilenet_2': 4, 'ghostnet': 6, 'resnest50': 8}
 ARCH_BY_ID = {i: n for n, i in ARCH_IDS.items()}
 ARCH_NAMES = ('mobilenet_v2', 'resnet50', 'mobilenet_1', 'mobilenet_05', 'mobilenet_2')      # ids 0..4 by position (kept for callers that index it)
-_ARCH_CHOICES = ('mobilenet_v2', 'resnet50', 'ghostnet', 'mobilenet_1', 'mobilenet_05', 'mobilenet_2')      # as the refusal message lists them
+_ARCH_CHOICES = ('mobilenet_v2', 'resnet50', 'resnest50', 'ghostnet', 'mobilenet_1', 'mobilenet_05', 'mobilenet_2')      # as the refusal message lists them
 MOBILENET1_WIDTHS = {'mobilenet_1': 1.0, 'mobilenet_05': 0.5, 'mobilenet_2': 2.0}      # the widths whose channel counts are all multiples of 16
 
 _HDR_MAGIC = 0x53594e4833353558          # "SYNH355X" (csrc/synergy_abi.hip ConstHeader)
@@ -159,27 +160,58 @@ def ghostnet_keys():
     return out
 
 
+def resnest50_keys():
+    """(state_dict key, shape) of every ResNeSt-50 tensor in the module's own state_dict() order (num_batches_tracked left out): the
+    order syn_load_backbone_resnest50 expects, fc_tex included.  Written from the block table (synth.resnest50_blocks), not from the
+    module."""
+    bn = ('weight', 'bias', 'running_mean', 'running_var')
+    out = []
+
+    def conv_bn(conv, norm, shape):
+        out.append((conv + '.weight', shape))
+        out.extend((norm + '.' + s, (shape[0],)) for s in bn)
+
+    conv_bn('conv1.0', 'conv1.1', (32, 3, 3, 3))
+    conv_bn('conv1.3', 'conv1.4', (32, 32, 3, 3))
+    conv_bn('conv1.6', 'bn1', (64, 32, 3, 3))
+    for key, cin, c, inter, avd, down in resnest50_blocks():
+        conv_bn(key + '.conv1', key + '.bn1', (c, cin, 1, 1))
+        conv_bn(key + '.conv2.conv', key + '.conv2.bn0', (2 * c, c // 2, 3, 3))
+        out += [(key + '.conv2.fc1.weight', (inter, c, 1, 1)), (key + '.conv2.fc1.bias', (inter,))]
+        out.extend((key + '.conv2.bn1.' + s, (inter,)) for s in bn)
+        out += [(key + '.conv2.fc2.weight', (2 * c, inter, 1, 1)), (key + '.conv2.fc2.bias', (2 * c,))]
+        conv_bn(key + '.conv3', key + '.bn3', (4 * c, c, 1, 1))
+        if down:
+            conv_bn(key + '.downsample.1', key + '.downsample.2', (4 * c, cin, 1, 1))
+    for name, n in RESNEST_HEADS:
+        out += [(name + '.weight', (n, 2048)), (name + '.bias', (n,))]
+    return out
+
+
 def arch_keys(arch: str):
     """The (key, shape) table of a backbone by name."""
     if arch == 'ghostnet':
         return ghostnet_keys()
+    if arch == 'resnest50':
+        return resnest50_keys()
     if arch in MOBILENET1_WIDTHS:
         return mobilenet1_keys(MOBILENET1_WIDTHS[arch])
     return resnet50_keys() if arch == 'resnet50' else backbone_keys()
 
 
 def flatten_backbone(sd: dict, prefix: str = '', arch: str = 'mobilenet_v2') -> np.ndarray:
-    """state_dict -> the flat fp32 host array of syn_load_backbone[_resnet50 | _mobilenet1 | _ghostnet] (include/synergy_hip.h).
-    For ghostnet the keys under `prefix` must be exactly the module's: a missing or an unexpected key is refused, like a wrong shape."""
+    """state_dict -> the flat fp32 host array of syn_load_backbone[_resnet50 | _mobilenet1 | _ghostnet | _resnest50] (include/synergy_hip.h).
+    For ghostnet and resnest50 the keys under `prefix` must be exactly the module's: a missing or an unexpected key is refused, like a
+    wrong shape."""
     parts = []
     table = arch_keys(arch)
-    if arch == 'ghostnet':          # strict: exactly the module's tensors
+    if arch in ('ghostnet', 'resnest50'):          # strict: exactly the module's tensors
         have = {k[len(prefix):] for k in sd if k.startswith(prefix) and not k.endswith('num_batches_tracked')}
         want = {k for k, _ in table}
         if have - want:
-            raise RuntimeError(f'ghostnet state_dict: unexpected keys {sorted(have - want)[:4]}')
+            raise RuntimeError(f'{arch} state_dict: unexpected keys {sorted(have - want)[:4]}')
         if want - have:
-            raise RuntimeError(f'ghostnet state_dict: missing keys {sorted(want - have)[:4]}')
+            raise RuntimeError(f'{arch} state_dict: missing keys {sorted(want - have)[:4]}')
     for k, shape in table:
         v = sd[prefix + k]
         v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
@@ -242,7 +274,9 @@ class SynergyNet(nn.Module):
         outputs are taken, the adapter a maintainer would add), or the MobileNetV1 family 'mobilenet_1' / 'mobilenet_05' /
         'mobilenet_2' (main_train.py --arch mobilenet_1; the same [:, :62] adapter, pool_dim = 1024 x width), or 'ghostnet'
         (main_train.py --arch ghostnet; the reference's module returns only the [B,102] tensor, so its own wrapper cannot run it: here the
-        pooled feature is the 1280-vector after conv_head + ReLU that the heads consume, and the synergy refinement accepts it)."""
+        pooled feature is the 1280-vector after conv_head + ReLU that the heads consume, and the synergy refinement accepts it), or
+        'resnest50' (main_train.py --arch resnest50, the reference's I2P selector synergy3DMM.py:45-56; the module returns the 62
+        parameters and the 2048 channel means, pool_dim = 2048, so the synergy refinement is refused for it)."""
         super().__init__()
         if arch not in ARCH_IDS:
             raise RuntimeError(f"Please choose [{', '.join(_ARCH_CHOICES)}]")
@@ -336,7 +370,10 @@ class SynergyNet(nn.Module):
 
     def _upload_backbone(self):
         flat = flatten_backbone(self.state_dict(), BACKBONE_PREFIX, self.arch)
-        if self.arch == 'ghostnet':
+        if self.arch == 'resnest50':
+            assert flat.size == self._lib.syn_resnest50_flat_count()
+            abi.check(self._lib.syn_load_backbone_resnest50(self._h, flat.ctypes.data_as(C.c_void_p), flat.size))
+        elif self.arch == 'ghostnet':
             assert flat.size == self._lib.syn_ghostnet_flat_count()
             abi.check(self._lib.syn_load_backbone_ghostnet(self._h, flat.ctypes.data_as(C.c_void_p), flat.size))
         elif self.arch in MOBILENET1_WIDTHS:
@@ -515,7 +552,7 @@ class SynergyNet(nn.Module):
     def pool_dim(self):
         if self.arch in MOBILENET1_WIDTHS:
             return int(1024 * MOBILENET1_WIDTHS[self.arch])
-        return 2048 if self.arch == 'resnet50' else 1280
+        return 2048 if self.arch in ('resnet50', 'resnest50') else 1280
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)

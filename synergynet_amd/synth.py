@@ -293,6 +293,72 @@ def make_ghostnet_state(seed: int = 2031) -> dict:
     return sd
 
 
+def resnest50_blocks():
+    """Ordered (key, in, group width C, gate width, avd, downsample) of the 16 bottlenecks of the reference ResNeSt-50
+    (backbone_nets/ResNeSt/resnest.py:33-41: layers 3, 4, 6, 3, radix 2, cardinality 1, avd, avg_down).  The block's output has 4C
+    channels, conv2.conv maps C -> 2C in two groups, the gate is C -> max(C / 2, 32) -> 2C.  avd: the 3x3 / 2 average after the
+    split-attention sum and the 2x2 / 2 average in the downsample branch (layer2.0, 3.0, 4.0); downsample: a 1x1 convolution + BN on
+    the residual (every layerN.0).  At 120x120 the stem and the max pool give 30^2; the avd blocks give 15^2, 8^2, 4^2."""
+    out, cin = [], 64
+    for l, (c, count) in enumerate(((64, 3), (128, 4), (256, 6), (512, 3))):
+        for i in range(count):
+            out.append((f'layer{l + 1}.{i}', cin, c, max(c // 2, 32), l > 0 and i == 0, i == 0))
+            cin = 4 * c
+    return out
+
+
+RESNEST_HEADS = [('fc_ori', 12), ('fc_shape', 40), ('fc_exp', 10), ('fc_tex', 40)]      # module order; the forward concatenates the first three
+
+
+def make_resnest50_state(seed: int = 2741) -> dict:
+    """ResNeSt-50 state_dict (numpy fp32, reference key names, num_batches_tracked included).  Conv weights N(0, 2 / fan_in) in front of
+    a ReLU (the grouped conv2.conv: its own fan_in, C / 2 x 9); conv3 N(0, 1 / fan_in) with BN gamma U(0.3, 0.6), so the residual sums
+    do not grow over 16 blocks; the downsample N(0, 1.5 / fan_in) with gamma U(0.8, 1.2), so the signal keeps its size through the four
+    stages; other BN gamma U(0.8, 1.2); running_var U(0.8, 1.25); beta and running_mean only 0.02 N -- with 0.1 N the constants
+    re-injected by 50 BatchNorms drown what is left of the input after the four average pools, and two faces give the same output to
+    1e-3.  The gate: fc1 N(0, 2 / C), fc2 N(0, 0.5 / I), biases 0.1 N: the attention varies across channels and faces and stays
+    inside (0.05, 0.95).  Heads 0.02 N, head biases 0.1 N."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+
+    def conv(key, shape, g, bias=False):
+        fan_in = shape[1] * shape[2] * shape[3]
+        sd[key + '.weight'] = (rng.standard_normal(shape) * np.sqrt(g / fan_in)).astype(np.float32)
+        if bias:
+            sd[key + '.bias'] = (rng.standard_normal(shape[0]) * 0.1).astype(np.float32)
+
+    def bn(key, c, lo=0.8, hi=1.2):
+        sd[key + '.weight'] = rng.uniform(lo, hi, c).astype(np.float32)
+        sd[key + '.bias'] = (rng.standard_normal(c) * 0.02).astype(np.float32)
+        sd[key + '.running_mean'] = (rng.standard_normal(c) * 0.02).astype(np.float32)
+        sd[key + '.running_var'] = rng.uniform(0.8, 1.25, c).astype(np.float32)
+        sd[key + '.num_batches_tracked'] = np.array(1000, dtype=np.int64)
+
+    conv('conv1.0', (32, 3, 3, 3), 2.0)
+    bn('conv1.1', 32)
+    conv('conv1.3', (32, 32, 3, 3), 2.0)
+    bn('conv1.4', 32)
+    conv('conv1.6', (64, 32, 3, 3), 2.0)
+    bn('bn1', 64)
+    for key, cin, c, inter, avd, down in resnest50_blocks():
+        conv(key + '.conv1', (c, cin, 1, 1), 2.0)
+        bn(key + '.bn1', c)
+        conv(key + '.conv2.conv', (2 * c, c // 2, 3, 3), 2.0)
+        bn(key + '.conv2.bn0', 2 * c)
+        conv(key + '.conv2.fc1', (inter, c, 1, 1), 2.0, bias=True)
+        bn(key + '.conv2.bn1', inter)
+        conv(key + '.conv2.fc2', (2 * c, inter, 1, 1), 0.5, bias=True)
+        conv(key + '.conv3', (4 * c, c, 1, 1), 1.0)
+        bn(key + '.bn3', 4 * c, 0.3, 0.6)
+        if down:
+            conv(key + '.downsample.1', (4 * c, cin, 1, 1), 1.5)
+            bn(key + '.downsample.2', 4 * c)
+    for name, n in RESNEST_HEADS:
+        sd[name + '.weight'] = (rng.standard_normal((n, 2048)) * 0.02).astype(np.float32)
+        sd[name + '.bias'] = (rng.standard_normal(n) * 0.1).astype(np.float32)
+    return sd
+
+
 def _rotation(yaw, pitch, roll):
     cy, sy = np.cos(yaw), np.sin(yaw)
     cp, sp = np.cos(pitch), np.sin(pitch)
