@@ -10,9 +10,11 @@
 //   * the block input of the face lives in REGISTERS as pre-split B fragments (5 k32 steps x 2 pieces = 40 registers), the
 //     accumulators too: the waves walk the 30 hidden groups with no partial sums to exchange;
 //   * the WEIGHTS go through LDS: the eight waves of a workgroup (four faces) walk the groups in lockstep and share one fetch of each group's
-//     fragments + constants -- one contiguous 48 | 64 KB run of the packed blob, an eighth per wave, fetched into registers while the
-//     current group computes and written to the other half of a double buffer at its end; one barrier per group.  (Each wave
-//     fetching its own fragments would pull 1.2 MB through L2 per face.)
+//     fragments + constants -- one contiguous 48 | 64 KB run of the packed blob, an eighth per wave, fetched into registers TWO groups
+//     ahead and written to the other half of a double buffer during the depthwise of the group in front (the LDS is idle there); the
+//     group's expand operands are requested from LDS while the previous group's project runs, its project fragments inside its own
+//     expand chain: no LDS phase stands between the last matrix instruction of a group and the first of the next (lb4_stage).
+//     (Each wave fetching its own fragments would pull 1.2 MB through L2 per face.)
 //   * TWO waves per face (B = 1024 offers four faces per CU, and a lone wave per SIMD issues vector instructions at half the
 //     rate): wave (face, t) owns hidden tile t through expand and depthwise and half of the output tiles in the project; the
 //     two halves of the project operand cross through LDS (16 bytes per lane, one extra barrier per group).
@@ -99,9 +101,13 @@ struct Lb4StageArgs {
 };
 
 template <int N>
-__device__ __forceinline__ void lb4_fetch(u32x4 *pf, const unsigned *src /* + 4 lane */, int wave) {
+__device__ __forceinline__ void lb4_fetch(u32x4 *pf, const unsigned *src /* uniform */, unsigned lane16, int wave) {
+    // (a uniform base per piece + the lane's 32-bit byte offset: one address register for all pieces instead of a 64-bit pair each)
+    const unsigned long long a = reinterpret_cast<unsigned long long>(src + wave * 256);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    const char *base = reinterpret_cast<const char *>(((unsigned long long)hi << 32) | lo);
 #pragma unroll
-    for (int i = 0; i < N; ++i) pf[i] = *(const u32x4 *)(src + (wave + 8 * i) * 256);
+    for (int i = 0; i < N; ++i) pf[i] = *(const u32x4 *)(base + i * 8192 + lane16);
 }
 template <int N>
 __device__ __forceinline__ void lb4_park(const u32x4 *pf, unsigned *dst /* + 4 lane */, int wave) {
@@ -109,12 +115,48 @@ __device__ __forceinline__ void lb4_park(const u32x4 *pf, unsigned *dst /* + 4 l
     for (int i = 0; i < N; ++i) *(u32x4 *)&dst[(wave + 8 * i) * 256] = pf[i];
 }
 
+// What a group's expand chain and depthwise start from, read from LDS one group AHEAD (during the previous group's project): the accumulator's
+// start value, this wave's expand fragments, and rows 0-8 (filter taps) and 9 (BN shift) of the group's table for channels 16 t + 4 g .. + 3.
+struct Lb4Pre {
+    f32x4 D;
+    u32x4 Ae[5][2];
+    f32x4 wr[10];
+};
+constexpr int kLb4PreUnits = 10;     // eight registers each: units 0-4 = the k32 steps of Ae (0 with D in front), 5-9 = two table rows each
+// unit u of group `half` (configuration C).  The LDS returns in order: the start value first, then the fragments in the order the chain consumes them.
+template <class C>
+__device__ __forceinline__ void lb4_pre_unit(Lb4Pre &pre, const unsigned *half, int u, int t, unsigned l4, unsigned g4) {
+    if (u < 5) {
+        const float *Tb = reinterpret_cast<const float *>(half + C::WE_DW + C::WP_DW);
+        if (u == 0) pre.D = *(const f32x4 *)&Tb[10 * 32 + 16 * t + g4];
+#pragma unroll
+        for (int p = 1; p >= 0; --p) pre.Ae[u][p] = *(const u32x4 *)&half[((t * 5 + u) * 2 + p) * 256 + l4];
+    } else {
+        const float *Tb = reinterpret_cast<const float *>(half + C::WE_DW + C::WP_DW);
+#pragma unroll
+        for (int k = 2 * (u - 5); k < 2 * (u - 5) + 2; ++k) pre.wr[k] = *(const f32x4 *)&Tb[k * 32 + 16 * t + g4];
+    }
+}
+template <class T> struct Lb4Tag { using type = T; };
+template <int N> struct Lb4Int { static constexpr int value = N; };
+
 // GRPL: dwords per half of the LDS weight double buffer (>= the group run of every stage of the kernel)
 // PARTIAL (small batches): the workgroup (blockIdx.x = four faces, blockIdx.y = slice) walks only the hidden groups of its slice and
 // stores its raw accumulators; lb4_reduce_kernel adds the slices in fixed order, rescales, adds BN shift and residual.  A batch of 128
 // faces is then 32 x 6 workgroups of five groups each instead of 32 workgroups walking all thirty.
-template <class C, class CN, bool FIRST, int GRPL, bool PARTIAL = false>
-__device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa, const unsigned *GlbNext, int B, u32x4 (&Xr)[5][2], f32x4 (&vres)[5]) {
+//
+// The weight pipeline, per group G (two LDS halves, `pf` = one group in registers, `pre` = the next group's expand operands):
+//   top barrier          every wave is done with group G-1: its half may be rewritten
+//   expand chain         from `pre` (requested during G-1's project); behind each k32 step one output tile's project fragments are requested
+//   PARK G+1             pf -> the half G-1 has left;  FETCH G+2 -> pf (global; a whole group to land)
+//   depthwise, exchange barrier: it also publishes group G+1
+//   PRE G+1              requested from LDS while G's project runs, into registers the project frees as it goes (PRE0 units up front,
+//                        then one per output tile from tile LAG on, the rest behind the last)
+// At the first group of a slice | FIRST stage the prologue stands in for G-1; at a stage's last group G+1 is the NEXT stage's first group,
+// which goes to half 0 (NG is even) while half 1, the hand-over buffer, is written only between its own two barriers.
+template <class C, class CN, bool FIRST, int GRPL, bool PARTIAL, int NPF, int PRE0, int LAG>
+__device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa, const unsigned *GlbNext, int B, u32x4 (&Xr)[5][2], f32x4 (&vres)[5],
+                                          u32x4 (&pf)[NPF], Lb4Pre &pre) {
     constexpr int KE = C::KE, MTW = C::MTW, CIN = C::CIN, COUT = C::COUT;
     constexpr bool HANDOFF = !__is_same(CN, void);
     static_assert(KE == 5 && C::NG % 2 == 0, "160 input channels; the double buffer's parity carries over to the next stage");
@@ -128,20 +170,20 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
     const bool real = f < B;
     const int fc = real ? f : B - 1;
     const int n = lane & 15, g = lane >> 4;
-    const unsigned l4 = lane * 4, g4 = g * 4;
+    const unsigned l4 = lane * 4, g4 = g * 4, l16 = lane * 16;
     unsigned *Xch = smem + 2 * GRPL;
 
-    // every wave copies every eighth 1 KB piece of a group's run through registers: fetched at the start of the previous group,
-    // written to the other half of the double buffer at its end.  (LDS-DMA -- global_load_lds_dwordx4, no registers -- delivers
+    // every wave copies every eighth 1 KB piece of a group's run through registers: fetched two groups ahead, written to the other half
+    // of the double buffer during the depthwise of the group in front.  (LDS-DMA -- global_load_lds_dwordx4, no registers -- delivers
     // ~25 GB/s per CU whoever issues it: 44 KB per group took 1.8 us, longer than the group's arithmetic.)
     constexpr int NPW = C::NKB / 8;
     using CNX = typename std::conditional<HANDOFF, CN, Lb4NoNext>::type;
     constexpr int NPWN = CNX::NKB / 8;
-    u32x4 pf[NPW > NPWN ? NPW : NPWN];
+    static_assert(NPF >= NPW && NPF >= NPWN, "pf holds a group of this stage or of the next");
     const int gsl = PARTIAL ? (sa.g1 - sa.g0) : C::NG;   // groups per slice (all slices the same)
     const int gb = PARTIAL ? (int)blockIdx.y * gsl : 0, ge = gb + gsl;
     if (FIRST) {
-        lb4_fetch<NPW>(pf, Glb + (size_t)gb * C::GRP_DW + l4, wave);
+        lb4_fetch<NPW>(pf, Glb + (size_t)gb * C::GRP_DW, l16, wave);
         // ---- block input of this face -> pre-split B fragments in registers (x 16; both waves of the face hold it) ----
         f32x4 xv[KE][2];
 #pragma unroll
@@ -165,59 +207,61 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
 #pragma unroll
     for (int i = 0; i < MTW; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float c6e = 0.f, inv_p = 0.f;
-    if (FIRST) lb4_park<NPW>(pf, smem + l4, wave);
+    if (FIRST) {
+        lb4_park<NPW>(pf, smem + l4, wave);
+        if (!PARTIAL || gsl >= 2) lb4_fetch<NPW>(pf, Glb + (size_t)(gb + 1) * C::GRP_DW, l16, wave);     // (a slice of ONE group: nothing further to fetch)
+        __syncthreads();                                 // group gb is in half 0: its expand operands, which every later group finds requested by the group in front
+#pragma unroll
+        for (int u = 0; u < kLb4PreUnits; ++u) lb4_pre_unit<C>(pre, smem, u, t, l4, g4);
+    }
 
     {   // ReLU6 ceiling of the scaled expand output, accumulator -> output: constants of the block, kept in group 0's table
         const float *t0 = reinterpret_cast<const float *>(Glb + C::WE_DW + C::WP_DW);
         c6e = t0[11 * 32]; inv_p = t0[11 * 32 + 1];
     }
-    for (int G = gb; G < ge; ++G) {
-        __syncthreads();                                 // every wave has written its pieces of group G and is done with group G-1
-        if (G + 1 < ge) lb4_fetch<NPW>(pf, Glb + (size_t)(G + 1) * C::GRP_DW + l4, wave);
-        else if (HANDOFF) lb4_fetch<NPWN>(pf, GlbNext + l4, wave);          // the next block's first group
+    // One group.  NF pieces per wave of the group after next are fetched from `fsrc`, NP pieces of the next group parked, and the
+    // next group's expand operands requested in configuration CP (void: there is no next group): compile-time, so that the loop body holds no branch.
+    auto group = [&](auto nf_, auto np_, auto cp_, int G, const unsigned *fsrc) __attribute__((always_inline)) {
+        constexpr int NF = decltype(nf_)::value, NP = decltype(np_)::value;
+        using CP = typename decltype(cp_)::type;
+        constexpr bool HASNEXT = !__is_same(CP, void);
+        __syncthreads();                                 // every wave is done with group G-1 (and has its own reads of group G's operands back)
         const unsigned *We = smem + ((G - gb) & 1) * GRPL, *Wp = We + C::WE_DW;
-        const float *Tb = reinterpret_cast<const float *>(Wp + C::WP_DW);
-        __builtin_amdgcn_sched_barrier(0);               // the next group's fetch stays in front of this group's LDS reads
-        // fragments of this wave.  Round 5: the eight waves read 22 KB each here, the LDS delivers 128 bytes per cycle, and the expand chain
-        // used to wait for ALL of it (the project fragments were pinned in front of it): ~1400 cycles per group in which nothing else ran.
-        // Now only the expand fragments and the group's constants stand in front of the expand chain; the project fragments are requested
-        // behind it and land during the depthwise arithmetic, which leaves the LDS idle.
-        u32x4 Ae[KE][2], Ap[MTW][2];
-        // (the LDS returns in order: the accumulator's start value first, then the fragments in the order the chain consumes them, then the filter)
-        f32x4 D = *(const f32x4 *)&Tb[10 * 32 + 16 * t + g4];
-#pragma unroll
-        for (int kc = 0; kc < KE; ++kc)
-#pragma unroll
-            for (int p = 1; p >= 0; --p) Ae[kc][p] = *(const u32x4 *)&We[((t * KE + kc) * 2 + p) * 256 + l4];
+        unsigned *Wn = smem + ((G + 1 - gb) & 1) * GRPL;   // the half of group G-1, then of group G+1
+        // Round 5: the eight waves read 22 KB each at this point, the LDS delivers 128 bytes per cycle, and the expand chain used to wait for ALL
+        // of it: ~1400 cycles per group in which nothing else ran; then only the expand fragments stood in front of the chain.  Round 7: those
+        // were requested during the previous group's project, so the chain starts here, and each k32 step of it is followed by the request of one
+        // output tile's project fragments, into the registers that step's expand fragments have left: the LDS works under the chain instead of behind it.
+        u32x4 Ap[MTW][2];
+        f32x4 D = pre.D;
         constexpr int MTW0 = MTW > 5 ? MTW / 2 : MTW;    // (320 output channels: the second half of the project fragments after the exchange)
-        // depthwise filter, its BN shift: two channels x two halves per lane group, requested with the expand fragments
-        f32x2 wt[2][9], dsht[2];
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) wt[hf][k] = *(const f32x2 *)&Tb[k * 32 + 16 * t + 2 * hf + g4];
-            dsht[hf] = *(const f32x2 *)&Tb[9 * 32 + 16 * t + 2 * hf + g4];
-        }
+        static_assert(MTW0 == KE, "one output tile's project fragments per k32 step of the expand chain");
         // ---- expand 1x1 + BN shift: D = channels 32 G + 16 t + 4 g + i of pixel n (three partial products, smallest first) ----
-        __builtin_amdgcn_sched_barrier(0);               // every read above is issued before the first matrix instruction (the LDS returns in order: counted waits)
 #pragma unroll
         for (int kc = 0; kc < KE; ++kc) {
-            D = mfmaq(Ae[kc][1], Xr[kc][0], D);
-            D = mfmaq(Ae[kc][0], Xr[kc][1], D);
-            D = mfmaq(Ae[kc][0], Xr[kc][0], D);
+            D = mfmaq(pre.Ae[kc][1], Xr[kc][0], D);
+            D = mfmaq(pre.Ae[kc][0], Xr[kc][1], D);
+            D = mfmaq(pre.Ae[kc][0], Xr[kc][0], D);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int p = 0; p < 2; ++p) Ap[kc][p] = *(const u32x4 *)&Wp[((t * MTW + kc) * 2 + p) * 256 + l4];
+            __builtin_amdgcn_sched_barrier(0);
         }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < MTW0; ++i)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) Ap[i][p] = *(const u32x4 *)&Wp[((t * MTW + i) * 2 + p) * 256 + l4];
+        // the next group's weights: registers -> the half group G-1 has left (the top barrier above), behind the project fragments in the LDS queue;
+        // the group after next: global -> the same registers, with a whole group to land
+        if (NP) lb4_park<NP>(pf, Wn + l4, wave);
+        __builtin_amdgcn_sched_barrier(0);               // (the fetch behind the park, into the registers it has just read: not in front of it into others)
+        if (NF) lb4_fetch<NF>(pf, fsrc, l16, wave);
         __builtin_amdgcn_sched_barrier(0);
         // ---- ReLU6, depthwise 3x3 + BN shift + ReLU6 on the registers, split into this wave's half of the project operand ----
         u32x4 own;                                      // {piece 0 dwords hf 0, 1 | piece 1 dwords hf 0, 1}
 #pragma unroll
         for (int hf = 0; hf < 2; ++hf) {
-            const f32x2 (&w)[9] = wt[hf];
-            const f32x2 dsh = dsht[hf];
+            // depthwise filter, its BN shift: two channels x two halves per lane group
+            f32x2 w[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) w[k] = (f32x2){pre.wr[k][2 * hf], pre.wr[k][2 * hf + 1]};
+            const f32x2 dsh = (f32x2){pre.wr[9][2 * hf], pre.wr[9][2 * hf + 1]};
             f32x2 E;
             // ReLU6 as clamp modifiers (fused_block_lb.hip): E = relu6 / 6 = clamp(D / (96 Se)); the last add of the output clamps too
             E[0] = __builtin_amdgcn_fmed3f(D[2 * hf] * c6e, 0.0f, 1.0f);
@@ -245,7 +289,7 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
         }
         // ---- the partner's half: K slots 0-3 of a lane group are tile 0's channels, 4-7 tile 1's ----
         *(u32x4 *)&Xch[((fl * 2 + t) * 64 + lane) * 4] = own;
-        __syncthreads();
+        __syncthreads();                                 // the exchange; every wave's pieces of group G+1 are in LDS too
         const u32x4 oth = *(const u32x4 *)&Xch[((fl * 2 + (1 - t)) * 64 + lane) * 4];
 #pragma unroll
         for (int i = MTW0; i < MTW; ++i)
@@ -254,16 +298,30 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
         u32x4 Bd[2];
         Bd[0] = t == 0 ? (u32x4){own[0], own[1], oth[0], oth[1]} : (u32x4){oth[0], oth[1], own[0], own[1]};
         Bd[1] = t == 0 ? (u32x4){own[2], own[3], oth[2], oth[3]} : (u32x4){oth[2], oth[3], own[2], own[3]};
-        // ---- project 1x1, K = this group, this wave's half of the output tiles ----
+        // ---- project 1x1, K = this group, this wave's half of the output tiles; between its matrix instructions the next group's
+        //      expand operands are requested: PRE0 units in front, then one per output tile, into the registers that tile's fragments leave ----
 #pragma unroll
-        for (int i = 0; i < MTW; ++i) {
+        for (int i = 0; i <= MTW; ++i) {
+            if constexpr (HASNEXT) {
+#pragma unroll
+                for (int u = 0; u < kLb4PreUnits; ++u) {
+                    const int at = u < PRE0 ? 0 : (u - PRE0 + LAG < MTW ? u - PRE0 + LAG : MTW);
+                    if (at == i) lb4_pre_unit<CP>(pre, Wn, u, t, l4, g4);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (i == MTW) break;
             acc[i] = mfmaq(Ap[i][1], Bd[0], acc[i]);
             acc[i] = mfmaq(Ap[i][0], Bd[1], acc[i]);
             acc[i] = mfmaq(Ap[i][0], Bd[0], acc[i]);
+            if constexpr (HASNEXT) __builtin_amdgcn_sched_barrier(0);
         }
-        if (G + 1 < ge) lb4_park<NPW>(pf, smem + ((G + 1 - gb) & 1) * GRPL + l4, wave);
-        else if (HANDOFF) lb4_park<NPWN>(pf, smem + l4, wave);               // (NG is even: the next block starts in half 0 again)
-    }
+    };
+    // the last two groups of the stage fetch | park the next stage's first two groups (NPWN pieces; none without a next stage)
+    for (int G = gb; G < ge - 2; ++G)
+        group(Lb4Int<NPW>{}, Lb4Int<NPW>{}, Lb4Tag<C>{}, G, Glb + (size_t)(G + 2) * C::GRP_DW);
+    if (!PARTIAL || gsl >= 2) group(Lb4Int<NPWN>{}, Lb4Int<NPW>{}, Lb4Tag<C>{}, ge - 2, GlbNext);
+    group(Lb4Int<NPWN>{}, Lb4Int<NPWN>{}, Lb4Tag<CN>{}, ge - 1, HANDOFF ? GlbNext + CNX::NKB * 256 : nullptr);
     if constexpr (PARTIAL) {                             // raw accumulators of this slice -> [slice][B][16][COUT]
         if (real) {
 #pragma unroll
@@ -309,17 +367,23 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
         for (int kc = 0; kc < KE; ++kc)
 #pragma unroll
             for (int p = 0; p < 2; ++p) Xr[kc][p] = *(const u32x4 *)&HO[((fl * KE + kc) * 2 + p) * 256 + l4];
-        // (half 1 is rewritten at the end of the next block's first group, two barriers from here)
+        // (half 1 is rewritten during the next block's first group, behind that group's top barrier: every wave has these reads back by then)
     }
 }
+
+// units of the next group's expand operands requested in front of the project's first matrix instruction (the rest: one per output tile)
+// (the most that compiles without a spill: the single 160-channel block takes all ten, the chain's 160-channel stages, which also hold the
+// residual and a 64 KB group in flight, four; the 320-channel stage starts behind its second output tile -- each tile frees eight registers)
+constexpr int kPre0Q15 = 10, kPre0Q15C = 4, kPre0Q17 = 0, kLagQ15 = 1, kLagQ15C = 1, kLagQ17 = 2;
 
 template <class C, bool PARTIAL = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void fused_block_lb4_kernel(Lb4StageArgs sa, int B) {
     __shared__ __attribute__((aligned(16))) unsigned smem[C::LDS_DW];
-    u32x4 Xr[5][2];
+    u32x4 Xr[5][2], pf[C::NKB / 8];
     f32x4 vres[5];
-    lb4_stage<C, void, true, C::GRP_DW, PARTIAL>(smem, sa, nullptr, B, Xr, vres);
+    Lb4Pre pre;
+    lb4_stage<C, void, true, C::GRP_DW, PARTIAL, C::NKB / 8, C::MTW == 5 ? kPre0Q15 : kPre0Q17, C::MTW == 5 ? kLagQ15 : kLagQ17>(smem, sa, nullptr, B, Xr, vres, pf, pre);
 }
 
 // y = (slice 0 + slice 1 + ... in this order) / (16 Sp) + BN shift (+ x): one thread per four channels of a pixel
@@ -349,16 +413,19 @@ static_assert(kChain4LdsDw * 4 <= 160 * 1024 && 4 * 5 * 2 * 256 <= kChain4Grp, "
 struct Lb4ChainArgs { Lb4StageArgs s[3]; };
 
 // No L2 warm-up of the three weight runs at kernel start (syn_internal.h l2_touch), although the same touch gains 4.5 us in the features.7-14
-// chain: this kernel's groups are paced by the LDS (224 KB through it per group) and its two barriers, not by where the weight lines come from
-// (round-5 negative, 167.4 against 163.3 us: docs/history.md).
+// chain: this kernel's groups are not paced by where the weight lines come from (round-5 negative, 167.4 against 163.3 us: docs/history.md;
+// round 7 took the LDS phases off the group boundary for 7 us of 157, so the LDS was not the whole answer either).
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void fused_chain_lb4_kernel(Lb4ChainArgs ca, int B) {
     __shared__ __attribute__((aligned(16))) unsigned smem[kChain4LdsDw];
-    u32x4 Xr[5][2];
+    constexpr int NPF = Q17::NKB / 8;
+    static_assert(Q17::NKB >= Q15::NKB, "pf holds a group of any stage");
+    u32x4 Xr[5][2], pf[NPF];
     f32x4 vres[5];
-    lb4_stage<Q15, Q15, true, kChain4Grp>(smem, ca.s[0], ca.s[1].Glb, B, Xr, vres);
-    lb4_stage<Q15, Q17, false, kChain4Grp>(smem, ca.s[1], ca.s[2].Glb, B, Xr, vres);
-    lb4_stage<Q17, void, false, kChain4Grp>(smem, ca.s[2], nullptr, B, Xr, vres);
+    Lb4Pre pre;
+    lb4_stage<Q15, Q15, true, kChain4Grp, false, NPF, kPre0Q15C, kLagQ15C>(smem, ca.s[0], ca.s[1].Glb, B, Xr, vres, pf, pre);
+    lb4_stage<Q15, Q17, false, kChain4Grp, false, NPF, kPre0Q15C, kLagQ15C>(smem, ca.s[1], ca.s[2].Glb, B, Xr, vres, pf, pre);
+    lb4_stage<Q17, void, false, kChain4Grp, false, NPF, kPre0Q17, kLagQ17>(smem, ca.s[2], nullptr, B, Xr, vres, pf, pre);
 }
 
 template <class C>
