@@ -175,6 +175,26 @@ size_t syn_resnest50_flat_count(void);
 double syn_resnest50_flops_per_face(void);
 int syn_load_backbone_resnest50(syn_handle *h, const float *flat, size_t n_floats);
 
+/* The BasicBlock ResNets (reference backbone_nets/resnet_backbone.py:50-87, 282-301; `--arch resnet18` / `--arch resnet34` of
+ * main_train.py).  Backbone ids 10 and 11; the id table continues:
+ *   9: never assigned | 10 resnet18 | 11 resnet34
+ * `flat` = the module's state_dict() order without num_batches_tracked (synergynet_amd.synergy3DMM.resnet_basic_keys): conv1.weight, bn1.*,
+ * then per BasicBlock layerL.I: conv1.weight, bn1.*, conv2.weight, bn2.*, [downsample.0.weight, downsample.1.* on layer2.0 / 3.0 / 4.0];
+ * fc_tex / fc_ori / fc_shape / fc_exp {weight, bias}.  fc_tex is KEPT in flat, so a checkpoint flattens as it is: 11 238 438 floats
+ * (resnet18), 21 354 022 (resnet34); it is not packed.  BatchNorm is folded on the host in fp32 (eps 1e-5).
+ * After loading, syn_backbone_forward[_u8] run this network, every product exact fp32 (fp32-input MFMA): syn_numerics_report has nothing
+ * to prove, syn_backbone_range_status / _calibrate return 0.  param = the first 62 of the module's 102 outputs (ori 12 | shape 40 |
+ * exp 10; fc_tex does not run), pool = the 512 channel means: not 1280 wide, so syn_refine_landmarks refuses these archs.
+ * SYNERGY_HIP_FUSION / syn_set_schedule(h, .): 0 = per-layer (22 / 38 launches: every 3x3 convolution reads its taps from global memory,
+ * the 1x1 stride-2 downsample of layer2.0 / 3.0 / 4.0 is a launch of its own); 1 = LDS-tiled (19 / 35 launches: a workgroup stages a band
+ * of input rows with its halo, or whole faces of the 8^2 / 4^2 maps, once in LDS, at most 80 KiB, and conv1 of those three blocks also
+ * produces the downsample from its centre tap); 2 (default) = as 1.  The schedules are bit-identical.
+ * syn_resnet_basic_flops_per_face = 2 x the MACs the forward runs (Conv2d and the three heads): 2 x 553 011 200 (resnet18),
+ * 2 x 1 129 564 160 (resnet34).  An arch other than 10 / 11: the counts return 0, the loader SYN_ERR_INVALID. */
+size_t syn_resnet_basic_flat_count(int arch);
+double syn_resnet_basic_flops_per_face(int arch);
+int syn_load_backbone_resnet_basic(syn_handle *h, int arch, const float *flat, size_t n_floats);
+
 /* ParamsPack (utils/params.py:10-35) + the register_buffer block (synergy3DMM.py:95-105).
  * HOST arrays: w_shp [3*n_vert,40], w_exp [3*n_vert,10], u [3*n_vert] (= u_shp+u_exp),
  * param_mean/param_std [>=62] (first 62 used), keypoints [3*n_lmk] flat indices into the
@@ -210,7 +230,7 @@ int syn_describe_constants(syn_handle *h, void *host_header, size_t bytes);
 /* Device-free twins of the hand-off: neither makes a HIP call, so a loader process (or a test) without a GPU can produce and
  * vet the blob.  syn_pack_constants_host writes, from HOST arrays (same meaning as syn_load_backbone / _resnet50 / syn_load_basis;
  * backbone_flat or the whole basis group may be NULL), exactly the bytes syn_export_constants produces after the same loads;
- * arch 0 = mobilenet_v2, 1 = resnet50, 2 / 3 / 4 = mobilenet_1 / _05 / _2, 6 = ghostnet, 8 = resnest50 (5 and 7 were never assigned and are refused).  syn_check_constants_host applies syn_import_constants' acceptance checks (magic, version,
+ * arch 0 = mobilenet_v2, 1 = resnet50, 2 / 3 / 4 = mobilenet_1 / _05 / _2, 6 = ghostnet, 8 = resnest50, 10 / 11 = resnet18 / resnet34 (5, 7 and 9 were never assigned and are refused).  syn_check_constants_host applies syn_import_constants' acceptance checks (magic, version,
  * sizes vs this library's network tables, payload within the buffer) to a host copy of a blob. */
 size_t syn_pack_constants_host_bytes(int arch, int have_backbone, int n_vert, int n_lmk);
 int syn_pack_constants_host(int arch, const float *backbone_flat, size_t n_floats, const float *w_shp, const float *w_exp,
@@ -623,6 +643,19 @@ int syn_ghostnet_block(syn_handle *h, int block, int fused, const float *in_nhwc
  * are device pointers; the block's intermediates live in the handle's workspace (one stream at a time, as the forward). */
 int syn_resnest50_block(syn_handle *h, int block, int fused, const float *in_nhwc, int B, size_t n_in,
                         float *out, size_t n_out, float *aux, size_t n_aux, void *stream);
+
+/* One block of the loaded resnet18 / resnet34 (arch 10 / 11) on activations the caller supplies, through exactly the launches the forward
+ * uses for that block (one helper derives the launch arguments for both) -- the hook tests/test_gpu_resnet_basic.py judges every block with.
+ *   block 0          stem + max pool: in = normalised fp32 crops [B,3,120,120] (NCHW, as syn_backbone_forward takes them), out = [B,30,30,64]
+ *   block 1..8 / 16  BasicBlocks layer1.0 .. layer4.1 / layer4.2: in = NHWC fp32 [B,hin,hin,cin], out = [B,hout,hout,C]
+ *   block 9 / 17     pool + heads: in = [B,4,4,512], out = [B,62]
+ * fused = 1: the LDS-tiled convolutions (the downsample inside conv1 on layer2.0 / 3.0 / 4.0); fused = 0: one launch per layer, taps from
+ * global memory.  n_in / n_out are ELEMENT counts.  Refused with SYN_ERR_INVALID and a message that names what was expected, before any
+ * launch, with `out` untouched: a count that differs from what the block needs, a handle whose arch is neither resnet18 nor resnet34, a
+ * block outside the range, B < 1 or B > 65536, fused other than 0 / 1.  Asynchronous on `stream`; all pointers are device pointers; the
+ * block's intermediates live in the handle's workspace (one stream at a time, as the forward). */
+int syn_resnet_basic_block(syn_handle *h, int block, int fused, const float *in_nhwc, int B, size_t n_in, float *out, size_t n_out,
+                           void *stream);
 
 /* The dense reconstruction (transform = 1) into a pitched output with HIP events around its kernels, on the default stream;
  * synchronises.  ms2[0] = per-face prologue, ms2[1] = the contraction + pose epilogue + mesh stores -- the HBM-write-bound kernel

@@ -51,6 +51,9 @@ _SIGS = {
     'syn_resnest50_flat_count': (C.c_size_t, []),
     'syn_resnest50_flops_per_face': (C.c_double, []),
     'syn_load_backbone_resnest50': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    'syn_resnet_basic_flat_count': (C.c_size_t, [C.c_int]),
+    'syn_resnet_basic_flops_per_face': (C.c_double, [C.c_int]),
+    'syn_load_backbone_resnet_basic': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     'syn_load_basis': (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int, C.c_int]),
     'syn_constants_bytes': (C.c_size_t, [C.c_void_p]),
     'syn_export_constants': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -116,6 +119,7 @@ _SIGS = {
                                      C.c_void_p]),
     'syn_resnest50_block': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                       C.c_void_p]),
+    'syn_resnet_basic_block': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     'syn_reconstruct_profile': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'syn_backbone_flops_per_face': (C.c_double, []),
     'syn_pointwise_flops_per_face': (C.c_double, []),

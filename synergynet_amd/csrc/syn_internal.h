@@ -308,6 +308,23 @@ void launch_rs_combine(const float *U, const float *att, float *V, int B, int HW
 void launch_rs_avd(const float *V, float *out, int B, int Hin, int Ho, int C, hipStream_t s);
 void launch_rs_dspool(const float *X, float *out, int B, int Hin, int Ho, int C, hipStream_t s);
 
+// ---- resnet18 / resnet34 (resnet_basic_kernels.hip): every product exact fp32; C a power of two >= 64, N % 32 == 0 ----
+// 3x3 pad 1 stride 1 | 2 + BN (+ res [B,Ho,Ho,N]) (+ ReLU): X [B,Hin,Hin,C], W [N][9][C] tap-major, Y [B,Ho,Ho,N]; taps from global memory
+void launch_bb_conv3x3(const float *X, const float *W, const float *scale, const float *shift, const float *res, float *Y, int B, int Hin,
+                       int Ho, int C, int N, int stride, int relu, hipStream_t s);
+// the 1x1 stride-2 downsample + BN: W [N][C]
+void launch_bb_down1x1(const float *X, const float *W, const float *scale, const float *shift, float *Y, int B, int Hin, int Ho, int C,
+                       int N, hipStream_t s);
+// the same convolution from an input band staged in LDS; at stride 2 Wd is required and Yd = BN(downsample), from the centre tap
+constexpr size_t kBbLdsBytes = 80 * 1024;      // two workgroups share a CU's 160 KiB
+constexpr int kBbLdsGroups = 512;              // the channels are split over workgroups until the grid has this many (2 per CU)
+constexpr int kBbFacesMinGroups = 256;         // whole faces per workgroup only once that grid has a workgroup for every CU
+struct BbLdsGrid { int faces, rows, nb, gridx, split; size_t lds; };      // whole faces per workgroup (0: bands) | output rows per band, bands per face; workgroups, channel ranges, LDS bytes
+BbLdsGrid bb_lds_grid(int B, int Hin, int Ho, int C, int N, int stride);
+void launch_bb_conv3x3_lds(const float *X, const float *W, const float *scale, const float *shift, const float *res, float *Y,
+                           const float *Wd, const float *dscale, const float *dshift, float *Yd, int B, int Hin, int Ho, int C, int N,
+                           int stride, int relu, hipStream_t s);
+
 // ---- reconstruction -----------------------------------------------------------------
 // basis: pre-packed per 32-vertex tile in MFMA-operand lane order (see recon_kernels.hip):
 //   Bp[tile][coord x|y|z][chunk][lane][4], K = 52: 0..39 shape, 40..49 expression,

@@ -280,11 +280,12 @@ const ResNet50 &resnet50() {
 constexpr int kArchMb1First = 2, kArchLast = 4;
 bool is_mb1(int arch) { return arch >= kArchMb1First && arch <= kArchLast; }
 // The whole id table: 0 mobilenet_v2 | 1 resnet50 | 2 mobilenet_1 | 3 mobilenet_05 | 4 mobilenet_2 | 5: never assigned | 6 ghostnet |
-// 7: never assigned | 8 resnest50.
-constexpr int kArchGhost = 6, kArchResnest = 8;
+// 7: never assigned | 8 resnest50 | 9: never assigned | 10 resnet18 | 11 resnet34.
+constexpr int kArchGhost = 6, kArchResnest = 8, kArchRes18 = 10, kArchRes34 = 11;
 bool is_gn(int arch) { return arch == kArchGhost; }
 bool is_rs(int arch) { return arch == kArchResnest; }
-bool arch_known(int arch) { return (arch >= 0 && arch <= kArchLast) || arch == kArchGhost || arch == kArchResnest; }
+bool is_bb(int arch) { return arch == kArchRes18 || arch == kArchRes34; }      // the BasicBlock ResNets
+bool arch_known(int arch) { return (arch >= 0 && arch <= kArchLast) || arch == kArchGhost || arch == kArchResnest || is_bb(arch); }
 const char *arch_name(int arch) {
     switch (arch) {
     case 0: return "mobilenet_v2";
@@ -294,6 +295,8 @@ const char *arch_name(int arch) {
     case 4: return "mobilenet_2";
     case kArchGhost: return "ghostnet";
     case kArchResnest: return "resnest50";
+    case kArchRes18: return "resnet18";
+    case kArchRes34: return "resnet34";
     default: return "?";
     }
 }
@@ -562,6 +565,73 @@ const RsNet &rsnet() {
     return n;
 }
 
+// ---- resnet18 / resnet34 (reference backbone_nets/resnet_backbone.py:50-87 BasicBlock, :141-249 ResNet, :282-301), arch ids 10 / 11.
+// Stem 7x7 / 2 3 -> 64 + BN + ReLU, max pool, [2,2,2,2] / [3,4,6,3] BasicBlocks of 64 / 128 / 256 / 512 channels on 30^2 / 15^2 / 8^2 /
+// 4^2, global mean, four heads.  A BasicBlock: conv1 3x3 (stride 2 on layer2.0 / 3.0 / 4.0) + BN + ReLU, conv2 3x3 + BN, + identity (a
+// 1x1 stride-2 convolution + BN of the input on those three blocks), ReLU.  One table, parametrised by the block counts, serves both.
+struct BbConv { int cin = 0, cout = 0, k = 3; size_t src = 0, dst_w = 0, dst_scale = 0, dst_shift = 0; };      // flat: weight [cout][cin][k][k], bn x4; packed [cout][tap][cin]
+struct BbBlock {
+    int cin, C, hin, hout, stride;
+    bool down;
+    BbConv c1, c2, ds;
+};
+struct BbNet {
+    static constexpr int kPool = 512;
+    std::vector<BbBlock> blocks;
+    BbConv stem;                                               // packed [147][64] (row ci*49 + ky*7 + kx), as resnet_stem_kernel reads it
+    size_t flat_count = 0, packed_count = 0, src_fc = 0, dst_fc_w = 0, dst_fc_b = 0;
+    size_t buf_io = 0, buf_stem = 0, buf_t1 = 0, buf_r = 0;    // per-face floats: block input / output (x 2), the stem's output, conv1's output, the downsample's output
+    double macs = 0, flops = 0;
+    int last() const { return (int)blocks.size() + 1; }        // the hook's block index of pool + heads
+    size_t ws_per_face() const { return 2 * buf_io + buf_stem + buf_t1 + buf_r; }
+    explicit BbNet(const int (&count)[4]) {
+        static const int planes[4] = {64, 128, 256, 512};
+        size_t src = 0, dst = 0;
+        auto conv = [&](int cin, int cout, int k, int hw) {
+            BbConv c; c.cin = cin; c.cout = cout; c.k = k;
+            const size_t nw = (size_t)cout * cin * k * k;
+            c.src = src; src += nw + 4 * (size_t)cout;
+            c.dst_w = dst; dst += nw;
+            c.dst_scale = dst; dst += cout;
+            c.dst_shift = dst; dst += cout;
+            macs += (double)nw * hw;
+            return c;
+        };
+        auto up = [](size_t &m, size_t v) { m = v > m ? v : m; };
+        stem = conv(3, 64, 7, 3600);
+        buf_stem = (size_t)64 * 3600;
+        buf_io = (size_t)64 * 900;
+        int h = 30, cin = 64;
+        for (int l = 0; l < 4; ++l)
+            for (int i = 0; i < count[l]; ++i) {
+                BbBlock b{};
+                b.cin = cin; b.C = planes[l]; b.stride = (l > 0 && i == 0) ? 2 : 1; b.down = b.stride == 2;
+                b.hin = h; b.hout = b.stride == 2 ? (h + 1) / 2 : h;      // 30 -> 15 -> 8 -> 4 (3x3 pad 1 stride 2, and 1x1 stride 2 alike)
+                const int hw = b.hout * b.hout;
+                b.c1 = conv(b.cin, b.C, 3, hw);
+                b.c2 = conv(b.C, b.C, 3, hw);
+                if (b.down) b.ds = conv(b.cin, b.C, 1, hw);
+                up(buf_io, (size_t)b.C * hw);
+                up(buf_t1, (size_t)b.C * hw);
+                if (b.down) up(buf_r, (size_t)b.C * hw);
+                blocks.push_back(b);
+                h = b.hout; cin = b.C;
+            }
+        src_fc = src; src += (size_t)102 * kPool + 102;        // module order: fc_tex, fc_ori, fc_shape, fc_exp
+        dst_fc_w = dst; dst += (size_t)64 * kPool;             // rows 0..61 = ori | shape | exp; fc_tex is in flat (a checkpoint has it) but is not packed
+        dst_fc_b = dst; dst += 64;
+        macs += 62.0 * kPool;                                  // the adapter takes the first 62 outputs: fc_tex does not run
+        flat_count = src;
+        packed_count = dst;
+        flops = 2.0 * macs;
+    }
+};
+const BbNet &bbnet(int arch) {
+    static const int c18[4] = {2, 2, 2, 2}, c34[4] = {3, 4, 6, 3};
+    static const BbNet n18(c18), n34(c34);
+    return arch == kArchRes34 ? n34 : n18;
+}
+
 struct ConstHeader {   // first 256 bytes of an exported constants buffer
     uint64_t magic;
     uint32_t version, has_backbone, has_basis, n_vert, n_lmk, nvp, nlp, arch;
@@ -665,11 +735,12 @@ size_t ws_floats_per_face() {
     const size_t m1 = 2 * mb1net(4).buf_io + mb1net(4).buf_dw;      // the widest MobileNetV1 (equal to rn: the size does not change)
     const size_t two = mb > rn ? mb : rn, gn = gnnet().ws_per_face();      // (GhostNet needs less than half of rn: the size does not change)
     const size_t three = two > m1 ? two : m1, rs = rsnet().ws_per_face();      // (ResNeSt-50 needs 1 123 456 floats, below rn's 1 152 000: likewise)
-    const size_t four = three > gn ? three : gn;
-    return four > rs ? four : rs;    // one activation workspace serves every backbone
+    const size_t four = three > gn ? three : gn, bb = bbnet(kArchRes34).ws_per_face();      // (resnet18 / 34 need 432 000 floats, the stem's 60^2 x 64 output the largest tensor: likewise)
+    const size_t five = four > rs ? four : rs;
+    return five > bb ? five : bb;    // one activation workspace serves every backbone
 }
-size_t backbone_floats(int arch) { return is_rs(arch) ? rsnet().packed_count : is_gn(arch) ? gnnet().packed_count : is_mb1(arch) ? mb1net(arch).packed_count : (arch == 1 ? resnet50().packed_count : net().packed_count); }
-size_t backbone_flat_floats(int arch) { return is_rs(arch) ? rsnet().flat_count : is_gn(arch) ? gnnet().flat_count : is_mb1(arch) ? mb1net(arch).flat_count : (arch == 1 ? resnet50().flat_count : net().flat_count); }
+size_t backbone_floats(int arch) { return is_bb(arch) ? bbnet(arch).packed_count : is_rs(arch) ? rsnet().packed_count : is_gn(arch) ? gnnet().packed_count : is_mb1(arch) ? mb1net(arch).packed_count : (arch == 1 ? resnet50().packed_count : net().packed_count); }
+size_t backbone_flat_floats(int arch) { return is_bb(arch) ? bbnet(arch).flat_count : is_rs(arch) ? rsnet().flat_count : is_gn(arch) ? gnnet().flat_count : is_mb1(arch) ? mb1net(arch).flat_count : (arch == 1 ? resnet50().flat_count : net().flat_count); }
 
 // Both scratch regions only ever grow; growing synchronises the whole device first, so work in flight on another stream
 // (synergynet_amd/streams.py runs the reconstruction of batch i beside the backbone of batch i+1) never loses its buffer.
@@ -1529,6 +1600,94 @@ int run_resnest50(syn_handle *h, const float *img, const uint8_t *img8, int B, f
     return SYN_OK;
 }
 
+// ---- resnet18 / resnet34 forward (ResNet._forward_impl, resnet_backbone.py:227-249) ----
+// Schedule (SYNERGY_HIP_FUSION / syn_set_schedule): 0 = per-layer: every 3x3 convolution reads its taps from global memory
+// (bb_conv3x3_kernel), the downsample of layer2.0 / 3.0 / 4.0 is a launch of its own; 1 = LDS-tiled: bb_conv3x3_lds_kernel, conv1 of those
+// three blocks also produces the downsample; 2 (default) = as 1.  Every output is the same MFMA sequence in both: bit-identical results.
+bool bb_fused(const syn_handle *h) { return h->fusion >= 1; }      // no batch threshold: measured faster at 1, 32, 128 and 1024 faces
+// One block of the forward, the ONLY place the launch arguments are derived: run_resnet_basic walks blocks 0 .. last through it and
+// syn_resnet_basic_block runs one of them.  block 0 = stem + max pool (in8 uint8 HWC crops, or in = normalised fp32 NCHW crops -> out
+// [B,30,30,64]); 1 .. last - 1 = the BasicBlocks (in [B,hin,hin,cin] -> out [B,hout,hout,C]); last = pool + heads (in [B,4,4,512] -> out =
+// param [B,62], pool, nullable, [B,512]).  scr = B x (buf_stem + buf_t1 + buf_r) floats.  mark(code, flops per face) is called after every
+// launch; code: 0 the stem, 1 the max pool; 100 block + step with step 0 conv1 (with the downsample when fused), 1 the downsample,
+// 2 conv2; 100 last pool + heads.
+template <class Mark>
+void bb_launch_block(const BbNet &n, const float *P, int block, bool fused, const float *in, const uint8_t *in8, int B, float *out,
+                     float *pool, float *scr, hipStream_t s, Mark &&mark) {
+    if (block == 0) {
+        syn::launch_resnet_stem(in, in8, P + n.stem.dst_w, P + n.stem.dst_scale, P + n.stem.dst_shift, scr, B, s);
+        mark(0, 2.0 * 147 * 64 * 3600);
+        syn::launch_maxpool3x3s2(scr, out, B, 60, 30, 64, s);
+        mark(1, 0.0);
+        return;
+    }
+    if (block == n.last()) {
+        syn::launch_pool_fc_generic(in, P + n.dst_fc_w, P + n.dst_fc_b, out, pool, B, 16, BbNet::kPool, 62, 62, s);
+        mark(100 * block, 2.0 * BbNet::kPool * 62);
+        return;
+    }
+    const BbBlock &b = n.blocks[block - 1];
+    const int code = 100 * block, H = b.hin, H2 = b.hout;
+    float *t1 = scr + (size_t)B * n.buf_stem, *r = t1 + (size_t)B * n.buf_t1;
+    const double f1 = 2.0 * 9 * b.cin * b.C * H2 * H2, f2 = 2.0 * 9 * b.C * b.C * H2 * H2, fd = 2.0 * b.cin * b.C * H2 * H2;
+    auto conv = [&](const BbConv &c, const BbConv *ds, const float *X, const float *res, float *Y, int hin, int stride) {
+        const float *w = P + c.dst_w, *sc = P + c.dst_scale, *sh = P + c.dst_shift;
+        if (!fused) syn::launch_bb_conv3x3(X, w, sc, sh, res, Y, B, hin, H2, c.cin, c.cout, stride, 1, s);
+        else syn::launch_bb_conv3x3_lds(X, w, sc, sh, res, Y, ds ? P + ds->dst_w : nullptr, ds ? P + ds->dst_scale : nullptr,
+                                        ds ? P + ds->dst_shift : nullptr, ds ? r : nullptr, B, hin, H2, c.cin, c.cout, stride, 1, s);
+    };
+    conv(b.c1, b.down ? &b.ds : nullptr, in, nullptr, t1, H, b.stride);
+    mark(code + 0, f1 + (b.down && fused ? fd : 0.0));
+    if (b.down && !fused) {
+        syn::launch_bb_down1x1(in, P + b.ds.dst_w, P + b.ds.dst_scale, P + b.ds.dst_shift, r, B, H, H2, b.cin, b.C, s);
+        mark(code + 1, fd);
+    }
+    conv(b.c2, nullptr, t1, b.down ? r : in, out, H2, 1);
+    mark(code + 2, f2);
+}
+int bb_launch_count(const BbNet &n, bool fused) {
+    int c = 2 + 1;                // the stem and the max pool; pool + heads
+    for (const BbBlock &b : n.blocks) c += 2 + (b.down && !fused ? 1 : 0);
+    return c;                     // resnet18: 22 per layer, 19 LDS-tiled; resnet34: 38, 35
+}
+// per-face element counts of a hook block's input and output
+void bb_block_counts(const BbNet &n, int block, size_t *n_in, size_t *n_out) {
+    if (block == 0) { *n_in = (size_t)3 * 120 * 120; *n_out = (size_t)900 * 64; }
+    else if (block == n.last()) { *n_in = (size_t)16 * BbNet::kPool; *n_out = 62; }
+    else {
+        const BbBlock &b = n.blocks[block - 1];
+        *n_in = (size_t)b.hin * b.hin * b.cin; *n_out = (size_t)b.hout * b.hout * b.C;
+    }
+}
+
+int run_resnet_basic(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s,
+                     std::vector<hipEvent_t> *marks = nullptr, std::vector<int> *mark_launch = nullptr, std::vector<double> *mark_flops = nullptr) {
+    const BbNet &n = bbnet(h->arch);
+    int rc = ensure_ws(h, B);
+    if (rc) return rc;
+    float *X = h->ws, *Y = X + (size_t)B * n.buf_io, *scr = Y + (size_t)B * n.buf_io;
+    const float *P = h->d_backbone;
+    auto mark = [&](int code, double flops) {
+        if (!marks) return;
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, s);
+        marks->push_back(e);
+        mark_launch->push_back(code);
+        mark_flops->push_back(flops);
+    };
+    mark(-1, 0.0);
+    const bool fused = bb_fused(h);
+    bb_launch_block(n, P, 0, fused, img, img8, B, X, nullptr, scr, s, mark);
+    for (int block = 1; block < n.last(); ++block) {
+        bb_launch_block(n, P, block, fused, X, nullptr, B, Y, nullptr, scr, s, mark);
+        float *t = X; X = Y; Y = t;
+    }
+    bb_launch_block(n, P, n.last(), fused, X, nullptr, B, param, pool, scr, s, mark);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 }  // namespace
 
 namespace syn {
@@ -1614,6 +1773,7 @@ size_t syn_backbone_flat_count(void) { return net().flat_count; }
 double syn_backbone_flops_per_face(void) { return net().flops; }
 double syn_pointwise_flops_per_face(void) { return net().pw_flops; }
 int syn_backbone_launch_count(syn_handle *h) {
+    if (h && is_bb(h->arch)) return bb_launch_count(bbnet(h->arch), bb_fused(h));      // resnet18 19 / 22, resnet34 35 / 38
     if (h && is_rs(h->arch)) return rs_launch_count(rsnet(), rs_fused(h));      // 74 with the fused tail, 95 per layer
     if (h && is_gn(h->arch)) return gn_launch_count(gnnet(), gn_fused(h));      // 79 with the fused modules, 104 per layer
     if (h && is_mb1(h->arch)) return h->fusion >= 1 ? 15 : 28;      // stem + 13 blocks (x 2 per-layer) + pool and heads; schedule 2 below kMb1FusedMinBatch faces: 28
@@ -2190,7 +2350,7 @@ int syn_numerics_report(syn_handle *h, char *buf, size_t n) {
     char line[256];
     int n_fallback = 0;
     if (!h->d_backbone) out = "no backbone loaded\n";
-    else if (is_mb1(h->arch) || is_gn(h->arch) || is_rs(h->arch)) {
+    else if (is_mb1(h->arch) || is_gn(h->arch) || is_rs(h->arch) || is_bb(h->arch)) {
         snprintf(line, sizeof line, "%s: every product is exact fp32 (fp32-input MFMA, fp32 depthwise): no fp16 operand, nothing to prove or guard\n", arch_name(h->arch));
         out = line;
     }
@@ -2670,6 +2830,70 @@ int syn_load_backbone_resnest50(syn_handle *h, const float *flat, size_t n_float
     return SYN_OK;
 }
 
+// ---- resnet18 / resnet34: flat = the module's state_dict order without num_batches_tracked (synergynet_amd.synergy3DMM.resnet_basic_keys) ----
+size_t syn_resnet_basic_flat_count(int arch) { return is_bb(arch) ? bbnet(arch).flat_count : 0; }
+double syn_resnet_basic_flops_per_face(int arch) { return is_bb(arch) ? bbnet(arch).flops : 0.0; }
+
+static void pack_backbone_resnet_basic(int arch, const float *flat, std::vector<float> &pk) {
+    const BbNet &n = bbnet(arch);
+    pk.assign(n.packed_count, 0.f);
+    // BN folding in fp32: scale = gamma / sqrt(var + 1e-5), shift = beta - mean * scale
+    auto conv = [&](const BbConv &c, bool stem) {
+        const int kk = c.k * c.k;
+        const size_t nw = (size_t)c.cout * c.cin * kk;
+        for (int o = 0; o < c.cout; ++o)
+            for (int ci = 0; ci < c.cin; ++ci)
+                for (int t = 0; t < kk; ++t) {
+                    const float v = flat[c.src + ((size_t)o * c.cin + ci) * kk + t];
+                    if (stem) pk[c.dst_w + ((size_t)ci * kk + t) * c.cout + o] = v;      // [ci*49 + ky*7 + kx][64]
+                    else pk[c.dst_w + ((size_t)o * kk + t) * c.cin + ci] = v;            // [n][tap][cin]
+                }
+        const float *bn = flat + c.src + nw;                   // weight | bias | running_mean | running_var
+        for (int i = 0; i < c.cout; ++i) {
+            const float sc = bn[i] / sqrtf(bn[3 * c.cout + i] + 1e-5f);
+            pk[c.dst_scale + i] = sc;
+            pk[c.dst_shift + i] = bn[c.cout + i] - bn[2 * c.cout + i] * sc;
+        }
+    };
+    conv(n.stem, true);
+    for (const BbBlock &b : n.blocks) {
+        conv(b.c1, false);
+        conv(b.c2, false);
+        if (b.down) conv(b.ds, false);
+    }
+    {   // heads: flat order fc_tex, fc_ori, fc_shape, fc_exp; the forward's cat (:246) is ori | shape | exp | tex and the adapter takes the
+        // first 62: rows 0..61 = ori | shape | exp; fc_tex is not packed
+        const float *src = flat + n.src_fc + (size_t)40 * BbNet::kPool + 40;
+        static const int hn[3] = {12, 40, 10};
+        int row = 0;
+        for (int k = 0; k < 3; ++k) {
+            memcpy(pk.data() + n.dst_fc_w + (size_t)row * BbNet::kPool, src, sizeof(float) * hn[k] * BbNet::kPool);
+            src += (size_t)hn[k] * BbNet::kPool;
+            memcpy(pk.data() + n.dst_fc_b + row, src, sizeof(float) * hn[k]);
+            src += hn[k];
+            row += hn[k];
+        }
+    }
+}
+
+int syn_load_backbone_resnet_basic(syn_handle *h, int arch, const float *flat, size_t n_floats) {
+    if (!h || !flat) return fail(SYN_ERR_INVALID, "syn_load_backbone_resnet_basic: NULL argument");
+    if (!is_bb(arch)) return fail(SYN_ERR_INVALID, "syn_load_backbone_resnet_basic: arch=%d, expected 10 (resnet18) or 11 (resnet34)", arch);
+    const BbNet &n = bbnet(arch);
+    if (n_floats != n.flat_count) return fail(SYN_ERR_INVALID, "syn_load_backbone_resnet_basic: got %zu floats, %s has %zu", n_floats, arch_name(arch), n.flat_count);
+    std::vector<float> pk;
+    pack_backbone_resnet_basic(arch, flat, pk);
+    DeviceGuard g(h->device);
+    if (h->d_backbone) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->d_backbone)); h->d_backbone = nullptr; }
+    HIP_TRY(hipMalloc((void **)&h->d_backbone, n.packed_count * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->d_backbone, pk.data(), n.packed_count * sizeof(float), hipMemcpyHostToDevice));
+    h->arch = arch;
+    h->ri = RangeInfo{};
+    h->resnet_fp32 = 0; h->range_events = 0; h->guard_armed = 0; if (h->guard_word) { (void)hipDeviceSynchronize(); *(volatile unsigned *)h->guard_word = 0; }
+    h->resnet_w_unsafe[0] = h->resnet_w_unsafe[1] = h->resnet_w_unsafe[2] = 0;
+    return SYN_OK;
+}
+
 static void pack_basis(const float *w_shp, const float *w_exp, const float *u, const float *param_mean, const float *param_std,
                        const int64_t *keypoints, int n_lmk, int n_vert, std::vector<float> &pk) {
     const int nvp = round_up(n_vert, 32), nlp = round_up(n_lmk, 32);
@@ -2756,7 +2980,8 @@ int syn_pack_constants_host(int arch, const float *backbone_flat, size_t n_float
     if (bytes < need) return fail(SYN_ERR_INVALID, "syn_pack_constants_host: buffer %zu < %zu bytes", bytes, need);
     std::vector<float> bb, bs;
     if (has_bb) {
-        if (is_rs(arch)) pack_backbone_resnest50(backbone_flat, bb);
+        if (is_bb(arch)) pack_backbone_resnet_basic(arch, backbone_flat, bb);
+        else if (is_rs(arch)) pack_backbone_resnest50(backbone_flat, bb);
         else if (is_gn(arch)) pack_backbone_ghostnet(backbone_flat, bb);
         else if (is_mb1(arch)) pack_backbone_mobilenet1(arch, backbone_flat, bb);
         else if (arch == 1) pack_backbone_resnet50(backbone_flat, bb);
@@ -2994,6 +3219,7 @@ int syn_backbone_forward(syn_handle *h, const float *img, int B, float *param, f
     if (B <= 0) return fail(SYN_ERR_INVALID, "syn_backbone_forward: B=%d", B);
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_backbone_forward: backbone weights not loaded");
     DeviceGuard g(h->device);
+    if (is_bb(h->arch)) return run_resnet_basic(h, img, nullptr, B, param, pool, (hipStream_t)stream);
     if (is_rs(h->arch)) return run_resnest50(h, img, nullptr, B, param, pool, (hipStream_t)stream);
     if (is_gn(h->arch)) return run_ghostnet(h, img, nullptr, B, param, pool, (hipStream_t)stream);
     if (is_mb1(h->arch)) return run_mobilenet1(h, img, nullptr, B, param, pool, (hipStream_t)stream);
@@ -3006,6 +3232,7 @@ int syn_backbone_forward_u8(syn_handle *h, const uint8_t *img, int B, float *par
     if (B <= 0) return fail(SYN_ERR_INVALID, "syn_backbone_forward_u8: B=%d", B);
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_backbone_forward_u8: backbone weights not loaded");
     DeviceGuard g(h->device);
+    if (is_bb(h->arch)) return run_resnet_basic(h, nullptr, img, B, param, pool, (hipStream_t)stream);
     if (is_rs(h->arch)) return run_resnest50(h, nullptr, img, B, param, pool, (hipStream_t)stream);
     if (is_gn(h->arch)) return run_ghostnet(h, nullptr, img, B, param, pool, (hipStream_t)stream);
     if (is_mb1(h->arch)) return run_mobilenet1(h, nullptr, img, B, param, pool, (hipStream_t)stream);
@@ -3023,9 +3250,10 @@ int syn_backbone_profile(syn_handle *h, const uint8_t *img_hwc, int B, int max_l
     HIP_TRY(hipMalloc((void **)&param, (size_t)B * 62 * sizeof(float)));
     std::vector<hipEvent_t> marks;
     std::vector<int> feats;
-    if (is_gn(h->arch) || is_rs(h->arch)) {           // launch codes of gn_launch_block / rs_launch_block in feature_of_launch
+    if (is_gn(h->arch) || is_rs(h->arch) || is_bb(h->arch)) {           // launch codes of gn_launch_block / rs_launch_block / bb_launch_block in feature_of_launch
         std::vector<double> fl;
-        int rc = is_rs(h->arch) ? run_resnest50(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats, &fl)
+        int rc = is_bb(h->arch) ? run_resnet_basic(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats, &fl)
+               : is_rs(h->arch) ? run_resnest50(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats, &fl)
                                 : run_ghostnet(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats, &fl);
         int count = 0;
         if (rc == SYN_OK) {
@@ -3208,6 +3436,30 @@ int syn_resnest50_block(syn_handle *h, int block, int fused, const float *in, in
     return SYN_OK;
 }
 
+// One block of the loaded resnet18 / resnet34 on caller-supplied activations (include/synergy_hip.h): the launches are those of
+// run_resnet_basic (bb_launch_block), the intermediates live in the handle's workspace where run_resnet_basic keeps them.  Everything is
+// vetted before a launch.
+int syn_resnet_basic_block(syn_handle *h, int block, int fused, const float *in, int B, size_t n_in, float *out, size_t n_out, void *stream) {
+    if (!h || !in || !out) return fail(SYN_ERR_INVALID, "syn_resnet_basic_block: NULL argument (handle, in and out are required)");
+    if (!is_bb(h->arch)) return fail(SYN_ERR_INVALID, "syn_resnet_basic_block: this handle runs %s, expected resnet18 or resnet34", arch_name(h->arch));
+    const BbNet &n = bbnet(h->arch);
+    if (block < 0 || block > n.last())
+        return fail(SYN_ERR_INVALID, "syn_resnet_basic_block: block=%d, expected 0 (stem + max pool), 1..%d (BasicBlocks) or %d (pool + heads)", block, n.last() - 1, n.last());
+    if (B < 1 || B > 65536) return fail(SYN_ERR_INVALID, "syn_resnet_basic_block: B=%d, expected 1 <= B <= 65536", B);      // 32-bit pixel indices
+    if (fused != 0 && fused != 1) return fail(SYN_ERR_INVALID, "syn_resnet_basic_block: fused=%d, expected 0 or 1", fused);
+    size_t f_in, f_out;
+    bb_block_counts(n, block, &f_in, &f_out);
+    if (n_in != f_in * B || n_out != f_out * B)
+        return fail(SYN_ERR_INVALID, "syn_resnet_basic_block: block %d at B=%d expected n_in=%zu n_out=%zu, got %zu %zu", block, B, f_in * B, f_out * B, n_in, n_out);
+    if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_resnet_basic_block: backbone weights not loaded");
+    DeviceGuard g(h->device);
+    int rc = ensure_ws(h, B);
+    if (rc) return rc;
+    bb_launch_block(n, h->d_backbone, block, fused != 0, in, nullptr, B, out, nullptr, h->ws + 2 * (size_t)B * n.buf_io, (hipStream_t)stream, [](int, double) {});
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 // Profiling hook, not part of include/synergy_hip.h: runs the backbone with the fused block of
 // .features[feature] instrumented; out8 (host) = summed s_memtime ticks of wave 0 per stage
 // {stage0, expand, barrier, depthwise, barrier, project, epilogue} and the workgroup count.
@@ -3215,7 +3467,7 @@ int syn_resnest50_block(syn_handle *h, int block, int fused, const float *in, in
 int syn_debug_profile_block(syn_handle *h, const float *img, int B, int feature, unsigned long long *out8) {
     if (!h || !img || !out8 || B <= 0) return fail(SYN_ERR_INVALID, "syn_debug_profile_block: bad argument");
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_debug_profile_block: backbone weights not loaded");
-    if (is_mb1(h->arch) || is_gn(h->arch) || is_rs(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_profile_block: this handle runs %s", arch_name(h->arch));
+    if (is_mb1(h->arch) || is_gn(h->arch) || is_rs(h->arch) || is_bb(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_profile_block: this handle runs %s", arch_name(h->arch));
     DeviceGuard g(h->device);
     unsigned long long *d = nullptr;
     HIP_TRY(hipMalloc((void **)&d, 32 * sizeof(unsigned long long)));
@@ -3236,7 +3488,7 @@ int syn_debug_profile_block(syn_handle *h, const float *img, int B, int feature,
 int syn_debug_feature(syn_handle *h, const float *img, int B, int feature, float *out, void *stream) {
     if (!h || !img || !out || B <= 0 || feature < 0 || feature > 18) return fail(SYN_ERR_INVALID, "syn_debug_feature: bad argument");
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_debug_feature: backbone weights not loaded");
-    if (is_mb1(h->arch) || is_gn(h->arch) || is_rs(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_feature: this handle runs %s", arch_name(h->arch));
+    if (is_mb1(h->arch) || is_gn(h->arch) || is_rs(h->arch) || is_bb(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_feature: this handle runs %s", arch_name(h->arch));
     DeviceGuard g(h->device);
     return run_backbone(h, img, nullptr, B, nullptr, nullptr, (hipStream_t)stream, feature, out);
 }

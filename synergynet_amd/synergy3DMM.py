@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import abi
 from .params import ParamsPack
 from .synth import (GHOSTNET_HEADS, HEADS, MOBILENET1_HEADS, RESNEST_HEADS, RESNET_HEADS, ghostnet_blocks, mbv2_layers, mobilenet1_blocks,
-                    resnest50_blocks, resnet50_convs)
+                    resnest50_blocks, resnet50_convs, resnet_basic_blocks)
 
 BACKBONE_PREFIX = 'I2P.backbone.'
 _BASIS_BUFFERS = ('param_mean', 'param_std', 'w_shp', 'u', 'w_exp', 'u_base', 'w_shp_base', 'w_exp_base')
@@ -45,11 +45,13 @@ def parse_param_62(param):
     return p, offset, alpha_shp, alpha_exp
 
 
-# backbone ids of the C ABI (include/synergy_hip.h; the `arch` word of the constants header).  5 and 7: never assigned.
-ARCH_IDS = {'mobilenet_v2': 0, 'resnet50': 1, 'mobilenet_1': 2, 'mobilenet_05': 3, 'mobilenet_2': 4, 'ghostnet': 6, 'resnest50': 8}
+# backbone ids of the C ABI (include/synergy_hip.h; the `arch` word of the constants header).  5, 7 and 9: never assigned.
+ARCH_IDS = {'mobilenet_v2': 0, 'resnet50': 1, 'mobilenet_1': 2, 'mobilenet_05': 3, 'mobilenet_2': 4, 'ghostnet': 6, 'resnest50': 8,
+            'resnet18': 10, 'resnet34': 11}
 ARCH_BY_ID = {i: n for n, i in ARCH_IDS.items()}
 ARCH_NAMES = ('mobilenet_v2', 'resnet50', 'mobilenet_1', 'mobilenet_05', 'mobilenet_2')      # ids 0..4 by position (kept for callers that index it)
 _ARCH_CHOICES = ('mobilenet_v2', 'resnet50', 'resnest50', 'ghostnet', 'mobilenet_1', 'mobilenet_05', 'mobilenet_2')      # as the refusal message lists them
+RESNET_BASIC = ('resnet18', 'resnet34')      # the BasicBlock ResNets; named after the bracket of the refusal message
 MOBILENET1_WIDTHS = {'mobilenet_1': 1.0, 'mobilenet_05': 0.5, 'mobilenet_2': 2.0}      # the widths whose channel counts are all multiples of 16
 
 _HDR_MAGIC = 0x53594e4833353558          # "SYNH355X" (csrc/synergy_abi.hip ConstHeader)
@@ -188,8 +190,32 @@ def resnest50_keys():
     return out
 
 
+def resnet_basic_keys(arch: str):
+    """(state_dict key, shape) of every resnet18 / resnet34 tensor in the module's own state_dict() order (num_batches_tracked left out):
+    the order syn_load_backbone_resnet_basic expects, fc_tex included.  Written from the block table (synth.resnet_basic_blocks), not from
+    the module."""
+    bn = ('weight', 'bias', 'running_mean', 'running_var')
+    out = []
+
+    def conv_bn(conv, norm, shape):
+        out.append((conv + '.weight', shape))
+        out.extend((norm + '.' + s, (shape[0],)) for s in bn)
+
+    conv_bn('conv1', 'bn1', (64, 3, 7, 7))
+    for key, cin, c, stride, down in resnet_basic_blocks(arch):
+        conv_bn(key + '.conv1', key + '.bn1', (c, cin, 3, 3))
+        conv_bn(key + '.conv2', key + '.bn2', (c, c, 3, 3))
+        if down:
+            conv_bn(key + '.downsample.0', key + '.downsample.1', (c, cin, 1, 1))
+    for name, n in RESNET_HEADS:
+        out += [(name + '.weight', (n, 512)), (name + '.bias', (n,))]
+    return out
+
+
 def arch_keys(arch: str):
     """The (key, shape) table of a backbone by name."""
+    if arch in RESNET_BASIC:
+        return resnet_basic_keys(arch)
     if arch == 'ghostnet':
         return ghostnet_keys()
     if arch == 'resnest50':
@@ -201,11 +227,11 @@ def arch_keys(arch: str):
 
 def flatten_backbone(sd: dict, prefix: str = '', arch: str = 'mobilenet_v2') -> np.ndarray:
     """state_dict -> the flat fp32 host array of syn_load_backbone[_resnet50 | _mobilenet1 | _ghostnet | _resnest50] (include/synergy_hip.h).
-    For ghostnet and resnest50 the keys under `prefix` must be exactly the module's: a missing or an unexpected key is refused, like a
+    For ghostnet, resnest50, resnet18 and resnet34 the keys under `prefix` must be exactly the module's: a missing or an unexpected key is refused, like a
     wrong shape."""
     parts = []
     table = arch_keys(arch)
-    if arch in ('ghostnet', 'resnest50'):          # strict: exactly the module's tensors
+    if arch in ('ghostnet', 'resnest50') + RESNET_BASIC:          # strict: exactly the module's tensors
         have = {k[len(prefix):] for k in sd if k.startswith(prefix) and not k.endswith('num_batches_tracked')}
         want = {k for k, _ in table}
         if have - want:
@@ -276,10 +302,12 @@ class SynergyNet(nn.Module):
         (main_train.py --arch ghostnet; the reference's module returns only the [B,102] tensor, so its own wrapper cannot run it: here the
         pooled feature is the 1280-vector after conv_head + ReLU that the heads consume, and the synergy refinement accepts it), or
         'resnest50' (main_train.py --arch resnest50, the reference's I2P selector synergy3DMM.py:45-56; the module returns the 62
-        parameters and the 2048 channel means, pool_dim = 2048, so the synergy refinement is refused for it)."""
+        parameters and the 2048 channel means, pool_dim = 2048, so the synergy refinement is refused for it), or the BasicBlock
+        ResNets 'resnet18' / 'resnet34' (main_train.py --arch resnet18; the [:, :62] adapter of resnet50, pool_dim = 512, the refinement
+        refused likewise).  resnet101 / resnet152 and the ResNeXt / wide variants stay refused by name."""
         super().__init__()
         if arch not in ARCH_IDS:
-            raise RuntimeError(f"Please choose [{', '.join(_ARCH_CHOICES)}]")
+            raise RuntimeError(f"Please choose [{', '.join(_ARCH_CHOICES)}], {' or '.join(RESNET_BASIC)}")
         self.arch = arch
         if not torch.cuda.is_available():
             raise RuntimeError('synergynet_amd.SynergyNet needs a ROCm GPU (MI355X); there is no CPU path')
@@ -370,7 +398,11 @@ class SynergyNet(nn.Module):
 
     def _upload_backbone(self):
         flat = flatten_backbone(self.state_dict(), BACKBONE_PREFIX, self.arch)
-        if self.arch == 'resnest50':
+        if self.arch in RESNET_BASIC:
+            a = ARCH_IDS[self.arch]
+            assert flat.size == self._lib.syn_resnet_basic_flat_count(a)
+            abi.check(self._lib.syn_load_backbone_resnet_basic(self._h, a, flat.ctypes.data_as(C.c_void_p), flat.size))
+        elif self.arch == 'resnest50':
             assert flat.size == self._lib.syn_resnest50_flat_count()
             abi.check(self._lib.syn_load_backbone_resnest50(self._h, flat.ctypes.data_as(C.c_void_p), flat.size))
         elif self.arch == 'ghostnet':
@@ -552,6 +584,8 @@ class SynergyNet(nn.Module):
     def pool_dim(self):
         if self.arch in MOBILENET1_WIDTHS:
             return int(1024 * MOBILENET1_WIDTHS[self.arch])
+        if self.arch in RESNET_BASIC:
+            return 512
         return 2048 if self.arch in ('resnet50', 'resnest50') else 1280
 
     def _stream(self):

@@ -359,6 +359,59 @@ def make_resnest50_state(seed: int = 2741) -> dict:
     return sd
 
 
+RESNET_BASIC_LAYERS = {'resnet18': (2, 2, 2, 2), 'resnet34': (3, 4, 6, 3)}
+
+
+def resnet_basic_blocks(arch: str):
+    """Ordered (key, in, out, stride, downsample) of the BasicBlocks of the reference resnet18 / resnet34
+    (backbone_nets/resnet_backbone.py:282-301: layers [2,2,2,2] / [3,4,6,3] of 64 / 128 / 256 / 512 channels).  A block is conv1 3x3
+    (the stride) + bn1 + ReLU, conv2 3x3 + bn2, + identity, ReLU; layer2.0 / 3.0 / 4.0 have stride 2 and a 1x1 stride-2 convolution + BN
+    on the identity (:210-214; layer1.0 has neither: 64 -> 64 at stride 1).  At 120x120 the stem and the max pool give 30^2; the strided
+    blocks give 15^2, 8^2, 4^2."""
+    out, cin = [], 64
+    for l, (c, count) in enumerate(zip((64, 128, 256, 512), RESNET_BASIC_LAYERS[arch])):
+        for i in range(count):
+            s = 2 if l > 0 and i == 0 else 1
+            out.append((f'layer{l + 1}.{i}', cin, c, s, s == 2))
+            cin = c
+    return out
+
+
+def make_resnet_basic_state(arch: str, seed: int = 3187) -> dict:
+    """resnet18 / resnet34 state_dict (numpy fp32, reference key names, num_batches_tracked included).  Conv weights N(0, 2 / fan_in) in
+    front of a ReLU; conv2 N(0, 1 / fan_in) with bn2 gamma U(0.4, 0.7), so the 8 / 16 residual sums neither grow nor let the branch die;
+    the downsample N(0, 1 / fan_in) with gamma U(0.8, 1.2): the identity keeps its size through the three strided blocks; other BN gamma
+    U(0.8, 1.2); running_var U(0.8, 1.25); beta and running_mean 0.05 N.  Heads 0.05 N, head biases 0.1 N (module order: fc_tex first)."""
+    rng = np.random.default_rng(seed + (0 if arch == 'resnet18' else 1))
+    sd = {}
+
+    def conv(key, shape, g):
+        fan_in = shape[1] * shape[2] * shape[3]
+        sd[key + '.weight'] = (rng.standard_normal(shape) * np.sqrt(g / fan_in)).astype(np.float32)
+
+    def bn(key, c, lo=0.8, hi=1.2):
+        sd[key + '.weight'] = rng.uniform(lo, hi, c).astype(np.float32)
+        sd[key + '.bias'] = (rng.standard_normal(c) * 0.05).astype(np.float32)
+        sd[key + '.running_mean'] = (rng.standard_normal(c) * 0.05).astype(np.float32)
+        sd[key + '.running_var'] = rng.uniform(0.8, 1.25, c).astype(np.float32)
+        sd[key + '.num_batches_tracked'] = np.array(1000, dtype=np.int64)
+
+    conv('conv1', (64, 3, 7, 7), 2.0)
+    bn('bn1', 64)
+    for key, cin, c, stride, down in resnet_basic_blocks(arch):
+        conv(key + '.conv1', (c, cin, 3, 3), 2.0)
+        bn(key + '.bn1', c)
+        conv(key + '.conv2', (c, c, 3, 3), 1.0)
+        bn(key + '.bn2', c, 0.4, 0.7)
+        if down:
+            conv(key + '.downsample.0', (c, cin, 1, 1), 1.0)
+            bn(key + '.downsample.1', c)
+    for name, n in RESNET_HEADS:
+        sd[name + '.weight'] = (rng.standard_normal((n, 512)) * 0.05).astype(np.float32)
+        sd[name + '.bias'] = (rng.standard_normal(n) * 0.1).astype(np.float32)
+    return sd
+
+
 def _rotation(yaw, pitch, roll):
     cy, sy = np.cos(yaw), np.sin(yaw)
     cp, sp = np.cos(pitch), np.sin(pitch)
