@@ -589,6 +589,46 @@ int syn_refine_points(syn_handle *h, const float *lmk /*[B 3 68]*/, const float 
 /* MLP_rev: landmarks [B,3,68] in crop space -> whitened parameters [B,62] (ori 12 | shape 40 | expr 10; relu'd like the reference). */
 int syn_landmarks_to_param(syn_handle *h, const float *lmk /*[B 3 68]*/, int B, float *param /*[B 62]*/, void *stream);
 
+/* ---- losses of the training graph's forward (model_building.py:141-157, loss_definition.py) ---- */
+
+/* WingLoss of pred / target [B,3,n_points] -> one float.  d = |target - pred| per element; d < omega: omega log(1 + d / epsilon), else
+ * d - C with C = omega - omega log(1 + omega / epsilon); the sum of the terms over the number of elements that took a branch.  As in the
+ * reference d == omega is linear, a NaN d takes neither branch (neither summed nor counted; all NaN: 0 / 0 = NaN), d = inf gives inf.
+ * Sums in fp64 in an order fixed by B * n_points alone, no floating-point atomics: the same bits on every call and every handle.
+ * Scratch and ordering as syn_refine_landmarks (the handle's synergy scratch; calls on one handle on one stream).  Any backbone.
+ * SYN_ERR_INVALID for NULL pointers, B <= 0, n_points < 1, omega or epsilon not positive; `loss` is then untouched. */
+int syn_wing_loss(syn_handle *h, const float *pred, const float *target, int B, int n_points, float omega, float epsilon,
+                  float *loss /*1 float*/, void *stream);
+
+/* ParamLoss per face, input / target [B,62] -> loss [B].  mode 0 ('normal'): sqrt(mean((a[:12] - b[:12])^2) + mean((a[12:62] - b[12:62])^2));
+ * mode 1 ('only_3dmm'): sqrt(mean((input[:50] - target[12:62])^2)) -- the slices are the reference's own.  A face's loss has the same
+ * bits alone and at any position of any batch.  Any backbone, no scratch.  SYN_ERR_INVALID for NULL pointers, B <= 0, another mode. */
+int syn_param_loss(syn_handle *h, const float *input /*[B 62]*/, const float *target /*[B 62]*/, int B, int mode /*0 normal | 1 only_3dmm*/,
+                   float *loss /*[B]*/, void *stream);
+
+/* SynergyNet.forward(input, target) behind the backbone: the landmarks of `param` and of `target` (as syn_landmarks_pose makes them: crop
+ * space, transform = 1, no ROI), MLP_for on the predicted landmarks, MLP_rev on the refined ones, then ONE launch for the five weighted
+ * losses -- all enqueued on `stream`, no host synchronisation.
+ *   scalars[0] = loss_LMK_f0       = 0.05  WingLoss(landmarks(param), landmarks(target))
+ *   scalars[1] = loss_LMK_pointNet = 0.05  WingLoss(refined landmarks, landmarks(target))
+ *   per_face[0][b] = loss_Param_In   = 0.02  ParamLoss(param, target)
+ *   per_face[1][b] = loss_Param_S2   = 0.02  ParamLoss(param_rev, target, only_3dmm)
+ *   per_face[2][b] = loss_Param_S1S2 = 0.001 ParamLoss(param_rev, param, only_3dmm)
+ * meter (nullable, 8 doubles on the device, zeroed by the caller before the first batch; one call at a time per meter):
+ *   [i] += (batch mean of loss i) * B for the five losses in the order above, [5] += (sum of the five means) * B, [6] += B, [7] += 1
+ *   -- AverageMeter.update(mean, B) of main_train.py:128-134; [i] / [6] is the running average.
+ * Scratch (35.8 KB per face) and its caveat as syn_refine_landmarks.  SYN_ERR_NOT_LOADED before syn_load_synergy / syn_load_basis;
+ * SYN_ERR_INVALID for B <= 0, NULL pointers or a backbone whose pooled feature is not 1280-d; refused before any launch. */
+int syn_synergy_losses(syn_handle *h, const float *param /*[B 62]*/, const float *target /*[B 62]*/, const float *pool /*[B 1280]*/, int B,
+                       float *scalars /*[2]: LMK_f0 | LMK_pointNet*/, float *per_face /*[3][B]: Param_In | Param_S2 | Param_S1S2*/,
+                       double *meter /*nullable: 8 doubles on the device*/, void *stream);
+
+/* CenterCrop(margin, mode='test') of the reference's benchmark loader (utils/ddfa.py:162-243) on uint8 images [B,H,W,C]: the interior
+ * [margin, H - margin) x [margin, W - margin) is copied, everything else becomes 0.  margin = 0: a plain copy; 2 margin >= min(H, W): all
+ * zeros (what the reference's slices give).  in == out is allowed (any other overlap is not).  SYN_ERR_INVALID for NULL pointers, a
+ * dimension <= 0 or margin < 0. */
+int syn_center_crop_u8(syn_handle *h, const uint8_t *in /*[B H W C]*/, int B, int H, int W, int C, int margin, uint8_t *out, void *stream);
+
 /* ---- introspection (bench / profiling) --------------------------------------------- */
 
 /* Number of kernel launches one per-layer syn_backbone_forward issues. */

@@ -447,4 +447,21 @@ void launch_pose(const float *param, const float *mean62, const float *std62, co
 void launch_lmk_pose(const float *param, const float *mean62, const float *std62, const float *basis_lmk, int n_lmk, int nlp, const float *roi,
                      int transform, float *lmk, double *angles, float *t3d, int B, hipStream_t s);
 
+// ---- losses of the training graph's forward + CenterCrop (loss_kernels.hip) ----
+// Batch sums are cut into FIXED chunks, one workgroup each, and folded by the workgroup that finishes last (an integer ticket counter,
+// zero before the launch and zero again after it): the order of every sum depends on the element count only.
+constexpr int kWingChunk = 2048;            // elements per workgroup of wing_loss_kernel
+constexpr int kLossFaces = 8;               // faces per workgroup of synergy_losses_kernel
+inline unsigned wing_chunks(size_t N) { return (unsigned)((N + kWingChunk - 1) / kWingChunk); }
+inline unsigned loss_groups(int B) { return (unsigned)((B + kLossFaces - 1) / kLossFaces); }
+// partial: [wing_chunks(N)][2] doubles of scratch; loss: one float
+void launch_wing_loss(const float *pred, const float *target, size_t N, float omega, float epsilon, double *partial, unsigned *counter,
+                      float *loss, hipStream_t s);
+void launch_param_loss(const float *input, const float *target, int B, int mode /*0 normal | 1 only_3dmm*/, float *loss, hipStream_t s);
+// partial: [loss_groups(B)][8] doubles of scratch; scalars [2], per_face [3][B], meter nullable [8] doubles
+void launch_synergy_losses(const float *param, const float *target, const float *lmk, const float *lmk_gt, const float *lmk_refined,
+                           const float *param_rev, int B, double *partial, unsigned *counter, float *scalars, float *per_face, double *meter,
+                           hipStream_t s);
+void launch_center_crop_u8(const uint8_t *in, uint8_t *out, int B, int H, int W, int C, int margin, hipStream_t s);
+
 }  // namespace syn

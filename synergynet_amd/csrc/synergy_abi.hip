@@ -4393,13 +4393,20 @@ struct SynBlob {
 };
 int pad16(int x) { return (x + 15) / 16 * 16; }
 
+// Behind the sws_bytes of scratch lies a tail that no entry point uses as scratch: the ticket counter of the loss kernels
+// (loss_kernels.hip), zeroed here and left at zero by every launch that uses it.
+constexpr size_t kSwsTail = 256;
 int ensure_sws(syn_handle *h, size_t bytes) {
     if (bytes <= h->sws_bytes) return SYN_OK;
+    bytes = (bytes + 255) / 256 * 256;
     if (h->sws) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->sws)); h->sws = nullptr; h->sws_bytes = 0; }
-    HIP_TRY(hipMalloc(&h->sws, bytes));
+    HIP_TRY(hipMalloc(&h->sws, bytes + kSwsTail));
+    HIP_TRY(hipMemset((char *)h->sws + bytes, 0, kSwsTail));
+    HIP_TRY(hipDeviceSynchronize());
     h->sws_bytes = bytes;
     return SYN_OK;
 }
+unsigned *loss_counter(const syn_handle *h) { return (unsigned *)((char *)h->sws + h->sws_bytes); }
 // scratch of a B-face call (floats): Lc [B,3,68] | pf [B*68,64] | X6 [B,2368] | g6 [B,512] | gf [B,1024]
 constexpr size_t kSwsLc = 3 * syn::kSynPts, kSwsPf = 64 * syn::kSynPts, kSwsX6 = syn::kSynFaceKpad, kSwsG6 = 512, kSwsGf = syn::kSynGlobal;
 constexpr size_t kSwsPerFace = kSwsLc + kSwsPf + kSwsX6 + kSwsG6 + kSwsGf;
@@ -4546,6 +4553,74 @@ int syn_landmarks_to_param(syn_handle *h, const float *lmk, int B, float *param,
     syn::launch_syn_trunk(trunk_weights(h, 1), lmk, B, nullptr, gf, syn::kSynGlobal, nullptr, s);
     syn::launch_syn_face_gemm(gf, syn::kSynGlobal, h->d_syn + o.Wrev, syn::kSynGlobal, h->d_syn + o.scale_rev, h->d_syn + o.shift_rev, param,
                               SYN_PARAM_DIM, SYN_PARAM_DIM, B, s);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Losses of the training graph's forward (model_building.py:141-157) and the benchmark loader's CenterCrop (kernels: loss_kernels.hip)
+// ---------------------------------------------------------------------------------------------
+int syn_wing_loss(syn_handle *h, const float *pred, const float *target, int B, int n_points, float omega, float epsilon, float *loss,
+                  void *stream) {
+    if (!h || !pred || !target || !loss) return fail(SYN_ERR_INVALID, "syn_wing_loss: NULL argument");
+    if (B <= 0) return fail(SYN_ERR_INVALID, "syn_wing_loss: B=%d", B);
+    if (n_points < 1) return fail(SYN_ERR_INVALID, "syn_wing_loss: n_points=%d", n_points);
+    if (!(omega > 0.f) || !(epsilon > 0.f)) return fail(SYN_ERR_INVALID, "syn_wing_loss: omega=%g epsilon=%g", (double)omega, (double)epsilon);
+    DeviceGuard g(h->device);
+    const size_t N = (size_t)B * 3 * (size_t)n_points;
+    int rc = ensure_sws(h, (size_t)syn::wing_chunks(N) * 2 * sizeof(double));
+    if (rc != SYN_OK) return rc;
+    syn::launch_wing_loss(pred, target, N, omega, epsilon, (double *)h->sws, loss_counter(h), loss, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+int syn_param_loss(syn_handle *h, const float *input, const float *target, int B, int mode, float *loss, void *stream) {
+    if (!h || !input || !target || !loss) return fail(SYN_ERR_INVALID, "syn_param_loss: NULL argument");
+    if (B <= 0) return fail(SYN_ERR_INVALID, "syn_param_loss: B=%d", B);
+    if (mode != 0 && mode != 1) return fail(SYN_ERR_INVALID, "syn_param_loss: mode=%d (0 normal, 1 only_3dmm)", mode);
+    DeviceGuard g(h->device);
+    syn::launch_param_loss(input, target, B, mode, loss, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+int syn_synergy_losses(syn_handle *h, const float *param, const float *target, const float *pool, int B, float *scalars, float *per_face,
+                       double *meter, void *stream) {
+    if (!h || !param || !target || !pool || !scalars || !per_face) return fail(SYN_ERR_INVALID, "syn_synergy_losses: NULL argument");
+    if (B <= 0) return fail(SYN_ERR_INVALID, "syn_synergy_losses: B=%d", B);
+    int rc = synergy_ready(h, "syn_synergy_losses");
+    if (rc != SYN_OK) return rc;
+    if (!h->d_basis) return fail(SYN_ERR_NOT_LOADED, "syn_synergy_losses: 3DMM basis not loaded");
+    if (h->n_lmk != syn::kSynPts) return fail(SYN_ERR_INVALID, "syn_synergy_losses: the landmark basis has %d points, the MLPs take %d", h->n_lmk, syn::kSynPts);
+    DeviceGuard g(h->device);
+    // behind the refinement's scratch: Lgt [B,3,68] | Lr [B,3,68] | param_rev [B,64] | chunk sums [groups][8] doubles
+    const size_t groups = syn::loss_groups(B);
+    rc = ensure_sws(h, (kSwsPerFace + 2 * kSwsLc + 64) * B * sizeof(float) + groups * 8 * sizeof(double));
+    if (rc != SYN_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    float *Lc = h->sws, *Lgt = h->sws + kSwsPerFace * B, *Lr = Lgt + kSwsLc * B, *prev = Lr + kSwsLc * B;
+    double *partial = (double *)(prev + (size_t)64 * B);
+    syn::launch_lmk_pose(param, basis_mean(h), basis_std(h), basis_lmk(h), h->n_lmk, h->nlp, nullptr, 1, Lc, nullptr, nullptr, B, s);
+    syn::launch_lmk_pose(target, basis_mean(h), basis_std(h), basis_lmk(h), h->n_lmk, h->nlp, nullptr, 1, Lgt, nullptr, nullptr, B, s);
+    rc = run_refine(h, Lc, pool, param, B, nullptr, Lr, nullptr, s);
+    if (rc != SYN_OK) return rc;
+    float *gf = h->sws + (kSwsPerFace - kSwsGf) * B;
+    const SynOffsets &o = h->syn_off;
+    syn::launch_syn_trunk(trunk_weights(h, 1), Lr, B, nullptr, gf, syn::kSynGlobal, nullptr, s);
+    syn::launch_syn_face_gemm(gf, syn::kSynGlobal, h->d_syn + o.Wrev, syn::kSynGlobal, h->d_syn + o.scale_rev, h->d_syn + o.shift_rev, prev,
+                              SYN_PARAM_DIM, SYN_PARAM_DIM, B, s);
+    syn::launch_synergy_losses(param, target, Lc, Lgt, Lr, prev, B, partial, loss_counter(h), scalars, per_face, meter, s);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+int syn_center_crop_u8(syn_handle *h, const uint8_t *in, int B, int H, int W, int C, int margin, uint8_t *out, void *stream) {
+    if (!h || !in || !out) return fail(SYN_ERR_INVALID, "syn_center_crop_u8: NULL argument");
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return fail(SYN_ERR_INVALID, "syn_center_crop_u8: B=%d H=%d W=%d C=%d", B, H, W, C);
+    if (margin < 0) return fail(SYN_ERR_INVALID, "syn_center_crop_u8: margin=%d", margin);
+    DeviceGuard g(h->device);
+    syn::launch_center_crop_u8(in, out, B, H, W, C, margin, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return SYN_OK;
 }

@@ -32,6 +32,9 @@ from .synth import (GHOSTNET_HEADS, HEADS, MOBILENET1_HEADS, RESNEST_HEADS, RESN
                     resnest50_blocks, resnet50_convs, resnet_basic_blocks)
 
 BACKBONE_PREFIX = 'I2P.backbone.'
+# the keys of SynergyNet.forward's dict in the reference's order (model_building.py:80-85), weights 0.05 / 0.05 / 0.02 / 0.02 / 0.001
+LOSS_NAMES = ('loss_LMK_f0', 'loss_LMK_pointNet', 'loss_Param_In', 'loss_Param_S2', 'loss_Param_S1S2')
+PARAM_LOSS_MODES = ('normal', 'only_3dmm')
 _BASIS_BUFFERS = ('param_mean', 'param_std', 'w_shp', 'u', 'w_exp', 'u_base', 'w_shp_base', 'w_exp_base')
 
 
@@ -788,6 +791,81 @@ class SynergyNet(nn.Module):
         param, pool = self.forward_test(self._dev_f32(input), return_pool=True)
         lmk_refined, lmk = self.refine_landmarks(param, pool, return_coarse=True)
         return dict(param=param, lmk=lmk, lmk_refined=lmk_refined, param_rev=self.landmarks_to_param(lmk_refined))
+
+    # ------------------------------------------------------------------ losses of the training graph's forward
+    def get_losses(self):
+        """reference model_building.py:164-165: the keys of forward's dict, in its order"""
+        return LOSS_NAMES
+
+    def wing_loss(self, pred, target, omega=10, epsilon=2):
+        """reference loss_definition.py WingLoss on [B,3,n] tensors -> 0-d device tensor (syn_wing_loss; any backbone)"""
+        p, t = self._dev_f32(pred), self._dev_f32(target)
+        if p.dim() != 3 or p.shape[1] != 3 or p.shape[0] < 1 or p.shape[2] < 1:
+            raise RuntimeError(f'pred must be [B,3,n], got {tuple(p.shape)}')
+        if t.shape != p.shape:
+            raise RuntimeError(f'target must have the shape of pred {tuple(p.shape)}, got {tuple(t.shape)}')
+        with torch.cuda.device(self.device):
+            out = torch.empty((), dtype=torch.float32, device=self.device)
+            abi.check(self._lib.syn_wing_loss(self._h, p.data_ptr(), t.data_ptr(), p.shape[0], p.shape[2], float(omega), float(epsilon),
+                                              out.data_ptr(), self._stream()))
+        return out
+
+    def param_loss(self, input, target, mode='normal'):
+        """reference loss_definition.py ParamLoss on [B,62] tensors -> [B] device tensor (syn_param_loss; any backbone)"""
+        if mode not in PARAM_LOSS_MODES:
+            raise RuntimeError(f"mode must be 'normal' or 'only_3dmm', got {mode!r}")
+        a, b = self._check_faces('input', input, (62,)), self._check_faces('target', target, (62,))
+        if a.shape[0] != b.shape[0] or a.shape[0] < 1:
+            raise RuntimeError('input and target must hold the same number of faces (at least one)')
+        with torch.cuda.device(self.device):
+            out = torch.empty((a.shape[0],), dtype=torch.float32, device=self.device)
+            abi.check(self._lib.syn_param_loss(self._h, a.data_ptr(), b.data_ptr(), a.shape[0], PARAM_LOSS_MODES.index(mode), out.data_ptr(),
+                                               self._stream()))
+        return out
+
+    def _losses(self, param, pool, target, meter=None):
+        t = self._check_faces('target', target, (62,))
+        B = param.shape[0]
+        if t.shape[0] != B:
+            raise RuntimeError(f'target must be [{B},62] (one row per face of the input), got {tuple(t.shape)}')
+        if meter is not None and not (isinstance(meter, torch.Tensor) and meter.dtype == torch.float64 and tuple(meter.shape) == (8,)
+                                      and meter.device == self.device and meter.is_contiguous()):
+            raise RuntimeError(f'meter must be a contiguous float64 [8] tensor on {self.device}')
+        with torch.cuda.device(self.device):
+            scalars = torch.empty((2,), dtype=torch.float32, device=self.device)
+            per_face = torch.empty((3, B), dtype=torch.float32, device=self.device)
+            abi.check(self._lib.syn_synergy_losses(self._h, param.data_ptr(), t.data_ptr(), pool.data_ptr(), B, scalars.data_ptr(),
+                                                   per_face.data_ptr(), meter.data_ptr() if meter is not None else None, self._stream()))
+        return dict(zip(LOSS_NAMES, (scalars[0], scalars[1], per_face[0], per_face[1], per_face[2])))
+
+    def forward(self, input, target, meter=None):
+        """reference model_building.py:141-157: [B,3,120,120] crops (whatever forward_test takes) and the whitened [B,62] target -> the
+        dict of the five weighted losses, device tensors: the two landmark losses 0-d, the three parameter losses [B].  Forward only.
+        meter: a zeroed float64 [8] device tensor the batch is added to (include/synergy_hip.h syn_synergy_losses; `validate`)."""
+        self._need_synergy()
+        param, pool = self.forward_test(self._dev_f32(input), return_pool=True)
+        return self._losses(param, pool, target, meter)
+
+    def losses_crops_u8(self, crops, target, meter=None):
+        """`forward` from uint8 crops [B,120,120,3] (what forward_crops_u8 takes)"""
+        self._need_synergy()
+        param, pool = self.forward_crops_u8(crops, return_pool=True)
+        return self._losses(param, pool, target, meter)
+
+    def validate(self, batches):
+        """The bookkeeping of main_train.py:106-134 over an iterable of (crops or input, target) batches: every batch goes through
+        `losses_crops_u8` (uint8 crops) or `forward` with ONE device-side meter, which is read once at the end -- no device-to-host
+        copy inside the loop.  -> {name: average} for the five losses and 'loss_total'; each batch's mean weighs in with its size, as
+        AverageMeter.update(mean, B) does."""
+        self._need_synergy()
+        meter = torch.zeros((8,), dtype=torch.float64, device=self.device)
+        for x, target in batches:
+            u8 = x.dtype == torch.uint8 if isinstance(x, torch.Tensor) else np.asarray(x).dtype == np.uint8
+            (self.losses_crops_u8 if u8 else self.forward)(x, target, meter=meter)
+        m = meter.cpu().numpy()
+        if m[6] == 0:
+            raise RuntimeError('validate: no batches')
+        return {name: float(m[i] / m[6]) for i, name in enumerate(LOSS_NAMES + ('loss_total',))}
 
     def pose_matrix_batch(self, param):
         """Batched predict_pose(..., ret_mat=True) (utils/inference.py:146-157): [B,3,4] fp32 = [R | t3d] of parse_pose
