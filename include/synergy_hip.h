@@ -623,6 +623,49 @@ int syn_synergy_losses(syn_handle *h, const float *param /*[B 62]*/, const float
                        float *scalars /*[2]: LMK_f0 | LMK_pointNet*/, float *per_face /*[3][B]: Param_In | Param_S2 | Param_S1S2*/,
                        double *meter /*nullable: 8 doubles on the device*/, void *stream);
 
+/* ---- backward of the loss head and of its two loss modules (vector-Jacobian products) ---- */
+
+/* The vector-Jacobian product of the loss head of syn_synergy_losses: given what flows into each of the five losses it returns the
+ * gradients of the head's two inputs, d_param [B,62] and d_pool [B,1280] (what main_train.py:138 needs at the backbone boundary).
+ *   g_scalars[2]     upstream gradients of loss_LMK_f0 and loss_LMK_pointNet          (device)
+ *   g_per_face[3][B] upstream gradients of loss_Param_In, loss_Param_S2, loss_Param_S1S2 (device)
+ * Both NULL: 1 for the two scalars and 1 / B for each per-face loss, i.e. the gradient of main_train.py:128-132's loss_total.  Exactly
+ * one of them NULL is SYN_ERR_INVALID.  One C call enqueues the forward launches again, the two WingLoss counts and the backward's
+ * launches; no host synchronisation (but see Scratch).  The head is in the eval() form of the forward (BatchNorm running statistics folded): these are the gradients
+ * of the reference model in eval().  No gradients for the MLPs' weights.  Conventions as torch differentiates the reference: a ReLU
+ * output of 0 passes nothing; the max over the 68 points routes to the FIRST point that attains it; the WingLoss rules of
+ * syn_wing_loss_backward; a face whose param equals its target has NaN in its rows of d_param / d_pool (sqrt'(0) x 0) and no other
+ * face sees it.  fp32: the layers' products, their transposes and the per-face products across faces on the exact-fp32 matrix
+ * instruction with the forward's K walk, the rest ordered fused multiply-adds; no floating-point atomics; a face's gradient
+ * from the three per-face losses has the same bits alone and at any position of any batch, the two WingLoss terms depend on the batch
+ * through their integer counts alone.
+ * Scratch: the forward's 35.8 KB per face + 20 KB per face + 690 KB per face of a pass of at most 512 faces, i.e. up to 362 MB from
+ * 512 faces on -- twenty times what any other entry point keeps; it stays on the handle until syn_destroy.  Growing to it costs a
+ * device-wide synchronisation, a free and an allocation INSIDE the call: only a call that does not grow the scratch is free of host
+ * synchronisation (make one call at the largest batch first).  One stream per handle, as syn_refine_landmarks.  Refusals as
+ * syn_synergy_losses, decided before any launch with the outputs untouched. */
+int syn_synergy_losses_backward(syn_handle *h, const float *param /*[B 62]*/, const float *target /*[B 62]*/, const float *pool /*[B 1280]*/,
+                                int B, const float *g_scalars /*nullable [2]*/, const float *g_per_face /*nullable [3][B]*/,
+                                float *d_param /*[B 62]*/, float *d_pool /*[B 1280]*/, void *stream);
+
+/* d_pred[e] = g slope sign(pred[e] - target[e]) / n for syn_wing_loss(pred, target): slope = omega / (epsilon + d) for d < omega and 1 for
+ * d >= omega with d = |target - pred| in fp32, n = the batch-wide number of elements that took a branch (an integer count, formed on the
+ * device by a first launch).  As torch differentiates the reference: d == 0 gives 0; a NaN d is not counted and receives 0, not NaN;
+ * d = inf is linear, +-1 / n; every d NaN gives all zeros.  The gradient of `target` is the negative of d_pred.  g: one float on the
+ * device, NULL = 1.  fp64 behind the fp32 difference, one rounding; no floating-point sum: the same bits on every call and handle.
+ * Scratch, ordering and the refusals of syn_wing_loss; d_pred is untouched by a refused call. */
+int syn_wing_loss_backward(syn_handle *h, const float *pred, const float *target, int B, int n_points, float omega, float epsilon,
+                           const float *g /*nullable: 1 float on the device*/, float *d_pred /*[B 3 n_points]*/, void *stream);
+
+/* Gradients of syn_param_loss(input, target, mode) for the upstream g [B] (NULL = ones): d_input[b][k] = g[b] diff / (count L[b]) with
+ * count = 12 for k < 12 and 50 behind it (mode 0), 50 for k < 50 and nothing (0) for k >= 50 (mode 1); d_target is the negative at the
+ * target's own positions (mode 1: target[12 + k] against input[k]; target[:12] receives 0).  L[b] == 0 gives NaN (0 / 0, torch's
+ * sqrt'(0) x 0) in that face's gradient and in no other face's.  A face's gradient has the same bits alone and at any position of any
+ * batch.  Either output may be NULL, not both.  No scratch.  Refusals as syn_param_loss; the outputs are then untouched. */
+int syn_param_loss_backward(syn_handle *h, const float *input /*[B 62]*/, const float *target /*[B 62]*/, int B, int mode,
+                            const float *g /*nullable [B]*/, float *d_input /*nullable [B 62]*/, float *d_target /*nullable [B 62]*/,
+                            void *stream);
+
 /* CenterCrop(margin, mode='test') of the reference's benchmark loader (utils/ddfa.py:162-243) on uint8 images [B,H,W,C]: the interior
  * [margin, H - margin) x [margin, W - margin) is copied, everything else becomes 0.  margin = 0: a plain copy; 2 margin >= min(H, W): all
  * zeros (what the reference's slices give).  in == out is allowed (any other overlap is not).  SYN_ERR_INVALID for NULL pointers, a

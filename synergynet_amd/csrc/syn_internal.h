@@ -41,6 +41,12 @@ constexpr int kParam = 62;
 constexpr int kPool = 1280;
 constexpr int kBasisK = 52;         // 40 shape + 10 expression + 1 (mean u, alpha = 1) + 1 zero pad
 constexpr int kVertTile = 32;        // vertices per reconstruction tile (one 32x32 MFMA column block)
+// Element k of basis column j (a vertex of the tile) inside one (tile, coordinate) block of kBasisK x 32 floats of the exact-fp32 tiles
+// (recon_kernels.hip recon_kernel / lmk_pose_kernel): k = 8 t + 4 h + s < 48 at t 256 + (32 h + j) 4 + s, the tail k = 48 + 2 h + s behind
+// them (k = 50: the mean shape, coefficient 1; k = 51: zero pad).  Readers outside recon_kernels.hip go through this.
+constexpr int lmk_tile_offset(int j, int k) {
+    return k < 48 ? (k >> 3) * 256 + (32 * ((k >> 2) & 1) + j) * 4 + (k & 3) : 6 * 256 + (32 * ((k - 48) >> 1) + j) * 2 + ((k - 48) & 1);
+}
 
 // ---- backbone ---------------------------------------------------------------------
 // Activations are NHWC fp32: act[b][y][x][c].
@@ -463,5 +469,37 @@ void launch_synergy_losses(const float *param, const float *target, const float 
                            const float *param_rev, int B, double *partial, unsigned *counter, float *scalars, float *per_face, double *meter,
                            hipStream_t s);
 void launch_center_crop_u8(const uint8_t *in, uint8_t *out, int B, int H, int W, int C, int margin, hipStream_t s);
+
+// ---- backward of the two loss modules (loss_backward_kernels.hip) ----
+// count: [wing_chunks(N) + 1] 64-bit words of scratch (chunk counts, then n); g nullable (1 float: upstream gradient 1); counter as above
+void launch_wing_loss_backward(const float *pred, const float *target, size_t N, float omega, float epsilon, const float *g,
+                               unsigned long long *count, unsigned *counter, float *d_pred, hipStream_t s);
+// g nullable ([B]: ones); d_input / d_target [B,62], either nullable
+void launch_param_loss_backward(const float *input, const float *target, int B, int mode, const float *g, float *d_input, float *d_target,
+                                hipStream_t s);
+void launch_wing_count(const float *pred, const float *target, size_t N, float omega, unsigned long long *count, unsigned *counter, hipStream_t s);
+
+// backward of the whole loss head (loss_backward_kernels.hip head_backward_kernel): one face at a time per workgroup
+constexpr int kHeadWs = 176816;             // floats of scratch per workgroup (the kernel's static_assert pins the layout)
+constexpr int kHeadGroupsMax = 512;         // faces of one pass of the backward's launches: the images stop growing there, a larger batch takes several passes
+constexpr int kHeadFaceFloats = 1024 + 64 + 64 + 64 + 1024 + 512 + 2368;     // per-face vectors between the launches
+struct HeadBwdArgs {
+    SynTrunkW tf, tr;                        // MLP_for / MLP_rev trunks
+    SynHeadW hw;
+    const float *W6f, *Wrev, *sc_rev, *sh_rev;
+    const float *mean, *stdv, *basis;        // de-whitening constants, fp32 landmark tiles
+    const float *param, *target;             // [B,62]
+    const float *Lc, *Lgt, *Lr, *pf, *G6;    // what the forward launches left in scratch
+    const unsigned long long *n0, *n1;       // elements counted by the two WingLosses
+    const float *g_scalars, *g_per_face;     // nullable together: 1 and 1 / B
+    float *ws;                               // the workgroups' images, kHeadWs floats each
+    float *GFRg, *S2g, *GS2g, *DPARg, *DGFRg, *DG6g, *DX6g;     // per face: [1024] [64] [64] [64] [1024] [512] [kSynFaceKpad]
+    float *d_param, *d_pool;
+    int B;
+};
+// phase 0 .. 3 of the walk for faces [b0, b0 + faces), faces <= kHeadGroupsMax (see head_backward_kernel)
+void launch_head_backward_phase(int phase, const HeadBwdArgs &a, int b0, int faces, hipStream_t s);
+// out[b][k] = sum_n G[b][n] W[n][k], W [N][K] row-major with N % 16 == 0 and K % 32 == 0: one wave per 16 faces x 32 outputs
+void launch_face_tgemm(const float *G, int ldg, const float *W, int ldw, int N, float *out, int ldo, int K, int B, hipStream_t s);
 
 }  // namespace syn

@@ -4615,6 +4615,100 @@ int syn_synergy_losses(syn_handle *h, const float *param, const float *target, c
     return SYN_OK;
 }
 
+// Backward of the two loss modules (kernels: loss_backward_kernels.hip)
+int syn_wing_loss_backward(syn_handle *h, const float *pred, const float *target, int B, int n_points, float omega, float epsilon, const float *g,
+                           float *d_pred, void *stream) {
+    if (!h || !pred || !target || !d_pred) return fail(SYN_ERR_INVALID, "syn_wing_loss_backward: NULL argument");
+    if (B <= 0) return fail(SYN_ERR_INVALID, "syn_wing_loss_backward: B=%d", B);
+    if (n_points < 1) return fail(SYN_ERR_INVALID, "syn_wing_loss_backward: n_points=%d", n_points);
+    if (!(omega > 0.f) || !(epsilon > 0.f))
+        return fail(SYN_ERR_INVALID, "syn_wing_loss_backward: omega=%g epsilon=%g", (double)omega, (double)epsilon);
+    DeviceGuard guard(h->device);
+    const size_t N = (size_t)B * 3 * (size_t)n_points;
+    int rc = ensure_sws(h, ((size_t)syn::wing_chunks(N) + 1) * sizeof(unsigned long long));      // chunk counts | n
+    if (rc != SYN_OK) return rc;
+    syn::launch_wing_loss_backward(pred, target, N, omega, epsilon, g, (unsigned long long *)h->sws, loss_counter(h), d_pred, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+int syn_param_loss_backward(syn_handle *h, const float *input, const float *target, int B, int mode, const float *g, float *d_input,
+                            float *d_target, void *stream) {
+    if (!h || !input || !target) return fail(SYN_ERR_INVALID, "syn_param_loss_backward: NULL argument");
+    if (!d_input && !d_target) return fail(SYN_ERR_INVALID, "syn_param_loss_backward: NULL argument (d_input and d_target: at least one output)");
+    if (B <= 0) return fail(SYN_ERR_INVALID, "syn_param_loss_backward: B=%d", B);
+    if (mode != 0 && mode != 1) return fail(SYN_ERR_INVALID, "syn_param_loss_backward: mode=%d (0 normal, 1 only_3dmm)", mode);
+    DeviceGuard guard(h->device);
+    syn::launch_param_loss_backward(input, target, B, mode, g, d_input, d_target, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+// The loss head's backward: the forward launches of syn_synergy_losses (without MLP_rev's and the loss launch), the two WingLoss counts,
+// then per pass of at most kHeadGroupsMax faces the four phases of head_backward_kernel with the per-face GEMMs across faces between
+// them (loss_backward_kernels.hip).  Scratch: the forward's | 2 x (chunks + 1) counts | per-face vectors | the pass's images.
+int syn_synergy_losses_backward(syn_handle *h, const float *param, const float *target, const float *pool, int B, const float *g_scalars,
+                                const float *g_per_face, float *d_param, float *d_pool, void *stream) {
+    if (!h || !param || !target || !pool || !d_param || !d_pool) return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward: NULL argument");
+    if ((g_scalars == nullptr) != (g_per_face == nullptr))
+        return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward: g_scalars and g_per_face are NULL together (the loss_total gradient) or not at all");
+    if (B <= 0) return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward: B=%d", B);
+    int rc = synergy_ready(h, "syn_synergy_losses_backward");
+    if (rc != SYN_OK) return rc;
+    if (!h->d_basis) return fail(SYN_ERR_NOT_LOADED, "syn_synergy_losses_backward: 3DMM basis not loaded");
+    if (h->n_lmk != syn::kSynPts)
+        return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward: the landmark basis has %d points, the MLPs take %d", h->n_lmk, syn::kSynPts);
+    DeviceGuard guard(h->device);
+    const size_t N = (size_t)B * kSwsLc, chunks = syn::wing_chunks(N);
+    const int groups = B < syn::kHeadGroupsMax ? B : syn::kHeadGroupsMax;
+    const size_t fwd_floats = ((kSwsPerFace + 2 * kSwsLc + 64) * B + 3) / 4 * 4, count_words = (2 * (chunks + 1) + 1) / 2 * 2;
+    const size_t face_floats = (size_t)syn::kHeadFaceFloats * B;
+    rc = ensure_sws(h, (fwd_floats + face_floats + (size_t)groups * syn::kHeadWs) * sizeof(float) + count_words * sizeof(unsigned long long));
+    if (rc != SYN_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    float *Lc = h->sws, *Lgt = h->sws + kSwsPerFace * B, *Lr = Lgt + kSwsLc * B;
+    unsigned long long *count = (unsigned long long *)(h->sws + fwd_floats);
+    syn::launch_lmk_pose(param, basis_mean(h), basis_std(h), basis_lmk(h), h->n_lmk, h->nlp, nullptr, 1, Lc, nullptr, nullptr, B, s);
+    syn::launch_lmk_pose(target, basis_mean(h), basis_std(h), basis_lmk(h), h->n_lmk, h->nlp, nullptr, 1, Lgt, nullptr, nullptr, B, s);
+    rc = run_refine(h, Lc, pool, param, B, nullptr, Lr, nullptr, s);
+    if (rc != SYN_OK) return rc;
+    syn::launch_wing_count(Lc, Lgt, N, 10.f, count, loss_counter(h), s);
+    syn::launch_wing_count(Lr, Lgt, N, 10.f, count + chunks + 1, loss_counter(h), s);
+    const SynOffsets &o = h->syn_off;
+    const float *d = h->d_syn;
+    syn::HeadBwdArgs a;
+    a.tf = trunk_weights(h, 0);
+    a.tr = trunk_weights(h, 1);
+    a.hw = {d + o.W6p, d + o.scale6, d + o.shift6, d + o.W7, d + o.scale7, d + o.shift7, d + o.W8, d + o.scale8, d + o.shift8,
+            d + o.W9, d + o.scale9, d + o.shift9};
+    a.W6f = d + o.W6f; a.Wrev = d + o.Wrev; a.sc_rev = d + o.scale_rev; a.sh_rev = d + o.shift_rev;
+    a.mean = basis_mean(h); a.stdv = basis_std(h); a.basis = basis_lmk(h);
+    a.param = param; a.target = target;
+    a.Lc = Lc; a.Lgt = Lgt; a.Lr = Lr; a.pf = h->sws + kSwsLc * B; a.G6 = h->sws + (kSwsLc + kSwsPf + kSwsX6) * B;
+    a.n0 = count + chunks; a.n1 = count + 2 * chunks + 1;
+    a.g_scalars = g_scalars; a.g_per_face = g_per_face;
+    float *pf = (float *)(count + count_words);              // per-face vectors between the launches, then the workgroups' images
+    a.GFRg = pf; a.S2g = a.GFRg + (size_t)syn::kSynGlobal * B; a.GS2g = a.S2g + (size_t)64 * B; a.DPARg = a.GS2g + (size_t)64 * B;
+    a.DGFRg = a.DPARg + (size_t)64 * B; a.DG6g = a.DGFRg + (size_t)syn::kSynGlobal * B; a.DX6g = a.DG6g + (size_t)512 * B;
+    a.ws = pf + face_floats;
+    a.d_param = d_param; a.d_pool = d_pool; a.B = B;
+    for (int b0 = 0; b0 < B; b0 += groups) {                 // a pass of at most kHeadGroupsMax faces: the images are reused by the next one
+        const int nb = B - b0 < groups ? B - b0 : groups;
+        syn::launch_head_backward_phase(0, a, b0, nb, s);
+        syn::launch_syn_face_gemm(a.GFRg + (size_t)syn::kSynGlobal * b0, syn::kSynGlobal, a.Wrev, syn::kSynGlobal, a.sc_rev, a.sh_rev,
+                                  a.S2g + (size_t)64 * b0, 64, SYN_PARAM_DIM, nb, s);
+        syn::launch_head_backward_phase(1, a, b0, nb, s);
+        syn::launch_face_tgemm(a.GS2g + (size_t)64 * b0, 64, a.Wrev, syn::kSynGlobal, 64, a.DGFRg + (size_t)syn::kSynGlobal * b0, syn::kSynGlobal,
+                               syn::kSynGlobal, nb, s);
+        syn::launch_head_backward_phase(2, a, b0, nb, s);
+        syn::launch_face_tgemm(a.DG6g + (size_t)512 * b0, 512, a.W6f, syn::kSynFaceKpad, 512, a.DX6g + (size_t)syn::kSynFaceKpad * b0,
+                               syn::kSynFaceKpad, syn::kSynFaceKpad, nb, s);
+        syn::launch_head_backward_phase(3, a, b0, nb, s);
+    }
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 int syn_center_crop_u8(syn_handle *h, const uint8_t *in, int B, int H, int W, int C, int margin, uint8_t *out, void *stream) {
     if (!h || !in || !out) return fail(SYN_ERR_INVALID, "syn_center_crop_u8: NULL argument");
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return fail(SYN_ERR_INVALID, "syn_center_crop_u8: B=%d H=%d W=%d C=%d", B, H, W, C);

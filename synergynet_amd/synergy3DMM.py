@@ -25,6 +25,7 @@ import warnings
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import abi
 from .params import ParamsPack
@@ -291,6 +292,65 @@ def _download_stream(dev):
     if key not in _DL_STREAMS:
         _DL_STREAMS[key] = torch.cuda.Stream(device=dev)
     return _DL_STREAMS[key]
+
+
+class _WingLossFn(torch.autograd.Function):
+    """SynergyNet.wing_loss under autograd: syn_wing_loss forward, syn_wing_loss_backward for the gradient"""
+
+    @staticmethod
+    def forward(ctx, model, pred, target, omega, epsilon):
+        ctx.model, ctx.omega, ctx.epsilon = model, omega, epsilon
+        ctx.save_for_backward(pred, target)
+        return model._wing_loss(pred, target, omega, epsilon)
+
+    @staticmethod
+    @once_differentiable                                  # first order only: a double backward raises
+    def backward(ctx, grad):
+        pred, target = ctx.saved_tensors
+        g = grad.to(device=pred.device, dtype=torch.float32).contiguous()
+        d = ctx.model._wing_loss_backward(pred, target, ctx.omega, ctx.epsilon, g)
+        return None, d if ctx.needs_input_grad[1] else None, -d if ctx.needs_input_grad[2] else None, None, None
+
+
+class _ParamLossFn(torch.autograd.Function):
+    """SynergyNet.param_loss under autograd: syn_param_loss forward, syn_param_loss_backward for the gradients"""
+
+    @staticmethod
+    def forward(ctx, model, input, target, mode):
+        ctx.model, ctx.mode = model, mode
+        ctx.save_for_backward(input, target)
+        return model._param_loss(input, target, mode)
+
+    @staticmethod
+    @once_differentiable                                  # first order only: a double backward raises
+    def backward(ctx, grad):
+        input, target = ctx.saved_tensors
+        g = grad.to(device=input.device, dtype=torch.float32).contiguous()
+        da, db = ctx.model._param_loss_backward(input, target, ctx.mode, g, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        return None, da, db, None
+
+
+class _LossHeadFn(torch.autograd.Function):
+    """SynergyNet.loss_head under autograd: syn_synergy_losses forward; the backward packs the five incoming gradients into
+    g_scalars [2] / g_per_face [3][B] on the device and calls syn_synergy_losses_backward.  No gradient for target."""
+
+    @staticmethod
+    def forward(ctx, model, param, pool, target):
+        ctx.model = model
+        ctx.save_for_backward(param, pool, target)
+        d = model._losses(param, pool, target)
+        return tuple(d[k].clone() for k in LOSS_NAMES)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        param, pool, target = ctx.saved_tensors
+        B = param.shape[0]
+        f32 = dict(device=param.device, dtype=torch.float32)
+        gs = torch.stack([(g if g is not None else torch.zeros((), **f32)).to(**f32).reshape(()) for g in grads[:2]]).contiguous()
+        gp = torch.stack([(g if g is not None else torch.zeros((B,), **f32)).to(**f32).reshape(B) for g in grads[2:]]).contiguous()
+        d_param, d_pool = ctx.model._losses_backward(param, pool, target, gs, gp)
+        return None, d_param, d_pool, None
 
 
 class SynergyNet(nn.Module):
@@ -804,24 +864,52 @@ class SynergyNet(nn.Module):
             raise RuntimeError(f'pred must be [B,3,n], got {tuple(p.shape)}')
         if t.shape != p.shape:
             raise RuntimeError(f'target must have the shape of pred {tuple(p.shape)}, got {tuple(t.shape)}')
+        if torch.is_grad_enabled() and (p.requires_grad or t.requires_grad):
+            return _WingLossFn.apply(self, p, t, float(omega), float(epsilon))
+        return self._wing_loss(p, t, float(omega), float(epsilon))
+
+    def _wing_loss(self, p, t, omega, epsilon):
         with torch.cuda.device(self.device):
             out = torch.empty((), dtype=torch.float32, device=self.device)
-            abi.check(self._lib.syn_wing_loss(self._h, p.data_ptr(), t.data_ptr(), p.shape[0], p.shape[2], float(omega), float(epsilon),
-                                              out.data_ptr(), self._stream()))
+            abi.check(self._lib.syn_wing_loss(self._h, p.data_ptr(), t.data_ptr(), p.shape[0], p.shape[2], omega, epsilon, out.data_ptr(),
+                                              self._stream()))
+        return out
+
+    def _wing_loss_backward(self, p, t, omega, epsilon, g=None):
+        """syn_wing_loss_backward: the gradient of `pred` for the upstream g (0-d device tensor; None: 1); target's is its negative"""
+        with torch.cuda.device(self.device):
+            out = torch.empty_like(p)
+            abi.check(self._lib.syn_wing_loss_backward(self._h, p.data_ptr(), t.data_ptr(), p.shape[0], p.shape[2], omega, epsilon,
+                                                       g.data_ptr() if g is not None else None, out.data_ptr(), self._stream()))
         return out
 
     def param_loss(self, input, target, mode='normal'):
-        """reference loss_definition.py ParamLoss on [B,62] tensors -> [B] device tensor (syn_param_loss; any backbone)"""
+        """reference loss_definition.py ParamLoss on [B,62] tensors -> [B] device tensor (syn_param_loss; any backbone).  With an input
+        that requires grad the result carries a grad_fn (syn_param_loss_backward); so does `wing_loss`."""
         if mode not in PARAM_LOSS_MODES:
             raise RuntimeError(f"mode must be 'normal' or 'only_3dmm', got {mode!r}")
         a, b = self._check_faces('input', input, (62,)), self._check_faces('target', target, (62,))
         if a.shape[0] != b.shape[0] or a.shape[0] < 1:
             raise RuntimeError('input and target must hold the same number of faces (at least one)')
+        if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad):
+            return _ParamLossFn.apply(self, a, b, PARAM_LOSS_MODES.index(mode))
+        return self._param_loss(a, b, PARAM_LOSS_MODES.index(mode))
+
+    def _param_loss(self, a, b, mode):
         with torch.cuda.device(self.device):
             out = torch.empty((a.shape[0],), dtype=torch.float32, device=self.device)
-            abi.check(self._lib.syn_param_loss(self._h, a.data_ptr(), b.data_ptr(), a.shape[0], PARAM_LOSS_MODES.index(mode), out.data_ptr(),
-                                               self._stream()))
+            abi.check(self._lib.syn_param_loss(self._h, a.data_ptr(), b.data_ptr(), a.shape[0], mode, out.data_ptr(), self._stream()))
         return out
+
+    def _param_loss_backward(self, a, b, mode, g=None, want_input=True, want_target=False):
+        """syn_param_loss_backward -> (d_input or None, d_target or None) for the upstream g ([B] device tensor; None: ones)"""
+        with torch.cuda.device(self.device):
+            da = torch.empty_like(a) if want_input else None
+            db = torch.empty_like(b) if want_target else None
+            abi.check(self._lib.syn_param_loss_backward(self._h, a.data_ptr(), b.data_ptr(), a.shape[0], mode,
+                                                        g.data_ptr() if g is not None else None, da.data_ptr() if want_input else None,
+                                                        db.data_ptr() if want_target else None, self._stream()))
+        return da, db
 
     def _losses(self, param, pool, target, meter=None):
         t = self._check_faces('target', target, (62,))
@@ -837,6 +925,38 @@ class SynergyNet(nn.Module):
             abi.check(self._lib.syn_synergy_losses(self._h, param.data_ptr(), t.data_ptr(), pool.data_ptr(), B, scalars.data_ptr(),
                                                    per_face.data_ptr(), meter.data_ptr() if meter is not None else None, self._stream()))
         return dict(zip(LOSS_NAMES, (scalars[0], scalars[1], per_face[0], per_face[1], per_face[2])))
+
+    def _losses_backward(self, param, pool, target, g_scalars=None, g_per_face=None):
+        B = param.shape[0]
+        with torch.cuda.device(self.device):
+            d_param = torch.empty((B, 62), dtype=torch.float32, device=self.device)
+            d_pool = torch.empty((B, 1280), dtype=torch.float32, device=self.device)
+            abi.check(self._lib.syn_synergy_losses_backward(self._h, param.data_ptr(), target.data_ptr(), pool.data_ptr(), B,
+                                                            g_scalars.data_ptr() if g_scalars is not None else None,
+                                                            g_per_face.data_ptr() if g_per_face is not None else None,
+                                                            d_param.data_ptr(), d_pool.data_ptr(), self._stream()))
+        return d_param, d_pool
+
+    def _head_inputs(self, param, pool, target):
+        self._need_synergy()
+        p, po, t = self._check_faces('param', param, (62,)), self._check_faces('pool', pool, (1280,)), self._check_faces('target', target, (62,))
+        if po.shape[0] != p.shape[0] or t.shape[0] != p.shape[0] or p.shape[0] < 1:
+            raise RuntimeError('param, pool and target must hold the same number of faces (at least one)')
+        return p, po, t
+
+    def loss_head(self, param, pool, target):
+        """The loss head behind any backbone: whitened param [B,62], pooled feature [B,1280], whitened target [B,62] -> the reference's
+        dict of the five weighted losses (keys, order and values of `forward`).  If param or pool requires grad the tensors carry a
+        grad_fn whose backward is syn_synergy_losses_backward (the head in eval() form); target gets no gradient."""
+        p, po, t = self._head_inputs(param, pool, target)
+        if torch.is_grad_enabled() and (p.requires_grad or po.requires_grad):
+            return dict(zip(LOSS_NAMES, _LossHeadFn.apply(self, p, po, t.detach())))
+        return self._losses(p, po, t)
+
+    def loss_total_grad(self, param, pool, target):
+        """(d_param [B,62], d_pool [B,1280]) of main_train.py:128-132's loss_total = the sum of the five losses' means"""
+        p, po, t = self._head_inputs(param, pool, target)
+        return self._losses_backward(p.detach(), po.detach(), t.detach())
 
     def forward(self, input, target, meter=None):
         """reference model_building.py:141-157: [B,3,120,120] crops (whatever forward_test takes) and the whitened [B,62] target -> the
