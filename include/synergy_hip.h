@@ -632,7 +632,7 @@ int syn_synergy_losses(syn_handle *h, const float *param /*[B 62]*/, const float
  * Both NULL: 1 for the two scalars and 1 / B for each per-face loss, i.e. the gradient of main_train.py:128-132's loss_total.  Exactly
  * one of them NULL is SYN_ERR_INVALID.  One C call enqueues the forward launches again, the two WingLoss counts and the backward's
  * launches; no host synchronisation (but see Scratch).  The head is in the eval() form of the forward (BatchNorm running statistics folded): these are the gradients
- * of the reference model in eval().  No gradients for the MLPs' weights.  Conventions as torch differentiates the reference: a ReLU
+ * of the reference model in eval().  No gradients for the MLPs' weights (syn_synergy_losses_backward_weights returns them).  Conventions as torch differentiates the reference: a ReLU
  * output of 0 passes nothing; the max over the 68 points routes to the FIRST point that attains it; the WingLoss rules of
  * syn_wing_loss_backward; a face whose param equals its target has NaN in its rows of d_param / d_pool (sqrt'(0) x 0) and no other
  * face sees it.  fp32: the layers' products, their transposes and the per-face products across faces on the exact-fp32 matrix
@@ -647,6 +647,27 @@ int syn_synergy_losses(syn_handle *h, const float *param /*[B 62]*/, const float
 int syn_synergy_losses_backward(syn_handle *h, const float *param /*[B 62]*/, const float *target /*[B 62]*/, const float *pool /*[B 1280]*/,
                                 int B, const float *g_scalars /*nullable [2]*/, const float *g_per_face /*nullable [3][B]*/,
                                 float *d_param /*[B 62]*/, float *d_pool /*[B 1280]*/, void *stream);
+
+/* syn_synergy_losses_backward plus the gradients of MLP_for's / MLP_rev's weights: fine-tuning with frozen BatchNorm.
+ * d_flat [syn_synergy_flat_count()] has the FLAT layout of syn_load_synergy and receives the gradients of the UNFOLDED tensors: conv
+ * weight and bias, BatchNorm weight and bias; the running_mean / running_var slots receive 0.  Every element is written on every call.
+ * Per layer y = relu(scale (W x) + shift) with g the gradient at y behind the ReLU mask and before the scale, summed over the faces and
+ * (per-point layers) the 68 points: Gx = sum g (x) x, s = sum g; dW = scale Gx, dbias = scale s, dbeta = s, dgamma = rstd (sum_k W Gx +
+ * (bias - mean) s) -- no division by gamma.  Upstream conventions and NULL / NULL as syn_synergy_losses_backward; d_param / d_pool are
+ * optional here and, when given, have that entry's bits.  The products across faces run on the exact-fp32 matrix instruction (a face's
+ * 68 points are 17 whole K steps: no padded row enters a sum), conv5's as ordered fused multiply-adds over faces; no floating-point
+ * atomics; faces are added in ascending order, pass after pass, so the bits are a function of the inputs, B and the pass size alone.
+ * Scratch: that entry's per-face 55.8 KB + 2.3 KB per face + 7.3 MB of accumulators + (690 + 419) KB per face of a pass of at most 256
+ * faces (test knob wgrad_pass), i.e. up to 284 MB; caveats as there.  SYN_ERR_INVALID also for NULL d_flat; refused before any launch. */
+int syn_synergy_losses_backward_weights(syn_handle *h, const float *param /*[B 62]*/, const float *target /*[B 62]*/,
+                                        const float *pool /*[B 1280]*/, int B, const float *g_scalars /*nullable [2]*/,
+                                        const float *g_per_face /*nullable [3][B]*/, float *d_param /*nullable [B 62]*/,
+                                        float *d_pool /*nullable [B 1280]*/, float *d_flat /*[syn_synergy_flat_count()]*/, void *stream);
+
+/* Replaces the MLPs' weights from a flat state that lives on the DEVICE (the layout of syn_load_synergy): folded in fp64 and rounded
+ * once, as the host does, and repacked into the handle's buffers by one launch on `stream`; no host synchronisation, no download.
+ * SYN_ERR_NOT_LOADED unless syn_load_synergy ran once on this handle (the buffers and offsets come from that call). */
+int syn_update_synergy_device(syn_handle *h, const float *flat_dev /*[n] device*/, size_t n, void *stream);
 
 /* d_pred[e] = g slope sign(pred[e] - target[e]) / n for syn_wing_loss(pred, target): slope = omega / (epsilon + d) for d < omega and 1 for
  * d >= omega with d = |target - pred| in fp32, n = the batch-wide number of elements that took a branch (an integer count, formed on the

@@ -156,14 +156,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kHB = 256;                                  // threads per workgroup
-constexpr int kP = kSynPts;                               // 68 = 17 x 4 rows
-static_assert(kP % 4 == 0, "row tiles of four");
-// scratch image of a workgroup (float offsets, all multiples of 4)
-constexpr int oA1 = 0, oA3 = oA1 + kP * 64, oA4 = oA3 + kP * 64, oH6 = oA4 + kP * 128, oH7 = oH6 + kP * 512, oH8 = oH7 + kP * 256,
-              oB1 = oH8 + kP * 128, oB2 = oB1 + kP * 64, oB3 = oB2 + kP * 64, oB4 = oB3 + kP * 64, oD0 = oB4 + kP * 128, oD1 = oD0 + kP * 512,
-              oDA2X = oD1 + kP * 512, oARGF = oDA2X + kP * 64, oARGR = oARGF + 1024, oM9 = oARGR + 1024, oDLR = oM9 + kP * 4,
-              oDLC = oDLR + 208, oEnd = oDLC + 208;
-static_assert(oEnd == kHeadWs, "syn_internal.h kHeadWs");
+static_assert(kSynPts % 4 == 0, "row tiles of four");       // kP = 68 = 17 x 4 rows
+using namespace headimg;                                  // the workgroup's scratch image (syn_internal.h)
+static_assert(headimg::kP == kSynPts, "one row per point");
 
 // The matrix products run on the exact-fp32 matrix instruction v_mfma_f32_16x16x4_f32 with the operand roles and the K walk of the
 // forward (synergy_kernels.hip): MFMA rows = 16 outputs, MFMA columns = 16 points, K 16 at a time, a lane fetches one float4 (k0 + 4 g ..)
@@ -263,10 +258,14 @@ __device__ __forceinline__ void conv1_fwd(const float *L, const float *W, const 
 }
 
 // D <- (Y > 0 ? D scale : 0): the gradient at a layer's matrix product from the gradient at its ReLU output (a select, as torch's)
-__device__ __forceinline__ void mask_scale(float *D, const float *Y, const float *sc, int N) {
+// Gu (nullable): the same gradient WITHOUT the scale, for the weight products; what D receives does not depend on it
+__device__ __forceinline__ void mask_scale(float *D, const float *Y, const float *sc, int N, float *Gu = nullptr) {
     for (int idx = threadIdx.x; idx < kP * N; idx += kHB) {
-        const float d = D[idx] * sc[idx % N];
-        D[idx] = Y[idx] > 0.f ? d : 0.f;
+        const float u = D[idx];
+        const float d = u * sc[idx % N];
+        const bool on = Y[idx] > 0.f;
+        D[idx] = on ? d : 0.f;
+        if (Gu) Gu[idx] = on ? u : 0.f;
     }
     __syncthreads();
 }
@@ -426,6 +425,8 @@ __global__ __launch_bounds__(kHB) void head_backward_kernel(HeadBwdArgs A, int b
         float *GFR = A.GFRg + (size_t)b * kSynGlobal, *S2 = A.S2g + (size_t)b * 64, *GS2 = A.GS2g + (size_t)b * 64, *DPAR = A.DPARg + (size_t)b * 64;
         float *DGF = A.DGFRg + (size_t)b * kSynGlobal, *DG6 = A.DG6g + (size_t)b * 512, *DX6 = A.DX6g + (size_t)b * kSynFaceKpad;
         int *ARGF = (int *)(ws + oARGF), *ARGR = (int *)(ws + oARGR);
+        float *wg = A.wg ? A.wg + (size_t)blockIdx.x * kHeadWg : nullptr;      // unscaled gradients for the weight products
+        auto gu = [wg](int off) -> float * { return wg ? wg + off : nullptr; };
         const float *Lc = A.Lc + (size_t)b * 3 * kP, *Lgt = A.Lgt + (size_t)b * 3 * kP, *Lr = A.Lr + (size_t)b * 3 * kP;
         const float *A2 = A.pf + (size_t)b * kP * 64, *G6 = A.G6 + (size_t)b * 512;
         const float *pa = A.param + (size_t)b * kParam, *tg = A.target + (size_t)b * kParam;
@@ -469,6 +470,7 @@ __global__ __launch_bounds__(kHB) void head_backward_kernel(HeadBwdArgs A, int b
             if (k < 50) ds2 = g1 * 0.02 * (double)(S2[k] - tg[12 + k]) / (50.0 * L1) + g2 * 0.001 * (double)(S2[k] - pa[12 + k]) / (50.0 * L2);
             if (k >= 12 && k < kParam) dpar -= g2 * 0.001 * (double)(S2[k - 12] - pa[k]) / (50.0 * L2);
             GS2[k] = (k < kParam && S2[k] > 0.f) ? (float)ds2 * A.sc_rev[k] : 0.f;
+            if (A.GS2Ug) A.GS2Ug[(size_t)b * 64 + k] = (k < kParam && S2[k] > 0.f) ? (float)ds2 : 0.f;
             DPAR[k] = k < kParam ? (float)dpar : 0.f;
         }
         __syncthreads();
@@ -477,13 +479,13 @@ __global__ __launch_bounds__(kHB) void head_backward_kernel(HeadBwdArgs A, int b
         if constexpr (PH == 2) {
         // ---- MLP_rev backward behind the heads' transpose: max routing, conv5 .. conv1
         conv5_gather(DGF, tr.scale[4], ARGR, tr.W[4], lds, D0);
-        mask_scale(D0, B4, tr.scale[3], 128);
+        mask_scale(D0, B4, tr.scale[3], 128, gu(wR4));
         gemm_nn(D0, 128, tr.W[3], 64, 128, 64, [=](int m, int k, float a) { D1[m * 64 + k] = a; });
-        mask_scale(D1, B3, tr.scale[2], 64);
+        mask_scale(D1, B3, tr.scale[2], 64, gu(wR3));
         gemm_nn(D1, 64, tr.W[2], 64, 64, 64, [=](int m, int k, float a) { D0[m * 64 + k] = a; });
-        mask_scale(D0, B2, tr.scale[1], 64);
+        mask_scale(D0, B2, tr.scale[1], 64, gu(wR2));
         gemm_nn(D0, 64, tr.W[1], 64, 64, 64, [=](int m, int k, float a) { D1[m * 64 + k] = a; });
-        mask_scale(D1, B1, tr.scale[0], 64);
+        mask_scale(D1, B1, tr.scale[0], 64, gu(wR1));
         {
             const double up = (A.g_scalars ? (double)A.g_scalars[1] : 1.0) * 0.05, n1 = (double)A.n1[0];
             conv1_bwd(D1, tr.W[0], DLR, [=](int c, int m) { return wing_elem(Lr[c * kP + m], Lgt[c * kP + m], up, n1, omega, epsilon); });
@@ -500,31 +502,42 @@ __global__ __launch_bounds__(kHB) void head_backward_kernel(HeadBwdArgs A, int b
             }
             D0[idx] = a;
         }
+        if (wg)
+            for (int idx = tid; idx < kP * 4; idx += kHB) {
+                const int m = idx >> 2, c = idx & 3;
+                wg[wG9 + idx] = (c < 3 && M9[m * 4 + c] > 0.f) ? 0.05f * DLR[c * kP + m] : 0.f;
+            }
         __syncthreads();
-        mask_scale(D0, H8, hw.scale8, 128);
+        mask_scale(D0, H8, hw.scale8, 128, gu(wG8));
         gemm_nn(D0, 128, hw.W8, 256, 128, 256, [=](int m, int k, float a) { D1[m * 256 + k] = a; });
-        mask_scale(D1, H7, hw.scale7, 256);
+        mask_scale(D1, H7, hw.scale7, 256, gu(wG7));
         gemm_nn(D1, 256, hw.W7, 512, 256, 512, [=](int m, int k, float a) { D0[m * 512 + k] = a; });
-        mask_scale(D0, H6, hw.scale6, 512);                      // D0 = the gradient at conv6's sums [68][512]
+        mask_scale(D0, H6, hw.scale6, 512, gu(wG6));                    // D0 = the gradient at conv6's sums [68][512]
         gemm_nn(D0, 512, hw.W6p, 64, 512, 64, [=](int m, int k, float a) { DA2X[m * 64 + k] = a; });
         for (int n = tid; n < 512; n += kHB) {                   // the per-face half: the sum over the face's points, in point order
             float a = 0.f;
             for (int p = 0; p < kP; ++p) a += D0[p * 512 + n];
             DG6[n] = a;
         }
+        if (wg)
+            for (int n = tid; n < 512; n += kHB) {               // the same sum of the unscaled gradient
+                float a = 0.f;
+                for (int p = 0; p < kP; ++p) a += wg[wG6 + p * 512 + n];
+                A.DG6Ug[(size_t)b * 512 + n] = a;
+            }
         __syncthreads();
         }
         if constexpr (PH == 3) {
         for (int i = tid; i < kPool; i += kHB) A.d_pool[(size_t)b * kPool + i] = DX6[kSynGlobal + i];
         // ---- max routing, conv5 .. conv1 of MLP_for; conv6's per-point half joins at conv2's output
         conv5_gather(DX6, tf.scale[4], ARGF, tf.W[4], lds, D0);
-        mask_scale(D0, A4, tf.scale[3], 128);
+        mask_scale(D0, A4, tf.scale[3], 128, gu(wF4));
         gemm_nn(D0, 128, tf.W[3], 64, 128, 64, [=](int m, int k, float a) { D1[m * 64 + k] = a; });
-        mask_scale(D1, A3, tf.scale[2], 64);
+        mask_scale(D1, A3, tf.scale[2], 64, gu(wF3));
         gemm_nn(D1, 64, tf.W[2], 64, 64, 64, [=](int m, int k, float a) { D0[m * 64 + k] = a + DA2X[m * 64 + k]; });
-        mask_scale(D0, A2, tf.scale[1], 64);
+        mask_scale(D0, A2, tf.scale[1], 64, gu(wF2));
         gemm_nn(D0, 64, tf.W[1], 64, 64, 64, [=](int m, int k, float a) { D1[m * 64 + k] = a; });
-        mask_scale(D1, A1, tf.scale[0], 64);
+        mask_scale(D1, A1, tf.scale[0], 64, gu(wF1));
         {
             const double up = (A.g_scalars ? (double)A.g_scalars[0] : 1.0) * 0.05, n0 = (double)A.n0[0];
             conv1_bwd(D1, tf.W[0], DLC, [=](int c, int m) { return DLR[c * kP + m] + wing_elem(Lc[c * kP + m], Lgt[c * kP + m], up, n0, omega, epsilon); });

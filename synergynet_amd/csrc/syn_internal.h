@@ -32,7 +32,7 @@ __device__ __forceinline__ void l2_touch_done(unsigned &sink) { asm volatile("s_
 //   SYNERGY_HIP_TEST_KNOBS = "name=value,name=value,..."   (integers; 0x.. hexadecimal accepted)
 // read once per process (synergy_abi.hip); rounds 2-5 had 18 separate SYN_* variables.  Names: lb_chain, lb4_chain, small_f7, head_sliced_in,
 // head_wide_min, f16_pair56, rm_pair56, rm_pair34, rm_band2, rm_band3, stem_band, ablate_stem, recon_no_pk, recon_pk_wpg, recon_wgs, recon_prof,
-// lt_stage, lt_glds, resnet_exact_mask.
+// lt_stage, lt_glds, resnet_exact_mask, wgrad_pass, wgrad_chunk.
 long long test_knob(const char *name, long long dflt);
 bool test_knob_set(const char *name);
 
@@ -496,7 +496,48 @@ struct HeadBwdArgs {
     float *GFRg, *S2g, *GS2g, *DPARg, *DGFRg, *DG6g, *DX6g;     // per face: [1024] [64] [64] [64] [1024] [512] [kSynFaceKpad]
     float *d_param, *d_pool;
     int B;
+    // weight gradients, all three null unless syn_synergy_losses_backward_weights runs the phases: the workgroups' images
+    // of UNSCALED masked gradients (kHeadWg floats each) and, per face, MLP_rev's heads' [64] and conv6's per-face half [512]
+    float *wg = nullptr, *GS2Ug = nullptr, *DG6Ug = nullptr;
 };
+// a workgroup's image (float offsets, all multiples of 4; head_backward_kernel and the weight products of loss_wgrad_kernels.hip)
+namespace headimg {
+constexpr int kP = kSynPts;
+constexpr int oA1 = 0, oA3 = oA1 + kP * 64, oA4 = oA3 + kP * 64, oH6 = oA4 + kP * 128, oH7 = oH6 + kP * 512, oH8 = oH7 + kP * 256,
+              oB1 = oH8 + kP * 128, oB2 = oB1 + kP * 64, oB3 = oB2 + kP * 64, oB4 = oB3 + kP * 64, oD0 = oB4 + kP * 128, oD1 = oD0 + kP * 512,
+              oDA2X = oD1 + kP * 512, oARGF = oDA2X + kP * 64, oARGR = oARGF + 1024, oM9 = oARGR + 1024, oDLR = oM9 + kP * 4,
+              oDLC = oDLR + 208, oEnd = oDLC + 208;
+static_assert(oEnd == kHeadWs, "kHeadWs");
+// the image of unscaled gradients g (ReLU mask applied, before the multiplication by the layer's scale), [68][N] each:
+// MLP_rev conv4 .. conv1 | MLP_for conv9 (N = 4, column 3 zero), conv8, conv7, conv6 | MLP_for conv4 .. conv1
+constexpr int wR4 = 0, wR3 = wR4 + kP * 128, wR2 = wR3 + kP * 64, wR1 = wR2 + kP * 64, wG9 = wR1 + kP * 64, wG8 = wG9 + kP * 4,
+              wG7 = wG8 + kP * 128, wG6 = wG7 + kP * 256, wF4 = wG6 + kP * 512, wF3 = wF4 + kP * 128, wF2 = wF3 + kP * 64, wF1 = wF2 + kP * 64,
+              wEnd = wF1 + kP * 64;
+}  // namespace headimg
+constexpr int kHeadWg = headimg::wEnd;      // 104 720 floats
+constexpr int kHeadWgPass = 256;            // default faces per pass of syn_synergy_losses_backward_weights (test knob wgrad_pass)
+constexpr int kHeadWgChunk = 4;             // default faces per chunk of the per-point weight products (test knob wgrad_chunk)
+
+// ---- weight gradients of the loss head (loss_wgrad_kernels.hip) ----
+// The 17 layers of the FLAT layout (MLP_for conv1 .. conv9, MLP_rev conv1 .. conv5, conv6_1 .. conv6_3): offsets in floats
+struct SynFlatLayer { size_t w, bias, bn; int N, K; };      // weight [N][K] | bias [N] | gamma, beta, mean, var [4][N]
+constexpr int kSynFlatLayers = 17;
+SynFlatLayer syn_flat_layer(int i);
+size_t syn_flat_total();
+// Accumulators of Gx = sum g (x) x per layer, [pad16(N)][ld] with the sum s of g in column K (conv6's per-face half has none: its s is
+// that of the per-point half).  They live in scratch for the length of one call.
+struct HeadWgAcc { float *t[2][5], *c6p, *c6f, *c7, *c8, *c9, *rev; float *part; int chunk; };      // part: the chunks' partial tiles of a pass
+size_t head_wgrad_acc_floats();
+size_t head_wgrad_part_floats(int pass, int chunk);      // partial tiles of the per-point layers for a pass cut into chunks of `chunk` faces
+void head_wgrad_acc_carve(float *base, HeadWgAcc &acc);
+// the products of one pass (faces [b0, b0 + nb), images in a.ws / a.wg) added to the accumulators in a fixed order; first: start from 0
+void launch_head_wgrad_pass(const HeadBwdArgs &a, const HeadWgAcc &acc, const float *X6, int b0, int nb, bool first, hipStream_t s);
+// d_flat (every element) from the accumulators and the unfolded flat state on the device
+void launch_head_wgrad_final(const HeadWgAcc &acc, const float *flat, float *d_flat, hipStream_t s);
+// fold + repack a flat state on the device into the kernel-ready image of syn_load_synergy
+struct SynFoldLayer { size_t dstA, dstB, dstScale, dstShift; int ldA, ldB, KA; };    // columns [0, KA) -> dstA, [KA, K) -> dstB
+struct SynFoldTable { SynFoldLayer L[kSynFlatLayers]; };
+void launch_syn_fold_device(const float *flat, float *blob, const SynFoldTable &t, hipStream_t s);
 // phase 0 .. 3 of the walk for faces [b0, b0 + faces), faces <= kHeadGroupsMax (see head_backward_kernel)
 void launch_head_backward_phase(int phase, const HeadBwdArgs &a, int b0, int faces, hipStream_t s);
 // out[b][k] = sum_n G[b][n] W[n][k], W [N][K] row-major with N % 16 == 0 and K % 32 == 0: one wave per 16 faces x 32 outputs

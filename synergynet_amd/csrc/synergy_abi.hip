@@ -691,6 +691,7 @@ struct syn_handle {
     size_t rws_bytes = 0;
     // synergy refinement (syn_load_synergy / syn_refine_* / syn_landmarks_to_param): weights + per-call scratch, grown lazily
     float *d_syn = nullptr;
+    float *d_syn_flat = nullptr;   // the unfolded flat state on the device (weight gradients, syn_update_synergy_device)
     SynOffsets syn_off = {};
     float *sws = nullptr;          // Lc | point features | conv6 face rows | conv6 face sums | global feature
     size_t sws_bytes = 0;
@@ -1762,6 +1763,7 @@ int syn_destroy(syn_handle *h) {
     for (float *p : h->d_texc) if (p) (void)hipFree(p);
     if (h->rws) (void)hipFree(h->rws);
     if (h->d_syn) (void)hipFree(h->d_syn);
+    if (h->d_syn_flat) (void)hipFree(h->d_syn_flat);
     if (h->sws) (void)hipFree(h->sws);
     if (h->d_det) (void)hipFree(h->d_det);
     if (h->dws) (void)hipFree(h->dws);
@@ -4474,6 +4476,7 @@ int syn_fold_synergy_host(const float *flat, size_t n, float *folded, size_t n_f
 int syn_load_synergy(syn_handle *h, const float *flat, size_t n) {
     if (!h || !flat) return fail(SYN_ERR_INVALID, "syn_load_synergy: NULL argument");
     if (n != synergy_flat_count()) return fail(SYN_ERR_INVALID, "syn_load_synergy: %zu floats, expected %zu", n, synergy_flat_count());
+    if (syn::syn_flat_total() != synergy_flat_count()) return fail(SYN_ERR_INVALID, "syn_load_synergy: internal layout mismatch");
     const std::vector<SynFolded> f = fold_mlp(flat, kSynFor, 9), r = fold_mlp(flat + syn_mlp_count(kSynFor, 9, 5), kSynRev, 8);
     SynBlob b;
     SynOffsets o = {};
@@ -4498,6 +4501,8 @@ int syn_load_synergy(syn_handle *h, const float *flat, size_t n) {
     if (h->d_syn) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->d_syn)); h->d_syn = nullptr; }     // replacing: nothing may still read the old weights
     HIP_TRY(hipMalloc(&h->d_syn, b.v.size() * sizeof(float)));
     HIP_TRY(hipMemcpy(h->d_syn, b.v.data(), b.v.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (!h->d_syn_flat) HIP_TRY(hipMalloc(&h->d_syn_flat, n * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->d_syn_flat, flat, n * sizeof(float), hipMemcpyHostToDevice));
     h->syn_off = o;
     return SYN_OK;
 }
@@ -4647,23 +4652,35 @@ int syn_param_loss_backward(syn_handle *h, const float *input, const float *targ
 // The loss head's backward: the forward launches of syn_synergy_losses (without MLP_rev's and the loss launch), the two WingLoss counts,
 // then per pass of at most kHeadGroupsMax faces the four phases of head_backward_kernel with the per-face GEMMs across faces between
 // them (loss_backward_kernels.hip).  Scratch: the forward's | 2 x (chunks + 1) counts | per-face vectors | the pass's images.
-int syn_synergy_losses_backward(syn_handle *h, const float *param, const float *target, const float *pool, int B, const float *g_scalars,
-                                const float *g_per_face, float *d_param, float *d_pool, void *stream) {
-    if (!h || !param || !target || !pool || !d_param || !d_pool) return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward: NULL argument");
-    if ((g_scalars == nullptr) != (g_per_face == nullptr))
-        return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward: g_scalars and g_per_face are NULL together (the loss_total gradient) or not at all");
-    if (B <= 0) return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward: B=%d", B);
-    int rc = synergy_ready(h, "syn_synergy_losses_backward");
+// With d_flat (syn_synergy_losses_backward_weights) the phases also leave the unscaled gradients, every pass is followed
+// by the weight products across its faces (loss_wgrad_kernels.hip) and the call ends with the launch that writes d_flat; behind the
+// scratch above: the images of unscaled gradients | two more per-face vectors | the accumulators | d_param / d_pool where not given.
+static int losses_backward_impl(const char *who, syn_handle *h, const float *param, const float *target, const float *pool, int B,
+                                const float *g_scalars, const float *g_per_face, float *d_param, float *d_pool, float *d_flat, void *stream) {
+    const bool wgt = d_flat != nullptr;
+    int rc = synergy_ready(h, who);
     if (rc != SYN_OK) return rc;
-    if (!h->d_basis) return fail(SYN_ERR_NOT_LOADED, "syn_synergy_losses_backward: 3DMM basis not loaded");
-    if (h->n_lmk != syn::kSynPts)
-        return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward: the landmark basis has %d points, the MLPs take %d", h->n_lmk, syn::kSynPts);
+    if (!h->d_basis) return fail(SYN_ERR_NOT_LOADED, "%s: 3DMM basis not loaded", who);
+    if (h->n_lmk != syn::kSynPts) return fail(SYN_ERR_INVALID, "%s: the landmark basis has %d points, the MLPs take %d", who, h->n_lmk, syn::kSynPts);
     DeviceGuard guard(h->device);
     const size_t N = (size_t)B * kSwsLc, chunks = syn::wing_chunks(N);
-    const int groups = B < syn::kHeadGroupsMax ? B : syn::kHeadGroupsMax;
+    int pass = syn::kHeadGroupsMax;
+    if (wgt) {
+        const long long k = syn::test_knob("wgrad_pass", syn::kHeadWgPass);
+        pass = k < 1 ? 1 : k > syn::kHeadGroupsMax ? syn::kHeadGroupsMax : (int)k;
+    }
+    const int groups = B < pass ? B : pass;
+    int chunk = 1;
+    if (wgt) {
+        const long long k = syn::test_knob("wgrad_chunk", syn::kHeadWgChunk);
+        chunk = k < 1 ? 1 : k > groups ? groups : (int)k;
+    }
     const size_t fwd_floats = ((kSwsPerFace + 2 * kSwsLc + 64) * B + 3) / 4 * 4, count_words = (2 * (chunks + 1) + 1) / 2 * 2;
     const size_t face_floats = (size_t)syn::kHeadFaceFloats * B;
-    rc = ensure_sws(h, (fwd_floats + face_floats + (size_t)groups * syn::kHeadWs) * sizeof(float) + count_words * sizeof(unsigned long long));
+    const size_t wg_floats = wgt ? (size_t)groups * syn::kHeadWg + (size_t)(64 + 512) * B + syn::head_wgrad_acc_floats() + syn::head_wgrad_part_floats(groups, chunk) +
+                                       (d_param ? 0 : (size_t)64 * B) + (d_pool ? 0 : (size_t)syn::kPool * B)
+                                 : 0;
+    rc = ensure_sws(h, (fwd_floats + face_floats + (size_t)groups * syn::kHeadWs + wg_floats) * sizeof(float) + count_words * sizeof(unsigned long long));
     if (rc != SYN_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     float *Lc = h->sws, *Lgt = h->sws + kSwsPerFace * B, *Lr = Lgt + kSwsLc * B;
@@ -4692,6 +4709,21 @@ int syn_synergy_losses_backward(syn_handle *h, const float *param, const float *
     a.DGFRg = a.DPARg + (size_t)64 * B; a.DG6g = a.DGFRg + (size_t)syn::kSynGlobal * B; a.DX6g = a.DG6g + (size_t)512 * B;
     a.ws = pf + face_floats;
     a.d_param = d_param; a.d_pool = d_pool; a.B = B;
+    syn::HeadWgAcc acc = {};
+    if (wgt) {
+        a.wg = a.ws + (size_t)groups * syn::kHeadWs;
+        a.GS2Ug = a.wg + (size_t)groups * syn::kHeadWg;
+        a.DG6Ug = a.GS2Ug + (size_t)64 * B;
+        float *p = a.DG6Ug + (size_t)512 * B;
+        syn::head_wgrad_acc_carve(p, acc);
+        p += syn::head_wgrad_acc_floats();
+        acc.part = p;
+        acc.chunk = chunk;
+        p += syn::head_wgrad_part_floats(groups, chunk);
+        if (!d_param) { a.d_param = p; p += (size_t)64 * B; }
+        if (!d_pool) a.d_pool = p;
+    }
+    const float *X6 = h->sws + (kSwsLc + kSwsPf) * B;
     for (int b0 = 0; b0 < B; b0 += groups) {                 // a pass of at most kHeadGroupsMax faces: the images are reused by the next one
         const int nb = B - b0 < groups ? B - b0 : groups;
         syn::launch_head_backward_phase(0, a, b0, nb, s);
@@ -4704,7 +4736,59 @@ int syn_synergy_losses_backward(syn_handle *h, const float *param, const float *
         syn::launch_face_tgemm(a.DG6g + (size_t)512 * b0, 512, a.W6f, syn::kSynFaceKpad, 512, a.DX6g + (size_t)syn::kSynFaceKpad * b0,
                                syn::kSynFaceKpad, syn::kSynFaceKpad, nb, s);
         syn::launch_head_backward_phase(3, a, b0, nb, s);
+        if (wgt) syn::launch_head_wgrad_pass(a, acc, X6, b0, nb, b0 == 0, s);
     }
+    if (wgt) syn::launch_head_wgrad_final(acc, h->d_syn_flat, d_flat, s);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+int syn_synergy_losses_backward(syn_handle *h, const float *param, const float *target, const float *pool, int B, const float *g_scalars,
+                                const float *g_per_face, float *d_param, float *d_pool, void *stream) {
+    if (!h || !param || !target || !pool || !d_param || !d_pool) return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward: NULL argument");
+    if ((g_scalars == nullptr) != (g_per_face == nullptr))
+        return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward: g_scalars and g_per_face are NULL together (the loss_total gradient) or not at all");
+    if (B <= 0) return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward: B=%d", B);
+    return losses_backward_impl("syn_synergy_losses_backward", h, param, target, pool, B, g_scalars, g_per_face, d_param, d_pool, nullptr, stream);
+}
+
+// Weight gradients of MLP_for / MLP_rev in the flat layout; d_param / d_pool are optional here
+int syn_synergy_losses_backward_weights(syn_handle *h, const float *param, const float *target, const float *pool, int B, const float *g_scalars,
+                                        const float *g_per_face, float *d_param, float *d_pool, float *d_flat, void *stream) {
+    if (!h || !param || !target || !pool || !d_flat) return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward_weights: NULL argument");
+    if ((g_scalars == nullptr) != (g_per_face == nullptr))
+        return fail(SYN_ERR_INVALID,
+                    "syn_synergy_losses_backward_weights: g_scalars and g_per_face are NULL together (the loss_total gradient) or not at all");
+    if (B <= 0) return fail(SYN_ERR_INVALID, "syn_synergy_losses_backward_weights: B=%d", B);
+    return losses_backward_impl("syn_synergy_losses_backward_weights", h, param, target, pool, B, g_scalars, g_per_face, d_param, d_pool, d_flat,
+                                stream);
+}
+
+// Replaces the handle's MLP weights from a flat state on the device: a copy into the handle's flat image, then one launch that folds
+// (fp64, one rounding, as fold_mlp) and repacks into the buffers and at the offsets syn_load_synergy set up.  Stream-ordered, no host
+// synchronisation.
+int syn_update_synergy_device(syn_handle *h, const float *flat_dev, size_t n, void *stream) {
+    if (!h || !flat_dev) return fail(SYN_ERR_INVALID, "syn_update_synergy_device: NULL argument");
+    if (n != synergy_flat_count()) return fail(SYN_ERR_INVALID, "syn_update_synergy_device: %zu floats, expected %zu", n, synergy_flat_count());
+    if (!h->d_syn || !h->d_syn_flat) return fail(SYN_ERR_NOT_LOADED, "syn_update_synergy_device: synergy weights not loaded (syn_load_synergy sets up the buffers)");
+    DeviceGuard guard(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (flat_dev != h->d_syn_flat) HIP_TRY(hipMemcpyAsync(h->d_syn_flat, flat_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    const SynOffsets &o = h->syn_off;
+    syn::SynFoldTable t;
+    auto set = [&t](int i, size_t W, int ld, size_t sc, size_t sh) { t.L[i] = {W, 0, sc, sh, ld, 0, syn::syn_flat_layer(i).K}; };
+    for (int which = 0; which < 2; ++which)
+        for (int i = 0; i < 5; ++i) set(which * 9 + i, o.tW[which][i], i == 0 ? 4 : syn::syn_flat_layer(i).K, o.tscale[which][i], o.tshift[which][i]);
+    t.L[5] = {o.W6p, o.W6f, o.scale6, o.shift6, 64, syn::kSynFaceKpad, 64};
+    set(6, o.W7, 512, o.scale7, o.shift7);
+    set(7, o.W8, 256, o.scale8, o.shift8);
+    set(8, o.W9, 128, o.scale9, o.shift9);
+    int row = 0;
+    for (int i = 14; i < 17; ++i) {
+        set(i, o.Wrev + (size_t)row * 1024, 1024, o.scale_rev + row, o.shift_rev + row);
+        row += syn::syn_flat_layer(i).N;
+    }
+    syn::launch_syn_fold_device(h->d_syn_flat, h->d_syn, t, s);
     HIP_TRY(hipGetLastError());
     return SYN_OK;
 }

@@ -353,6 +353,31 @@ class _LossHeadFn(torch.autograd.Function):
         return None, d_param, d_pool, None
 
 
+class _LossHeadWeightsFn(torch.autograd.Function):
+    """_LossHeadFn with the MLPs' learnable tensors among its inputs (model.synergy_parameters()): ONE call of
+    syn_synergy_losses_backward_weights gives d param, d pool and the flat weight gradient, whose slices go to the tensors."""
+
+    @staticmethod
+    def forward(ctx, model, param, pool, target, *weights):
+        ctx.model = model
+        ctx.save_for_backward(param, pool, target)
+        d = model._losses(param, pool, target)
+        return tuple(d[k].clone() for k in LOSS_NAMES)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        param, pool, target = ctx.saved_tensors
+        B = param.shape[0]
+        f32 = dict(device=param.device, dtype=torch.float32)
+        gs = torch.stack([(g if g is not None else torch.zeros((), **f32)).to(**f32).reshape(()) for g in grads[:2]]).contiguous()
+        gp = torch.stack([(g if g is not None else torch.zeros((B,), **f32)).to(**f32).reshape(B) for g in grads[2:]]).contiguous()
+        d_param, d_pool, d_flat = ctx.model._losses_backward_weights(param, pool, target, gs, gp)
+        dw = [d_flat[at:at + n].reshape(shape) if need else None
+              for (at, n, shape), need in zip(ctx.model._syn_slices, ctx.needs_input_grad[4:])]
+        return (None, d_param if ctx.needs_input_grad[1] else None, d_pool if ctx.needs_input_grad[2] else None, None, *dw)
+
+
 class SynergyNet(nn.Module):
     """Drop-in for reference synergy3DMM.SynergyNet (inference only), backed by HIP kernels."""
 
@@ -389,6 +414,8 @@ class SynergyNet(nn.Module):
         self._have_backbone = self._have_basis = False
         self._range_checked = False
         self.has_synergy = False        # MLP_for / MLP_rev weights uploaded (load_weights / load_synergy_state)
+        self._syn_flat = None           # the flat state of the last load_synergy_state (host)
+        self._syn_params = None         # synergy_parameters(): {key: nn.Parameter}, created on first call
         if not load_constants:          # constants arrive later through import_constants() (synergynet_amd/dist.py)
             self.eval()
             from . import inference
@@ -605,6 +632,59 @@ class SynergyNet(nn.Module):
         assert flat.size == self._lib.syn_synergy_flat_count()
         abi.check(self._lib.syn_load_synergy(self._h, flat.ctypes.data_as(C.c_void_p), flat.size))
         self.has_synergy = True
+        self._syn_flat = flat
+        if self._syn_params is not None:                      # the parameters follow the new state; the handle already holds it
+            with torch.no_grad():
+                for k, t in self._syn_tensors.items():
+                    at, n, shape = self._syn_where[k]
+                    t.copy_(torch.from_numpy(flat[at:at + n].reshape(shape)))
+            self._syn_uploaded = self._syn_versions()
+
+    # --- fine-tuning the two point-MLPs with frozen BatchNorm statistics ---
+    def synergy_parameters(self):
+        """Ordered {state_dict key: nn.Parameter} of the learnable tensors of MLP_for / MLP_rev (conv weight and bias, BatchNorm weight
+        and bias; the reference's key names and shapes), device tensors created on the first call from the loaded state.  They are NOT
+        registered on the module: state_dict() and parameters() stay what they were.  `loss_head` returns their gradients when they
+        require grad and re-uploads them when an optimiser has changed them (syn_update_synergy_device)."""
+        self._need_synergy()
+        if self._syn_params is None:
+            from .synth import synergy_layers
+            self._syn_where, self._syn_tensors, at = {}, {}, 0
+            for key, shape in synergy_layers():
+                n = int(np.prod(shape))
+                self._syn_where[key] = (at, n, shape)
+                t = torch.from_numpy(self._syn_flat[at:at + n].reshape(shape).copy()).to(self.device)
+                self._syn_tensors[key] = t if 'running_' in key else nn.Parameter(t)
+                at += n
+            self._syn_params = {k: t for k, t in self._syn_tensors.items() if isinstance(t, nn.Parameter)}
+            self._syn_slices = [self._syn_where[k] for k in self._syn_params]
+            self._syn_uploaded = self._syn_versions()
+        return dict(self._syn_params)
+
+    def _syn_versions(self):
+        return tuple(t._version for t in self._syn_tensors.values())
+
+    def _sync_synergy(self):
+        """the handle's weights follow the parameters: one flat device tensor and syn_update_synergy_device, only after a change"""
+        if self._syn_params is None or self._syn_versions() == self._syn_uploaded:
+            return
+        with torch.cuda.device(self.device), torch.no_grad():
+            flat = torch.cat([t.detach().reshape(-1) for t in self._syn_tensors.values()]).contiguous()
+            abi.check(self._lib.syn_update_synergy_device(self._h, flat.data_ptr(), flat.numel(), self._stream()))
+        self._syn_uploaded = self._syn_versions()
+
+    def synergy_state_dict(self):
+        """the current flat state as {key: tensor} with the reference's key names (load_synergy_state takes it back)"""
+        self._need_synergy()
+        if self._syn_params is not None:
+            return {k: t.detach().clone() for k, t in self._syn_tensors.items()}
+        from .synth import synergy_layers
+        out, at = {}, 0
+        for key, shape in synergy_layers():
+            n = int(np.prod(shape))
+            out[key] = torch.from_numpy(self._syn_flat[at:at + n].reshape(shape).copy()).to(self.device)
+            at += n
+        return out
 
     # --- multi-GPU: rank `src` loads, everybody else receives (SURVEY 8e) ---
     def constants_nbytes(self) -> int:
@@ -798,6 +878,8 @@ class SynergyNet(nn.Module):
         if not self.has_synergy:
             raise RuntimeError('synergy weights not loaded: the checkpoint carried no forwardDirection.* / reverseDirection.* keys '
                                '(load_synergy_state)')
+        if self._syn_params is not None:
+            self._sync_synergy()
 
     def _check_faces(self, name, t, shape):
         t = self._dev_f32(t)
@@ -937,6 +1019,19 @@ class SynergyNet(nn.Module):
                                                             d_param.data_ptr(), d_pool.data_ptr(), self._stream()))
         return d_param, d_pool
 
+    def _losses_backward_weights(self, param, pool, target, g_scalars=None, g_per_face=None):
+        """syn_synergy_losses_backward_weights -> (d_param, d_pool, d_flat [syn_synergy_flat_count()])"""
+        B = param.shape[0]
+        with torch.cuda.device(self.device):
+            d_param = torch.empty((B, 62), dtype=torch.float32, device=self.device)
+            d_pool = torch.empty((B, 1280), dtype=torch.float32, device=self.device)
+            d_flat = torch.empty((int(self._lib.syn_synergy_flat_count()),), dtype=torch.float32, device=self.device)
+            abi.check(self._lib.syn_synergy_losses_backward_weights(self._h, param.data_ptr(), target.data_ptr(), pool.data_ptr(), B,
+                                                                    g_scalars.data_ptr() if g_scalars is not None else None,
+                                                                    g_per_face.data_ptr() if g_per_face is not None else None,
+                                                                    d_param.data_ptr(), d_pool.data_ptr(), d_flat.data_ptr(), self._stream()))
+        return d_param, d_pool, d_flat
+
     def _head_inputs(self, param, pool, target):
         self._need_synergy()
         p, po, t = self._check_faces('param', param, (62,)), self._check_faces('pool', pool, (1280,)), self._check_faces('target', target, (62,))
@@ -947,8 +1042,13 @@ class SynergyNet(nn.Module):
     def loss_head(self, param, pool, target):
         """The loss head behind any backbone: whitened param [B,62], pooled feature [B,1280], whitened target [B,62] -> the reference's
         dict of the five weighted losses (keys, order and values of `forward`).  If param or pool requires grad the tensors carry a
-        grad_fn whose backward is syn_synergy_losses_backward (the head in eval() form); target gets no gradient."""
+        grad_fn whose backward is syn_synergy_losses_backward (the head in eval() form); target gets no gradient.
+        If a tensor of `synergy_parameters()` requires grad, the backward is syn_synergy_losses_backward_weights and also returns
+        their gradients; parameters an optimiser changed are uploaded before the forward."""
         p, po, t = self._head_inputs(param, pool, target)
+        ws = self._syn_params
+        if torch.is_grad_enabled() and ws is not None and any(w.requires_grad for w in ws.values()):
+            return dict(zip(LOSS_NAMES, _LossHeadWeightsFn.apply(self, p, po, t.detach(), *ws.values())))
         if torch.is_grad_enabled() and (p.requires_grad or po.requires_grad):
             return dict(zip(LOSS_NAMES, _LossHeadFn.apply(self, p, po, t.detach())))
         return self._losses(p, po, t)
