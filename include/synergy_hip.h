@@ -720,6 +720,28 @@ int syn_backbone_profile(syn_handle *h, const uint8_t *img_hwc, int B, int max_l
 int syn_mobilenet1_layer(syn_handle *h, int layer, int fused, const void *in, int in_u8, int B, size_t n_in,
                          float *out, size_t n_out, float *aux, size_t n_aux, void *stream);
 
+/* .features[first] .. .features[last] of the loaded mobilenet_v2 (arch 0) on activations the caller supplies -- the hook
+ * tests/test_gpu_mobilenet2_spans.py judges every element of every launch with.  The span runs inside the forward's own launch loop, entered
+ * at `first` and left at `last`, so the launches are the ones the forward selects for this batch size under the handle's schedule
+ * (SYNERGY_HIP_FUSION, SYNERGY_HIP_EARLY_RM, the range verdict, the test knobs); a pair or chain launch that the span cuts is replaced by
+ * the single-block launches, as in syn_backbone_profile's per-block mode.
+ *   first = 0     in = uint8 HWC crops [B,120,120,3] when in_u8 is set, fp32 CHW crops [B,3,120,120] otherwise; last >= 1 (the stem and
+ *                 features.1 share a launch)
+ *   first = 2..18 in = the NHWC fp32 input of .features[first], [B,hin,hin,cin]
+ *   last <= 18    out = the NHWC output of .features[last], [B,hout,hout,cout]
+ *   last = 19     through pool and heads: out = [B,62], a non-NULL aux receives the pool [B,1280] (the hidden-sliced features.17 that the tail
+ *                 adds up while staging its input is only reachable this way)
+ * Returns the number of launches n, or a negative syn_status; launch_tags[i] = what syn_backbone_profile calls feature_of_launch: 1 (stem +
+ * features.1), f (one launch, or the per-layer launches, of .features[f]), 100 a + b (.features[a] .. [b] in one launch, 1517 among them),
+ * 19 (pool + heads).  No events are created.  n_in / n_out / n_aux are ELEMENT counts (n_aux = 0 when aux is NULL).  Refused with
+ * SYN_ERR_INVALID and a message that names what was expected, before any launch, with `out` untouched: a count that differs from what
+ * the span needs, a handle whose arch is not mobilenet_v2, first > last or either outside 0..19 (first = 19 included), first = 1, first = 0
+ * with last = 0, in_u8 with first != 0, aux with last != 19, B < 1 or B > 65536, max_tags below the span's layer count (+ 1 with last = 19:
+ * the most launches any schedule issues).  Asynchronous on `stream`; all pointers but launch_tags are device pointers; the intermediates
+ * live in the handle's workspace (one stream at a time, as the forward). */
+int syn_mobilenet2_span(syn_handle *h, int first, int last, const void *in, int in_u8, int B, size_t n_in, float *out, size_t n_out,
+                        float *aux, size_t n_aux, int *launch_tags, int max_tags, void *stream);
+
 /* One block of the loaded GhostNet (arch 6) on activations the caller supplies, through exactly the launches the forward uses for that
  * block (one helper derives the launch arguments for both) -- the hook tests/test_gpu_ghostnet.py judges every block with.
  *   block 0..15  bottleneck blocks.0.0 .. blocks.8.3: in = NHWC fp32 [B,hin,hin,cin], out = [B,hout,hout,cout]; on a block with

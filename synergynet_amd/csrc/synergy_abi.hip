@@ -860,7 +860,8 @@ void pack_basis_tiles_f16(unsigned *dst, int n_rows_valid, int n_tiles, const fl
 int run_backbone(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s,
                  int stop_feature = -1, float *feature_out = nullptr, int prof_feature = -1,
                  unsigned long long *prof = nullptr, std::vector<hipEvent_t> *marks = nullptr,
-                 std::vector<int> *mark_feature = nullptr) {
+                 std::vector<int> *mark_feature = nullptr, int start_feature = 0, const float *span_in = nullptr,
+                 std::vector<int> *tags = nullptr) {
     const Net &n = net();
     int rc = ensure_ws(h, B);
     if (rc) return rc;
@@ -875,7 +876,8 @@ int run_backbone(syn_handle *h, const float *img, const uint8_t *img8, int B, fl
     auto any_unsafe16 = [&](int first, int last) { for (int f = first; f <= last; ++f) if ((u16 >> f) & 1u) return true; return false; };
     syn::HeadSliced head_sliced{nullptr, 0, nullptr, nullptr};     // features.17 left as hidden-slice partial sums for the tail to add (small batches)
     bool have_head_sliced = false;
-    auto mark = [&](int feature) {          // profiling hook: one event after every launch
+    auto mark = [&](int feature) {          // profiling hook: one event after every launch (syn_mobilenet2_span: the code alone, no event)
+        if (tags) { if (feature >= 0) tags->push_back(feature); return; }
         if (!marks) return;
         hipEvent_t e;
         if (hipEventCreate(&e) != hipSuccess) return;
@@ -884,7 +886,15 @@ int run_backbone(syn_handle *h, const float *img, const uint8_t *img8, int B, fl
         mark_feature->push_back(feature);
     };
     mark(-1);
-    for (size_t li = 0; li < nl; ++li) {
+    // test hook (syn_mobilenet2_span): enter at the first layer of .features[start_feature] with the caller's activations as the block input
+    size_t li0 = 0;
+    if (start_feature >= 2) {
+        while (li0 < nl && n.layers[li0].feature != start_feature) ++li0;
+        if (li0 == nl || !span_in) return SYN_ERR_INVALID;
+        const Layer &L0 = n.layers[li0];
+        HIP_TRY(hipMemcpyAsync(X, span_in, (size_t)B * L0.cin * L0.hin * L0.hin * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    for (size_t li = li0; li < nl; ++li) {
         const Layer &L = n.layers[li];
         const float *w = P + L.dst_w, *sc = P + L.dst_scale, *sh = P + L.dst_shift;
         // fused network head: stem conv + features.1 (dw + linear project) in one launch
@@ -3493,6 +3503,49 @@ int syn_debug_feature(syn_handle *h, const float *img, int B, int feature, float
     if (is_mb1(h->arch) || is_gn(h->arch) || is_rs(h->arch) || is_bb(h->arch)) return fail(SYN_ERR_INVALID, "syn_debug_feature: this handle runs %s", arch_name(h->arch));
     DeviceGuard g(h->device);
     return run_backbone(h, img, nullptr, B, nullptr, nullptr, (hipStream_t)stream, feature, out);
+}
+
+// .features[first] .. [last] of the loaded mobilenet_v2 on caller-supplied activations (include/synergy_hip.h): run_backbone itself, entered
+// at `first` and left at `last`, so the launches are those the forward selects for this batch under the handle's schedule.  Everything is
+// vetted before a device is touched.
+int syn_mobilenet2_span(syn_handle *h, int first, int last, const void *in, int in_u8, int B, size_t n_in, float *out, size_t n_out,
+                        float *aux, size_t n_aux, int *launch_tags, int max_tags, void *stream) {
+    if (!h || !in || !out || !launch_tags)
+        return fail(SYN_ERR_INVALID, "syn_mobilenet2_span: NULL argument (expected handle, in, out and launch_tags)");
+    if (h->arch != 0) return fail(SYN_ERR_INVALID, "syn_mobilenet2_span: this handle runs %s, expected mobilenet_v2", arch_name(h->arch));
+    if (first < 0 || first > 19 || last < 0 || last > 19 || first > last)
+        return fail(SYN_ERR_INVALID, "syn_mobilenet2_span: first=%d last=%d, expected 0 <= first <= last <= 19", first, last);
+    if (first == 1 || (first == 0 && last == 0))
+        return fail(SYN_ERR_INVALID, "syn_mobilenet2_span: first=%d last=%d, expected first = 0 with last >= 1 (the stem and features.1 share a launch) or first >= 2", first, last);
+    if (first == 19) return fail(SYN_ERR_INVALID, "syn_mobilenet2_span: first=19, expected first <= 18 (19 = pool and heads, reached as last = 19)");
+    if (in_u8 && first != 0) return fail(SYN_ERR_INVALID, "syn_mobilenet2_span: in_u8 is set with first=%d, expected only with first = 0 (the crops)", first);
+    if (aux && last != 19) return fail(SYN_ERR_INVALID, "syn_mobilenet2_span: aux with last=%d, expected NULL (only last = 19 has a second output, the pool)", last);
+    if (B < 1 || B > 65536)          // the kernels index pixels and pixel x channel quads in 32-bit integers
+        return fail(SYN_ERR_INVALID, "syn_mobilenet2_span: B=%d, expected 1 <= B <= 65536", B);
+    const Net &n = net();
+    size_t f_in = (size_t)3 * syn::kImg * syn::kImg, f_out = syn::kParam, n_layers = 0;
+    for (const Layer &L : n.layers) {
+        if (L.feature < first || L.feature > last) continue;
+        if (!n_layers && first >= 2) f_in = (size_t)L.cin * L.hin * L.hin;
+        if (last <= 18) f_out = (size_t)L.cout * L.hout * L.hout;
+        ++n_layers;
+    }
+    const size_t f_aux = aux ? (size_t)syn::kPool : 0, need_tags = n_layers + (last == 19 ? 1 : 0);     // (one launch per layer: the most any schedule issues)
+    if (n_in != f_in * B || n_out != f_out * B || n_aux != f_aux * B)
+        return fail(SYN_ERR_INVALID, "syn_mobilenet2_span: features %d..%d at B=%d expected n_in=%zu n_out=%zu n_aux=%zu, got %zu %zu %zu", first, last, B,
+                    f_in * B, f_out * B, f_aux * B, n_in, n_out, n_aux);
+    if (max_tags < 0 || (size_t)max_tags < need_tags)
+        return fail(SYN_ERR_INVALID, "syn_mobilenet2_span: max_tags=%d, expected >= %zu (the per-layer launch count of features %d..%d)", max_tags, need_tags, first, last);
+    if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_mobilenet2_span: backbone weights not loaded");
+    DeviceGuard g(h->device);
+    std::vector<int> tags;
+    const bool whole = last == 19;
+    const int rc = run_backbone(h, (first == 0 && !in_u8) ? (const float *)in : nullptr, (first == 0 && in_u8) ? (const uint8_t *)in : nullptr, B,
+                                whole ? out : nullptr, whole ? aux : nullptr, (hipStream_t)stream, whole ? -1 : last, whole ? nullptr : out, -1, nullptr,
+                                nullptr, nullptr, first, first >= 2 ? (const float *)in : nullptr, &tags);
+    if (rc != SYN_OK) return rc;
+    for (size_t i = 0; i < tags.size() && i < (size_t)max_tags; ++i) launch_tags[i] = tags[i];
+    return (int)tags.size();
 }
 
 // Calibration of the range verdict on the CALLER'S crops (include/synergy_hip.h): the load-time analysis proves the overflow side, but
