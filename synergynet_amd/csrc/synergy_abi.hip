@@ -285,69 +285,122 @@ constexpr int kArchGhost = 6, kArchResnest = 8, kArchRes18 = 10, kArchRes34 = 11
 bool is_gn(int arch) { return arch == kArchGhost; }
 bool is_rs(int arch) { return arch == kArchResnest; }
 bool is_bb(int arch) { return arch == kArchRes18 || arch == kArchRes34; }      // the BasicBlock ResNets
-bool arch_known(int arch) { return (arch >= 0 && arch <= kArchLast) || arch == kArchGhost || arch == kArchResnest || is_bb(arch); }
-const char *arch_name(int arch) {
-    switch (arch) {
-    case 0: return "mobilenet_v2";
-    case 1: return "resnet50";
-    case 2: return "mobilenet_1";
-    case 3: return "mobilenet_05";
-    case 4: return "mobilenet_2";
-    case kArchGhost: return "ghostnet";
-    case kArchResnest: return "resnest50";
-    case kArchRes18: return "resnet18";
-    case kArchRes34: return "resnet34";
-    default: return "?";
+// (arch_known, arch_name and everything else that depends on the id alone: the table of architectures behind the descriptors, arch_info)
+
+// ---- What the four exact-fp32 families (MobileNetV1, GhostNet, ResNeSt-50, resnet18 / 34) share: how a state_dict is laid out.
+// ConvBn = a convolution and the BatchNorm behind it.  flat: weight [cout][cin][k][k], then the BN's weight | bias | running_mean |
+// running_var, cout each; packed: the weights in the order its packer gives them (pack_conv / pack_conv_t below), the folded scale [cout],
+// the folded shift [cout].  A depthwise convolution has cin = 1, a grouped one has cin = the inputs of ONE group.
+struct ConvBn { int cin = 0, cout = 0, k = 1, groups = 1; size_t src = 0, dst_w = 0, dst_scale = 0, dst_shift = 0; };
+// The four heads: 102 x pool weights and 102 biases in flat, fc_tex in front of the others (tex_first) or behind them.  Packed are rows
+// 0..61 = ori | shape | exp of a [64][pool] matrix and a bias [64]; src = where fc_ori starts.  The texture head is loaded, never computed.
+struct Heads { int pool = 0; size_t src = 0, dst_w = 0, dst_b = 0; };
+// The cursor a *Net constructor walks its table with: floats taken so far from the flat input and given so far to the packed blob, in
+// the module's state_dict order, and the multiply-adds per face of what was laid out.
+struct Layout {
+    size_t src = 0, dst = 0;
+    double macs = 0;
+    size_t flat(size_t n) { const size_t at = src; src += n; return at; }         // n floats that are no ConvBn (SE vectors, fc1 / fc2, conv_head):
+    size_t packed(size_t n) { const size_t at = dst; dst += n; return at; }       // where they start
+    ConvBn conv(int cin, int cout, int k, int hw, int groups = 1) {                // hw = output pixels
+        ConvBn c; c.cin = cin; c.cout = cout; c.k = k; c.groups = groups;
+        const size_t nw = (size_t)cout * cin * k * k;
+        c.src = flat(nw + 4 * (size_t)cout);
+        c.dst_w = packed(nw); c.dst_scale = packed(cout); c.dst_shift = packed(cout);
+        macs += (double)nw * hw;
+        return c;
+    }
+    ConvBn depthwise(int c, int k, int hw) { return conv(1, c, k, hw); }
+    ConvBn grouped3x3(int cg, int ng, int groups, int hw) { return conv(cg, groups * ng, 3, hw, groups); }
+    ConvBn stem27(int c0) { return conv(3, c0, 3, 3600); }                        // 3x3 / 2 on the 120^2 crop: 27 taps
+    Heads heads(int pool, bool tex_first) {                                        // (the caller counts the MACs: 62 or 102 rows, as its module does)
+        Heads f; f.pool = pool;
+        f.src = flat((size_t)102 * pool + 102) + (tex_first ? (size_t)40 * pool + 40 : 0);
+        f.dst_w = packed((size_t)64 * pool); f.dst_b = packed(64);
+        return f;
+    }
+};
+void grow(size_t &m, size_t v) { m = v > m ? v : m; }
+
+// ... and how the pieces of a layout are packed.  BatchNorm folds, in fp32, to y = conv * scale + shift with scale = gamma / sqrt(var + 1e-5)
+// and shift = beta - mean * scale; bn = weight | bias | running_mean | running_var, c each.
+void fold_bn(const float *bn, int c, float *scale, float *shift) {
+    for (int i = 0; i < c; ++i) {
+        const float sc = bn[i] / sqrtf(bn[3 * c + i] + 1e-5f);
+        scale[i] = sc;
+        shift[i] = bn[c + i] - bn[2 * c + i] * sc;
     }
 }
+// weight [cout][cin][k][k] -> [cout][tap][cin], as the GEMM kernels read it (a 1x1 convolution stays as it is), and the folded BN
+void pack_conv(const float *flat, const ConvBn &c, std::vector<float> &pk) {
+    const int kk = c.k * c.k;
+    const float *w = flat + c.src;
+    for (int o = 0; o < c.cout; ++o)
+        for (int ci = 0; ci < c.cin; ++ci)
+            for (int t = 0; t < kk; ++t) pk[c.dst_w + ((size_t)o * kk + t) * c.cin + ci] = w[((size_t)o * c.cin + ci) * kk + t];
+    fold_bn(w + (size_t)c.cout * c.cin * kk, c.cout, pk.data() + c.dst_scale, pk.data() + c.dst_shift);
+}
+// weight [cout][cin][k][k] -> [ci * k * k + tap][cout], output channels innermost: the 27-tap stems [27][c0], the 7x7 stem [147][64] and
+// every depthwise filter (cin = 1: tap-major [k * k][c]); and the folded BN
+void pack_conv_t(const float *flat, const ConvBn &c, std::vector<float> &pk) {
+    const int rows = c.cin * c.k * c.k;
+    const float *w = flat + c.src;
+    for (int o = 0; o < c.cout; ++o)
+        for (int r = 0; r < rows; ++r) pk[c.dst_w + (size_t)r * c.cout + o] = w[(size_t)o * rows + r];
+    fold_bn(w + (size_t)c.cout * rows, c.cout, pk.data() + c.dst_scale, pk.data() + c.dst_shift);
+}
+// fc_ori [12], fc_shape [40], fc_exp [10], each {weight [rows][pool], bias}, consecutive in flat -> rows 0..61 of the packed matrix and bias
+void pack_heads(const float *flat, const Heads &f, std::vector<float> &pk) {
+    const float *src = flat + f.src;
+    static const int hn[3] = {12, 40, 10};
+    int row = 0;
+    for (int k = 0; k < 3; ++k) {
+        memcpy(pk.data() + f.dst_w + (size_t)row * f.pool, src, sizeof(float) * hn[k] * f.pool);
+        src += (size_t)hn[k] * f.pool;
+        memcpy(pk.data() + f.dst_b + row, src, sizeof(float) * hn[k]);
+        src += hn[k];
+        row += hn[k];
+    }
+}
+
 struct Mb1Block {
     int cin, cout, stride, hin, hout;
-    size_t src_dw, src_pw;                                     // flat: conv_dw.weight, bn_dw x4, conv_sep.weight, bn_sep x4
-    size_t dst_wd, dst_dscale, dst_dshift, dst_wp, dst_pscale, dst_pshift;      // packed: [9][cin] | [cin] | [cin] | [cout][cin] | [cout] | [cout]
+    ConvBn dw, pw;                                             // conv_dw + bn_dw, packed tap-major [9][cin]; conv_sep + bn_sep, [cout][cin]
 };
 struct Mb1Net {
     int c0 = 0, pool = 0;
+    ConvBn stem;                                               // conv1 + bn1, packed [27][c0]
     std::vector<Mb1Block> blocks;
-    size_t flat_count = 0, packed_count = 0, src_fc = 0, dst_stem_w = 0, dst_stem_scale = 0, dst_stem_shift = 0, dst_fc_w = 0, dst_fc_b = 0;
+    Heads fc;
+    size_t flat_count = 0, packed_count = 0;
     size_t buf_io = 0, buf_dw = 0;                             // per-face floats: a block's input / output, a depthwise output
     double flops = 0;
+    size_t ws_per_face() const { return 2 * buf_io + buf_dw; }
     explicit Mb1Net(int num, int den) {                        // width = num / den
         auto ch = [&](int c) { return c * num / den; };        // int(c * width): exact for the three widths
         static const int tab[13][3] = {{32, 64, 1}, {64, 128, 2}, {128, 128, 1}, {128, 256, 2}, {256, 256, 1}, {256, 512, 2}, {512, 512, 1},
                                        {512, 512, 1}, {512, 512, 1}, {512, 512, 1}, {512, 512, 1}, {512, 1024, 2}, {1024, 1024, 1}};      // dw2_1 .. dw6 (:66-82)
         c0 = ch(32); pool = ch(1024);
-        size_t src = 0, dst = 0;
-        src += (size_t)c0 * 27 + 4 * (size_t)c0;
-        dst_stem_w = dst; dst += (size_t)27 * c0;
-        dst_stem_scale = dst; dst += c0;
-        dst_stem_shift = dst; dst += c0;
-        flops = 2.0 * 27 * c0 * 3600;
+        Layout L;
+        stem = L.stem27(c0);
         buf_io = (size_t)c0 * 3600;
         int h = 60;
         for (const auto &t : tab) {
             Mb1Block b{};
             b.cin = ch(t[0]); b.cout = ch(t[1]); b.stride = t[2]; b.hin = h; b.hout = (h + 2 - 3) / b.stride + 1;      // 15 -> 8
-            b.src_dw = src; src += (size_t)b.cin * 9 + 4 * (size_t)b.cin;
-            b.src_pw = src; src += (size_t)b.cout * b.cin + 4 * (size_t)b.cout;
-            b.dst_wd = dst; dst += (size_t)9 * b.cin;
-            b.dst_dscale = dst; dst += b.cin;
-            b.dst_dshift = dst; dst += b.cin;
-            b.dst_wp = dst; dst += (size_t)b.cout * b.cin;
-            b.dst_pscale = dst; dst += b.cout;
-            b.dst_pshift = dst; dst += b.cout;
-            flops += 2.0 * (9.0 * b.cin + (double)b.cin * b.cout) * b.hout * b.hout;
-            const size_t osz = (size_t)b.cout * b.hout * b.hout, dsz = (size_t)b.cin * b.hout * b.hout;
-            buf_io = osz > buf_io ? osz : buf_io;
-            buf_dw = dsz > buf_dw ? dsz : buf_dw;
+            const int hw = b.hout * b.hout;
+            b.dw = L.depthwise(b.cin, 3, hw);
+            b.pw = L.conv(b.cin, b.cout, 1, hw);
+            grow(buf_io, (size_t)b.cout * hw);
+            grow(buf_dw, (size_t)b.cin * hw);
             blocks.push_back(b);
             h = b.hout;
         }
-        src_fc = src; src += (size_t)102 * pool + 102;
-        flat_count = src;
-        dst_fc_w = dst; dst += (size_t)64 * pool;              // rows 0..61 = ori | shape | exp; the texture head is loaded but never computed
-        dst_fc_b = dst; dst += 64;
-        packed_count = dst;
-        flops += 2.0 * pool * 102;                             // the network's own count (all four heads), as syn_resnet50_flops_per_face
+        fc = L.heads(pool, false);
+        L.macs += 102.0 * pool;                                // the network's own count (all four heads), as syn_resnet50_flops_per_face
+        flat_count = L.src;
+        packed_count = L.dst;
+        flops = 2.0 * L.macs;
     }
 };
 const Mb1Net &mb1net(int arch) {
@@ -359,25 +412,23 @@ const Mb1Net &mb1net(int arch) {
 // (blocks.0.0 .. blocks.8.3), blocks.9.0 = ConvBnAct 160 -> 960, global pool, conv_head 960 -> 1280 (bias) + ReLU, four heads.
 // A GhostModule(c -> o) = primary 1x1 c -> o / 2 + BN (+ ReLU), cheap = depthwise 3x3 on primary + BN (+ ReLU), cat(primary, cheap);
 // every o here is even, so the reference's [:, :oup] slice (:99) drops nothing -- GnNet() refuses a table where that is not so.
-struct GnConv { int cin = 0, cout = 0; size_t src = 0, dst_w = 0, dst_scale = 0, dst_shift = 0; };      // flat: weight [cout][cin], bn x4
-struct GnDw { int c = 0, k = 0; size_t src = 0, dst_w = 0, dst_scale = 0, dst_shift = 0; };             // flat: weight [c][1][k][k], bn x4; packed [k*k][c]
 struct GnBlock {
     int cin, mid, cout, k, stride, se, hin, hout;
     bool conv_sc;
-    GnConv g1p, g2p, scp;                                      // ghost1 / ghost2 primary, shortcut 1x1
-    GnDw g1d, g2d, dw, scd;                                    // ghost1 / ghost2 cheap, the stride-2 conv_dw, shortcut depthwise
+    ConvBn g1p, g2p, scp;                                      // ghost1 / ghost2 primary, shortcut 1x1: packed [cout][cin]
+    ConvBn g1d, g2d, dw, scd;                                  // ghost1 / ghost2 cheap, the stride-2 conv_dw, shortcut depthwise: packed tap-major [k*k][c]
     size_t src_se, dst_rw, dst_rb, dst_ew, dst_eb;             // se.conv_reduce {weight [se][mid], bias}, se.conv_expand {weight [mid][se], bias}
 };
 struct GnNet {
     static constexpr int kBlocks = 16, kStem = 16, kLast = 960, kPool = 1280;
     std::vector<GnBlock> blocks;
-    GnConv last;                                               // blocks.9.0
-    size_t flat_count = 0, packed_count = 0, dst_stem_w = 0, dst_stem_scale = 0, dst_stem_shift = 0;
-    size_t src_head = 0, dst_head_w = 0, dst_head_b = 0, src_fc = 0, dst_fc_w = 0, dst_fc_b = 0;
+    ConvBn stem, last;                                         // conv_stem + bn1, packed [27][16]; blocks.9.0
+    Heads fc;
+    size_t flat_count = 0, packed_count = 0, src_head = 0, dst_head_w = 0, dst_head_b = 0;
     // per-face floats of the workspace regions: block input / output (x 2), ghost1 output, conv_dw output, ghost2 primary, shortcut
     // depthwise and 1x1 outputs, and the small vectors (SE mean | reduced | gate; pooled 960 | 1280)
     size_t buf_io = 0, buf_g1 = 0, buf_d = 0, buf_t = 0, buf_s = 0, buf_r = 0, buf_small = 2304;
-    double macs = 0, flops = 0;
+    double flops = 0;
     size_t ws_per_face() const { return 2 * buf_io + buf_g1 + buf_d + buf_t + buf_s + buf_r + buf_small; }
     GnNet() {
         static const int tab[kBlocks][6] = {      // in, mid, out, k, stride, SE reduced channels (cfgs :240-265 through _make_divisible)
@@ -385,31 +436,8 @@ struct GnNet {
             {40, 120, 40, 5, 1, 32},  {40, 240, 80, 3, 2, 0},    {80, 200, 80, 3, 1, 0},    {80, 184, 80, 3, 1, 0},
             {80, 184, 80, 3, 1, 0},   {80, 480, 112, 3, 1, 120}, {112, 672, 112, 3, 1, 168}, {112, 672, 160, 5, 2, 168},
             {160, 960, 160, 5, 1, 0}, {160, 960, 160, 5, 1, 240}, {160, 960, 160, 5, 1, 0}, {160, 960, 160, 5, 1, 240}};
-        size_t src = 0, dst = 0;
-        auto conv = [&](int cin, int cout, int hw) {
-            GnConv c; c.cin = cin; c.cout = cout;
-            c.src = src; src += (size_t)cout * cin + 4 * (size_t)cout;
-            c.dst_w = dst; dst += (size_t)cout * cin;
-            c.dst_scale = dst; dst += cout;
-            c.dst_shift = dst; dst += cout;
-            macs += (double)cin * cout * hw;
-            return c;
-        };
-        auto dwc = [&](int c, int k, int hw) {
-            GnDw d; d.c = c; d.k = k;
-            d.src = src; src += (size_t)c * k * k + 4 * (size_t)c;
-            d.dst_w = dst; dst += (size_t)c * k * k;
-            d.dst_scale = dst; dst += c;
-            d.dst_shift = dst; dst += c;
-            macs += (double)c * k * k * hw;
-            return d;
-        };
-        auto up = [](size_t &m, size_t v) { m = v > m ? v : m; };
-        src += (size_t)kStem * 27 + 4 * (size_t)kStem;
-        dst_stem_w = dst; dst += (size_t)27 * kStem;
-        dst_stem_scale = dst; dst += kStem;
-        dst_stem_shift = dst; dst += kStem;
-        macs = 27.0 * kStem * 3600;
+        Layout L;
+        stem = L.stem27(kStem);
         buf_io = (size_t)kStem * 3600;
         int h = 60;
         for (const auto &t : tab) {
@@ -422,44 +450,39 @@ struct GnNet {
                 abort();
             }
             const int hw = b.hin * b.hin, hw2 = b.hout * b.hout;
-            b.g1p = conv(b.cin, b.mid / 2, hw);
-            b.g1d = dwc(b.mid / 2, 3, hw);
-            if (b.stride == 2) b.dw = dwc(b.mid, b.k, hw2);
+            b.g1p = L.conv(b.cin, b.mid / 2, 1, hw);
+            b.g1d = L.depthwise(b.mid / 2, 3, hw);
+            if (b.stride == 2) b.dw = L.depthwise(b.mid, b.k, hw2);
             if (b.se) {
-                b.src_se = src; src += 2 * (size_t)b.se * b.mid + b.se + b.mid;
-                b.dst_rw = dst; dst += (size_t)b.se * b.mid;
-                b.dst_rb = dst; dst += b.se;
-                b.dst_ew = dst; dst += (size_t)b.se * b.mid;
-                b.dst_eb = dst; dst += b.mid;
-                macs += 2.0 * b.se * b.mid;
+                const size_t wn = (size_t)b.se * b.mid;
+                b.src_se = L.flat(2 * wn + b.se + b.mid);
+                b.dst_rw = L.packed(wn); b.dst_rb = L.packed(b.se); b.dst_ew = L.packed(wn); b.dst_eb = L.packed(b.mid);
+                L.macs += 2.0 * b.se * b.mid;
             }
-            b.g2p = conv(b.mid, b.cout / 2, hw2);
-            b.g2d = dwc(b.cout / 2, 3, hw2);
+            b.g2p = L.conv(b.mid, b.cout / 2, 1, hw2);
+            b.g2d = L.depthwise(b.cout / 2, 3, hw2);
             if (b.conv_sc) {
-                b.scd = dwc(b.cin, b.k, hw2);
-                b.scp = conv(b.cin, b.cout, hw2);
+                b.scd = L.depthwise(b.cin, b.k, hw2);
+                b.scp = L.conv(b.cin, b.cout, 1, hw2);
             }
-            up(buf_io, (size_t)b.cout * hw2);
-            up(buf_g1, (size_t)b.mid * hw);
-            up(buf_d, (size_t)b.mid * hw2);
-            up(buf_t, (size_t)(b.cout / 2) * hw2);
-            up(buf_s, (size_t)b.cin * hw2);
-            up(buf_r, (size_t)b.cout * hw2);
+            grow(buf_io, (size_t)b.cout * hw2);
+            grow(buf_g1, (size_t)b.mid * hw);
+            grow(buf_d, (size_t)b.mid * hw2);
+            grow(buf_t, (size_t)(b.cout / 2) * hw2);
+            grow(buf_s, (size_t)b.cin * hw2);
+            grow(buf_r, (size_t)b.cout * hw2);
             blocks.push_back(b);
             h = b.hout;
         }
-        last = conv(160, kLast, 16);
-        src_head = src; src += (size_t)kPool * kLast + kPool;
-        dst_head_w = dst; dst += (size_t)kPool * kLast;
-        dst_head_b = dst; dst += kPool;
-        macs += (double)kPool * kLast;
-        src_fc = src; src += (size_t)102 * kPool + 102;
-        dst_fc_w = dst; dst += (size_t)64 * kPool;             // rows 0..61 = ori | shape | exp; classifier_texture is loaded but never computed
-        dst_fc_b = dst; dst += 64;
-        macs += 102.0 * kPool;                                 // the module's own count, all four heads
-        flat_count = src;
-        packed_count = dst;
-        flops = 2.0 * macs;
+        last = L.conv(160, kLast, 1, 16);
+        src_head = L.flat((size_t)kPool * kLast + kPool);      // conv_head {weight [1280][960], bias}
+        dst_head_w = L.packed((size_t)kPool * kLast); dst_head_b = L.packed(kPool);
+        L.macs += (double)kPool * kLast;
+        fc = L.heads(kPool, false);
+        L.macs += 102.0 * kPool;                               // the module's own count, all four heads
+        flat_count = L.src;
+        packed_count = L.dst;
+        flops = 2.0 * L.macs;
     }
 };
 const GnNet &gnnet() {
@@ -471,13 +494,11 @@ const GnNet &gnnet() {
 // convolutions 3 -> 32 / 2, 32 -> 32, 32 -> 64), bn1 + ReLU, max pool, 3 + 4 + 6 + 3 bottlenecks of group width C = 64 / 128 / 256 / 512,
 // global mean, four heads.  A bottleneck: conv1 1x1 -> C, conv2.conv 3x3 groups 2 -> 2C = U, the split-attention gate, V = att0 U0 +
 // att1 U1, [3x3 / 2 average on layerN.0, N >= 2], conv3 1x1 -> 4C, + residual ([2x2 / 2 ceil-mode average], 1x1, BN on layerN.0), ReLU.
-struct RsConv { int cin = 0, cout = 0; size_t src = 0, dst_w = 0, dst_scale = 0, dst_shift = 0; };      // flat: weight [cout][cin(,1,1)], bn x4
-struct RsConv3 { int cg = 0, ng = 0, groups = 1; size_t src = 0, dst_w = 0, dst_scale = 0, dst_shift = 0; };   // flat: weight [groups ng][cg][3][3], bn x4; packed [n][9][cg]
 struct RsBlock {
     int cin, C, cout, inter, hin, hout;
     bool avd, down;                                            // the 3x3 / 2 average (and the 2x2 / 2 downsample pool); a downsample branch
-    RsConv c1, c3, ds;
-    RsConv3 c2;
+    ConvBn c1, c3, ds;                                         // 1x1: packed [cout][cin]
+    ConvBn c2;                                                 // conv2.conv, 2 groups: flat [2 C][C / 2][3][3], packed [n][9][C / 2]
     size_t src_fc = 0, dst_w1t = 0, dst_s1 = 0, dst_h1 = 0, dst_w2t = 0, dst_b2 = 0;      // flat: fc1 {weight [I][C], bias}, bn1 x4, fc2 {weight [2C][I], bias}
     // per-face floats of the block's intermediates: conv1 output, U, V, the pooled V, the pooled input, the downsample output
     size_t n_t1() const { return (size_t)hin * hin * C; }
@@ -490,41 +511,18 @@ struct RsBlock {
 struct RsNet {
     static constexpr int kBlocks = 16, kStem = 32, kPool = 2048;
     std::vector<RsBlock> blocks;
-    RsConv3 stem2, stem3;
-    size_t flat_count = 0, packed_count = 0, dst_stem_w = 0, dst_stem_scale = 0, dst_stem_shift = 0, src_fc = 0, dst_fc_w = 0, dst_fc_b = 0;
+    ConvBn stem, stem2, stem3;                                 // conv1.0, packed [27][32]; conv1.3 and conv1.6, packed [n][9][32]
+    Heads fc;
+    size_t flat_count = 0, packed_count = 0;
     size_t buf_io = 0, buf_scratch = 0;                        // per-face floats: block input / output (x 2), a block's intermediates
-    double macs = 0, flops = 0;
+    double flops = 0;
     size_t ws_per_face() const { return 2 * buf_io + buf_scratch; }
     RsNet() {
         static const int layers[4][2] = {{64, 3}, {128, 4}, {256, 6}, {512, 3}};      // group width, blocks
-        size_t src = 0, dst = 0;
-        auto conv = [&](int cin, int cout, int hw) {
-            RsConv c; c.cin = cin; c.cout = cout;
-            c.src = src; src += (size_t)cout * cin + 4 * (size_t)cout;
-            c.dst_w = dst; dst += (size_t)cout * cin;
-            c.dst_scale = dst; dst += cout;
-            c.dst_shift = dst; dst += cout;
-            macs += (double)cin * cout * hw;
-            return c;
-        };
-        auto conv3 = [&](int cg, int ng, int groups, int hw) {
-            RsConv3 c; c.cg = cg; c.ng = ng; c.groups = groups;
-            const size_t nw = (size_t)groups * ng * cg * 9, n = (size_t)groups * ng;
-            c.src = src; src += nw + 4 * n;
-            c.dst_w = dst; dst += nw;
-            c.dst_scale = dst; dst += n;
-            c.dst_shift = dst; dst += n;
-            macs += (double)nw * hw;
-            return c;
-        };
-        auto up = [](size_t &m, size_t v) { m = v > m ? v : m; };
-        src += (size_t)kStem * 27 + 4 * (size_t)kStem;
-        dst_stem_w = dst; dst += (size_t)27 * kStem;
-        dst_stem_scale = dst; dst += kStem;
-        dst_stem_shift = dst; dst += kStem;
-        macs = 27.0 * kStem * 3600;
-        stem2 = conv3(kStem, kStem, 1, 3600);
-        stem3 = conv3(kStem, 2 * kStem, 1, 3600);              // its BatchNorm is the model's bn1
+        Layout L;
+        stem = L.stem27(kStem);
+        stem2 = L.grouped3x3(kStem, kStem, 1, 3600);
+        stem3 = L.grouped3x3(kStem, 2 * kStem, 1, 3600);       // its BatchNorm is the model's bn1
         buf_io = (size_t)2 * kStem * 3600;
         buf_scratch = (size_t)2 * kStem * 3600 + 2 * (size_t)kStem * 3600;      // the stem: conv1, conv2 and conv3 outputs
         int h = 30, cin = 64;
@@ -535,29 +533,25 @@ struct RsNet {
                 b.avd = l > 0 && i == 0; b.down = i == 0;
                 b.hin = h; b.hout = b.avd ? (h + 1) / 2 : h;   // 30 -> 15 -> 8 -> 4, by both pools
                 const int hw = b.hin * b.hin, hw2 = b.hout * b.hout;
-                b.c1 = conv(b.cin, b.C, hw);
-                b.c2 = conv3(b.C / 2, b.C, 2, hw);
-                b.src_fc = src; src += (size_t)b.inter * b.C + b.inter + 4 * (size_t)b.inter + 2 * (size_t)b.C * b.inter + 2 * (size_t)b.C;
-                b.dst_w1t = dst; dst += (size_t)b.inter * b.C;
-                b.dst_s1 = dst; dst += b.inter;
-                b.dst_h1 = dst; dst += b.inter;
-                b.dst_w2t = dst; dst += 2 * (size_t)b.C * b.inter;
-                b.dst_b2 = dst; dst += 2 * (size_t)b.C;
-                macs += 3.0 * b.C * b.inter;
-                b.c3 = conv(b.C, b.cout, hw2);
-                if (b.down) b.ds = conv(b.cin, b.cout, hw2);
-                up(buf_io, (size_t)b.cout * hw2);
-                up(buf_scratch, b.scratch());
+                b.c1 = L.conv(b.cin, b.C, 1, hw);
+                b.c2 = L.grouped3x3(b.C / 2, b.C, 2, hw);
+                const size_t w1 = (size_t)b.inter * b.C, w2 = 2 * (size_t)b.C * b.inter;
+                b.src_fc = L.flat(w1 + b.inter + 4 * (size_t)b.inter + w2 + 2 * (size_t)b.C);
+                b.dst_w1t = L.packed(w1); b.dst_s1 = L.packed(b.inter); b.dst_h1 = L.packed(b.inter);
+                b.dst_w2t = L.packed(w2); b.dst_b2 = L.packed(2 * (size_t)b.C);
+                L.macs += 3.0 * b.C * b.inter;
+                b.c3 = L.conv(b.C, b.cout, 1, hw2);
+                if (b.down) b.ds = L.conv(b.cin, b.cout, 1, hw2);
+                grow(buf_io, (size_t)b.cout * hw2);
+                grow(buf_scratch, b.scratch());
                 blocks.push_back(b);
                 h = b.hout; cin = b.cout;
             }
-        src_fc = src; src += (size_t)102 * kPool + 102;
-        dst_fc_w = dst; dst += (size_t)64 * kPool;             // rows 0..61 = ori | shape | exp; fc_tex is in flat (a checkpoint has it) but is not packed
-        dst_fc_b = dst; dst += 64;
-        macs += 62.0 * kPool;                                  // the module's forward never calls fc_tex
-        flat_count = src;
-        packed_count = dst;
-        flops = 2.0 * macs;
+        fc = L.heads(kPool, false);                            // fc_tex is in flat (a checkpoint has it) but is not packed
+        L.macs += 62.0 * kPool;                                // the module's forward never calls fc_tex
+        flat_count = L.src;
+        packed_count = L.dst;
+        flops = 2.0 * L.macs;
     }
 };
 const RsNet &rsnet() {
@@ -569,36 +563,25 @@ const RsNet &rsnet() {
 // Stem 7x7 / 2 3 -> 64 + BN + ReLU, max pool, [2,2,2,2] / [3,4,6,3] BasicBlocks of 64 / 128 / 256 / 512 channels on 30^2 / 15^2 / 8^2 /
 // 4^2, global mean, four heads.  A BasicBlock: conv1 3x3 (stride 2 on layer2.0 / 3.0 / 4.0) + BN + ReLU, conv2 3x3 + BN, + identity (a
 // 1x1 stride-2 convolution + BN of the input on those three blocks), ReLU.  One table, parametrised by the block counts, serves both.
-struct BbConv { int cin = 0, cout = 0, k = 3; size_t src = 0, dst_w = 0, dst_scale = 0, dst_shift = 0; };      // flat: weight [cout][cin][k][k], bn x4; packed [cout][tap][cin]
 struct BbBlock {
     int cin, C, hin, hout, stride;
     bool down;
-    BbConv c1, c2, ds;
+    ConvBn c1, c2, ds;                                         // packed [cout][tap][cin]
 };
 struct BbNet {
     static constexpr int kPool = 512;
     std::vector<BbBlock> blocks;
-    BbConv stem;                                               // packed [147][64] (row ci*49 + ky*7 + kx), as resnet_stem_kernel reads it
-    size_t flat_count = 0, packed_count = 0, src_fc = 0, dst_fc_w = 0, dst_fc_b = 0;
+    ConvBn stem;                                               // packed [147][64] (row ci*49 + ky*7 + kx), as resnet_stem_kernel reads it
+    Heads fc;
+    size_t flat_count = 0, packed_count = 0;
     size_t buf_io = 0, buf_stem = 0, buf_t1 = 0, buf_r = 0;    // per-face floats: block input / output (x 2), the stem's output, conv1's output, the downsample's output
-    double macs = 0, flops = 0;
+    double flops = 0;
     int last() const { return (int)blocks.size() + 1; }        // the hook's block index of pool + heads
     size_t ws_per_face() const { return 2 * buf_io + buf_stem + buf_t1 + buf_r; }
     explicit BbNet(const int (&count)[4]) {
         static const int planes[4] = {64, 128, 256, 512};
-        size_t src = 0, dst = 0;
-        auto conv = [&](int cin, int cout, int k, int hw) {
-            BbConv c; c.cin = cin; c.cout = cout; c.k = k;
-            const size_t nw = (size_t)cout * cin * k * k;
-            c.src = src; src += nw + 4 * (size_t)cout;
-            c.dst_w = dst; dst += nw;
-            c.dst_scale = dst; dst += cout;
-            c.dst_shift = dst; dst += cout;
-            macs += (double)nw * hw;
-            return c;
-        };
-        auto up = [](size_t &m, size_t v) { m = v > m ? v : m; };
-        stem = conv(3, 64, 7, 3600);
+        Layout L;
+        stem = L.conv(3, 64, 7, 3600);
         buf_stem = (size_t)64 * 3600;
         buf_io = (size_t)64 * 900;
         int h = 30, cin = 64;
@@ -608,22 +591,20 @@ struct BbNet {
                 b.cin = cin; b.C = planes[l]; b.stride = (l > 0 && i == 0) ? 2 : 1; b.down = b.stride == 2;
                 b.hin = h; b.hout = b.stride == 2 ? (h + 1) / 2 : h;      // 30 -> 15 -> 8 -> 4 (3x3 pad 1 stride 2, and 1x1 stride 2 alike)
                 const int hw = b.hout * b.hout;
-                b.c1 = conv(b.cin, b.C, 3, hw);
-                b.c2 = conv(b.C, b.C, 3, hw);
-                if (b.down) b.ds = conv(b.cin, b.C, 1, hw);
-                up(buf_io, (size_t)b.C * hw);
-                up(buf_t1, (size_t)b.C * hw);
-                if (b.down) up(buf_r, (size_t)b.C * hw);
+                b.c1 = L.conv(b.cin, b.C, 3, hw);
+                b.c2 = L.conv(b.C, b.C, 3, hw);
+                if (b.down) b.ds = L.conv(b.cin, b.C, 1, hw);
+                grow(buf_io, (size_t)b.C * hw);
+                grow(buf_t1, (size_t)b.C * hw);
+                if (b.down) grow(buf_r, (size_t)b.C * hw);
                 blocks.push_back(b);
                 h = b.hout; cin = b.C;
             }
-        src_fc = src; src += (size_t)102 * kPool + 102;        // module order: fc_tex, fc_ori, fc_shape, fc_exp
-        dst_fc_w = dst; dst += (size_t)64 * kPool;             // rows 0..61 = ori | shape | exp; fc_tex is in flat (a checkpoint has it) but is not packed
-        dst_fc_b = dst; dst += 64;
-        macs += 62.0 * kPool;                                  // the adapter takes the first 62 outputs: fc_tex does not run
-        flat_count = src;
-        packed_count = dst;
-        flops = 2.0 * macs;
+        fc = L.heads(kPool, true);                             // module order: fc_tex, fc_ori, fc_shape, fc_exp; fc_tex is in flat (a checkpoint has it) but is not packed
+        L.macs += 62.0 * kPool;                                // the adapter takes the first 62 outputs: fc_tex does not run
+        flat_count = L.src;
+        packed_count = L.dst;
+        flops = 2.0 * L.macs;
     }
 };
 const BbNet &bbnet(int arch) {
@@ -631,6 +612,22 @@ const BbNet &bbnet(int arch) {
     static const BbNet n18(c18), n34(c34);
     return arch == kArchRes34 ? n34 : n18;
 }
+
+// ---- every architecture a handle can run, built once from the descriptors above; everything that depends on the arch id alone reads it ----
+struct ArchInfo {
+    int id;
+    const char *name;
+    size_t flat, packed, ws_per_face;      // floats: the host flat input, the packed device blob, the activations of one face
+    int pool;                              // width of the pooled feature
+    void (*pack)(int arch, const float *flat, std::vector<float> &pk);
+};
+const std::vector<ArchInfo> &arch_table();      // (defined behind the packers)
+const ArchInfo *arch_info(int arch) {
+    for (const ArchInfo &a : arch_table()) if (a.id == arch) return &a;
+    return nullptr;
+}
+bool arch_known(int arch) { return arch_info(arch) != nullptr; }
+const char *arch_name(int arch) { const ArchInfo *a = arch_info(arch); return a ? a->name : "?"; }
 
 struct ConstHeader {   // first 256 bytes of an exported constants buffer
     uint64_t magic;
@@ -731,17 +728,16 @@ const float *basis_std_cs(const syn_handle *h) { return basis_mean(h) + 192; }  
 const unsigned *basis_f16_dense(const syn_handle *h) { return reinterpret_cast<const unsigned *>(basis_mean(h) + 256); }
 const unsigned *basis_f16_lmk(const syn_handle *h) { return basis_f16_dense(h) + (size_t)(h->nvp / 32) * 3 * syn::kBasisF16; }
 
+// One activation workspace serves every backbone: resnet50 and mobilenet_2 need 1 152 000 floats per face, ResNeSt-50 1 123 456,
+// resnet18 / 34 432 000 (the stem's 60^2 x 64 output the largest tensor), GhostNet less than half of the largest.
 size_t ws_floats_per_face() {
-    const size_t mb = 2 * net().max_io + 2 * net().max_hidden, rn = 4 * resnet50().buf_big + 2 * resnet50().buf_mid;
-    const size_t m1 = 2 * mb1net(4).buf_io + mb1net(4).buf_dw;      // the widest MobileNetV1 (equal to rn: the size does not change)
-    const size_t two = mb > rn ? mb : rn, gn = gnnet().ws_per_face();      // (GhostNet needs less than half of rn: the size does not change)
-    const size_t three = two > m1 ? two : m1, rs = rsnet().ws_per_face();      // (ResNeSt-50 needs 1 123 456 floats, below rn's 1 152 000: likewise)
-    const size_t four = three > gn ? three : gn, bb = bbnet(kArchRes34).ws_per_face();      // (resnet18 / 34 need 432 000 floats, the stem's 60^2 x 64 output the largest tensor: likewise)
-    const size_t five = four > rs ? four : rs;
-    return five > bb ? five : bb;    // one activation workspace serves every backbone
+    size_t m = 0;
+    for (const ArchInfo &a : arch_table()) m = std::max(m, a.ws_per_face);
+    return m;
 }
-size_t backbone_floats(int arch) { return is_bb(arch) ? bbnet(arch).packed_count : is_rs(arch) ? rsnet().packed_count : is_gn(arch) ? gnnet().packed_count : is_mb1(arch) ? mb1net(arch).packed_count : (arch == 1 ? resnet50().packed_count : net().packed_count); }
-size_t backbone_flat_floats(int arch) { return is_bb(arch) ? bbnet(arch).flat_count : is_rs(arch) ? rsnet().flat_count : is_gn(arch) ? gnnet().flat_count : is_mb1(arch) ? mb1net(arch).flat_count : (arch == 1 ? resnet50().flat_count : net().flat_count); }
+// (every caller has vetted the id with arch_known or holds it in a handle, whose id is always a known one)
+size_t backbone_floats(int arch) { const ArchInfo *a = arch_info(arch); return a ? a->packed : 0; }
+size_t backbone_flat_floats(int arch) { const ArchInfo *a = arch_info(arch); return a ? a->flat : 0; }
 
 // Both scratch regions only ever grow; growing synchronises the whole device first, so work in flight on another stream
 // (synergynet_amd/streams.py runs the reconstruction of batch i beside the backbone of batch i+1) never loses its buffer.
@@ -759,6 +755,25 @@ int ensure_rec(syn_handle *h, int B) {
     if (h->rec) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->rec)); h->rec = nullptr; h->rec_bytes = 0; }
     HIP_TRY(hipMalloc((void **)&h->rec, need));
     h->rec_bytes = need;
+    return SYN_OK;
+}
+
+// New weights: no range verdict, no sticky fp32 switch, the run-time guard disarmed and its word cleared, no unsafe convolutions.  A
+// loader whose blob carries a verdict (resnet50's weight criterion; mobilenet_v2's on import) reads it back afterwards.
+void reset_backbone_state(syn_handle *h) {
+    h->ri = RangeInfo{};
+    h->resnet_fp32 = 0; h->range_events = 0; h->guard_armed = 0;
+    if (h->guard_word) { (void)hipDeviceSynchronize(); *(volatile unsigned *)h->guard_word = 0; }
+    h->resnet_w_unsafe[0] = h->resnet_w_unsafe[1] = h->resnet_w_unsafe[2] = 0;
+}
+// The handle runs `arch` from now on, on the n packed floats of `packed` (host): waits for the device, replaces the allocation, uploads.
+int install_backbone(syn_handle *h, int arch, const float *packed, size_t n) {
+    DeviceGuard g(h->device);
+    if (h->d_backbone) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->d_backbone)); h->d_backbone = nullptr; }
+    HIP_TRY(hipMalloc((void **)&h->d_backbone, n * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->d_backbone, packed, n * sizeof(float), hipMemcpyHostToDevice));
+    h->arch = arch;
+    reset_backbone_state(h);
     return SYN_OK;
 }
 
@@ -1282,29 +1297,32 @@ bool mb1_fused(const syn_handle *h, int B) { return h->fusion == 1 || (h->fusion
 // One layer of the forward, the ONLY place the MobileNetV1 launch arguments are derived from Mb1Net / Mb1Block: run_mobilenet1 walks
 // layers 0..14 through it and syn_mobilenet1_layer runs one of them, so the two cannot drift apart.  layer 0 = stem (in8 or in -> out
 // [B,60,60,c0]); 1..13 = block layer - 1 (in -> out; per-layer: the depthwise output goes through aux); 14 = pool + heads (in [B,4,4,pool]
-// -> out = param [B,62], aux = pool, nullable).  mark(code) is called after every launch with the launch codes below.
+// -> out = param [B,62], aux = pool, nullable).  mark(code, flops per face) is called after every launch; code: 0 = stem, 1 + 2 i = block i
+// (fused, or its depthwise half), 2 + 2 i = its pointwise half, 27 = pool + heads.
 template <class Mark>
 void mb1_launch_layer(const Mb1Net &n, const float *P, int layer, bool fused, const float *in, const uint8_t *in8, int B, float *out,
                       float *aux, hipStream_t s, Mark &&mark) {
     if (layer == 0) {
-        syn::launch_mb1_stem(in, in8, P + n.dst_stem_w, P + n.dst_stem_scale, P + n.dst_stem_shift, out, n.c0, B, s);
-        mark(0);
+        syn::launch_mb1_stem(in, in8, P + n.stem.dst_w, P + n.stem.dst_scale, P + n.stem.dst_shift, out, n.c0, B, s);
+        mark(0, 2.0 * 27 * n.c0 * 3600);
     } else if (layer == 14) {
         // avgpool + heads (:127-138); the SynergyNet wrapper takes [:, :62] = ori | shape | exp, the first 62 rows as packed
-        syn::launch_pool_fc_generic(in, P + n.dst_fc_w, P + n.dst_fc_b, out, aux, B, 16, n.pool, 62, 62, s);
-        mark(27);
+        syn::launch_pool_fc_generic(in, P + n.fc.dst_w, P + n.fc.dst_b, out, aux, B, 16, n.pool, 62, 62, s);
+        mark(27, 2.0 * n.pool * 62 + 16.0 * n.pool);
     } else {
         const int bi = layer - 1;
         const Mb1Block &b = n.blocks[bi];
+        const ConvBn &d = b.dw, &p = b.pw;
+        const double f_dw = 2.0 * 9 * b.cin * b.hout * b.hout, f_pw = 2.0 * b.cin * b.cout * b.hout * b.hout;
         if (fused) {
-            syn::launch_mb1_block(in, P + b.dst_wd, P + b.dst_dscale, P + b.dst_dshift, P + b.dst_wp, P + b.dst_pscale, P + b.dst_pshift, out, B,
+            syn::launch_mb1_block(in, P + d.dst_w, P + d.dst_scale, P + d.dst_shift, P + p.dst_w, P + p.dst_scale, P + p.dst_shift, out, B,
                                   b.hin, b.hout, b.cin, b.cout, b.stride, s);
-            mark(1 + 2 * bi);
+            mark(1 + 2 * bi, f_dw + f_pw);
         } else {
-            syn::launch_mb1_depthwise(in, P + b.dst_wd, P + b.dst_dscale, P + b.dst_dshift, aux, B, b.hin, b.hout, b.cin, b.stride, s);
-            mark(1 + 2 * bi);
-            syn::launch_mb1_pointwise(aux, P + b.dst_wp, P + b.dst_pscale, P + b.dst_pshift, out, B * b.hout * b.hout, b.cin, b.cout, s);
-            mark(2 + 2 * bi);
+            syn::launch_mb1_depthwise(in, P + d.dst_w, P + d.dst_scale, P + d.dst_shift, aux, B, b.hin, b.hout, b.cin, b.stride, s);
+            mark(1 + 2 * bi, f_dw);
+            syn::launch_mb1_pointwise(aux, P + p.dst_w, P + p.dst_scale, P + p.dst_shift, out, B * b.hout * b.hout, b.cin, b.cout, s);
+            mark(2 + 2 * bi, f_pw);
         }
     }
 }
@@ -1318,24 +1336,35 @@ void mb1_layer_counts(const Mb1Net &n, int layer, size_t *n_in, size_t *n_out, s
     }
 }
 
-// marks / mark_launch (profiling): one event after every launch; launch codes 0 = stem, 1 + 2 i = block i (fused, or its depthwise
-// half), 2 + 2 i = its pointwise half, 27 = pool + heads.
+// Profiling of the four exact-fp32 forwards (syn_backbone_profile): one event on the forward's stream after every launch, with the
+// launch's code and its algorithmic FLOPs per face; entry 0 (code -1) marks the start.  A forward that is not profiled gets no LaunchMarks.
+struct LaunchMarks {
+    hipStream_t s;
+    std::vector<hipEvent_t> events;
+    std::vector<int> codes;
+    std::vector<double> flops;
+    explicit LaunchMarks(hipStream_t stream) : s(stream) {}
+    LaunchMarks(const LaunchMarks &) = delete;
+    ~LaunchMarks() { for (hipEvent_t e : events) (void)hipEventDestroy(e); }
+    void operator()(int code, double fl) {
+        hipEvent_t e;
+        if (hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, s);
+        events.push_back(e);
+        codes.push_back(code);
+        flops.push_back(fl);
+    }
+};
+
 int run_mobilenet1(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s,
-                   std::vector<hipEvent_t> *marks = nullptr, std::vector<int> *mark_launch = nullptr) {
+                   LaunchMarks *marks = nullptr) {
     const Mb1Net &n = mb1net(h->arch);
     int rc = ensure_ws(h, B);
     if (rc) return rc;
     float *X = h->ws, *Y = X + (size_t)B * n.buf_io, *D = Y + (size_t)B * n.buf_io;
     const float *P = h->d_backbone;
-    auto mark = [&](int code) {
-        if (!marks) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        (void)hipEventRecord(e, s);
-        marks->push_back(e);
-        mark_launch->push_back(code);
-    };
-    mark(-1);
+    auto mark = [&](int code, double flops) { if (marks) (*marks)(code, flops); };
+    mark(-1, 0.0);
     const bool fused = mb1_fused(h, B);
     mb1_launch_layer(n, P, 0, fused, img, img8, B, X, nullptr, s, mark);
     for (int layer = 1; layer <= 13; ++layer) {
@@ -1372,15 +1401,15 @@ GnWs gn_ws(const GnNet &n, float *base, int B) {
 template <class Mark>
 void gn_launch_block(const GnNet &n, const float *P, int block, bool fused, const float *in, int B, float *out, float *aux, const GnWs &w,
                      hipStream_t s, Mark &&mark) {
-    auto pw = [&](const GnConv &c, const float *A, int lda, const float *gate, int HW, float *C, int ldc, int act) {
+    auto pw = [&](const ConvBn &c, const float *A, int lda, const float *gate, int HW, float *C, int ldc, int act) {
         syn::launch_gn_pointwise(A, lda, P + c.dst_w, P + c.dst_scale, P + c.dst_shift, gate, HW, C, ldc, B * HW, c.cin, c.cout, act, s);
     };
-    auto dw = [&](const GnDw &d, const float *A, int lda, float *C, int ldc, const float *res, int ldr, float *pass_out, const float *pass_res,
+    auto dw = [&](const ConvBn &d, const float *A, int lda, float *C, int ldc, const float *res, int ldr, float *pass_out, const float *pass_res,
                   int Hin, int Hout, int stride, int relu) {
-        syn::launch_gn_depthwise(A, lda, P + d.dst_w, P + d.dst_scale, P + d.dst_shift, C, ldc, res, ldr, pass_out, pass_res, B, Hin, Hout, d.c, d.k,
-                                 stride, relu, s);
+        syn::launch_gn_depthwise(A, lda, P + d.dst_w, P + d.dst_scale, P + d.dst_shift, C, ldc, res, ldr, pass_out, pass_res, B, Hin, Hout, d.cout,
+                                 d.k, stride, relu, s);
     };
-    auto ghost = [&](const GnConv &c, const GnDw &d, const float *A, int lda, const float *gate, const float *res, int ldr, float *Y, int H,
+    auto ghost = [&](const ConvBn &c, const ConvBn &d, const float *A, int lda, const float *gate, const float *res, int ldr, float *Y, int H,
                      int relu) {
         syn::launch_gn_ghost(A, lda, gate, P + c.dst_w, P + c.dst_scale, P + c.dst_shift, P + d.dst_w, P + d.dst_scale, P + d.dst_shift, res, ldr, Y,
                              B, H, c.cin, c.cout, relu, s);
@@ -1398,7 +1427,7 @@ void gn_launch_block(const GnNet &n, const float *P, int block, bool fused, cons
                                  GnNet::kPool, 1, s);
         mark(1801, 2.0 * GnNet::kLast * GnNet::kPool);
         // the SynergyNet wrapper takes [:, :62] = ori | shape | exp, the first 62 rows as packed; a 1-pixel "pool" passes the feature through
-        syn::launch_pool_fc_generic(pool, P + n.dst_fc_w, P + n.dst_fc_b, out, nullptr, B, 1, GnNet::kPool, 62, 62, s);
+        syn::launch_pool_fc_generic(pool, P + n.fc.dst_w, P + n.fc.dst_b, out, nullptr, B, 1, GnNet::kPool, 62, 62, s);
         mark(1802, 2.0 * GnNet::kPool * 62);
         return;
     }
@@ -1462,25 +1491,17 @@ int gn_launch_count(const GnNet &n, bool fused) {
 }
 
 int run_ghostnet(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s,
-                 std::vector<hipEvent_t> *marks = nullptr, std::vector<int> *mark_launch = nullptr, std::vector<double> *mark_flops = nullptr) {
+                 LaunchMarks *marks = nullptr) {
     const GnNet &n = gnnet();
     int rc = ensure_ws(h, B);
     if (rc) return rc;
     float *X = h->ws, *Y = X + (size_t)B * n.buf_io;
     const GnWs w = gn_ws(n, Y + (size_t)B * n.buf_io, B);
     const float *P = h->d_backbone;
-    auto mark = [&](int code, double flops) {
-        if (!marks) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        (void)hipEventRecord(e, s);
-        marks->push_back(e);
-        mark_launch->push_back(code);
-        mark_flops->push_back(flops);
-    };
+    auto mark = [&](int code, double flops) { if (marks) (*marks)(code, flops); };
     mark(-1, 0.0);
     const bool fused = gn_fused(h);
-    syn::launch_mb1_stem(img, img8, P + n.dst_stem_w, P + n.dst_stem_scale, P + n.dst_stem_shift, X, GnNet::kStem, B, s);
+    syn::launch_mb1_stem(img, img8, P + n.stem.dst_w, P + n.stem.dst_scale, P + n.stem.dst_shift, X, GnNet::kStem, B, s);
     mark(0, 2.0 * 27 * GnNet::kStem * 3600);
     for (int block = 0; block <= 16; ++block) {
         gn_launch_block(n, P, block, fused, X, B, Y, nullptr, w, s, mark);
@@ -1506,15 +1527,15 @@ bool rs_fused(const syn_handle *h) { return h->fusion >= 1; }      // no batch t
 template <class Mark>
 void rs_launch_block(const RsNet &n, const float *P, int block, bool fused, const float *in, const uint8_t *in8, int in_hwc, int B,
                      float *out, float *aux, float *scr, hipStream_t s, Mark &&mark) {
-    auto gemm = [&](int op, const RsConv &c, const float *A, const float *att, const float *res, float *Y, int Hin, int Ho, int relu) {
+    auto gemm = [&](int op, const ConvBn &c, const float *A, const float *att, const float *res, float *Y, int Hin, int Ho, int relu) {
         syn::launch_rs_gemm(op, A, c.cin, att, P + c.dst_w, P + c.dst_scale, P + c.dst_shift, res, Y, B, Hin, Ho, c.cin, c.cout, relu, s);
     };
-    auto conv3 = [&](const RsConv3 &c, const float *X, float *Y, int H) {
-        syn::launch_rs_conv3x3(X, c.cg * c.groups, P + c.dst_w, P + c.dst_scale, P + c.dst_shift, Y, B, H, c.cg, c.ng, c.groups, s);
+    auto conv3 = [&](const ConvBn &c, const float *X, float *Y, int H) {      // c.cin inputs and c.cout / c.groups outputs per group
+        syn::launch_rs_conv3x3(X, c.cin * c.groups, P + c.dst_w, P + c.dst_scale, P + c.dst_shift, Y, B, H, c.cin, c.cout / c.groups, c.groups, s);
     };
     if (block == 0) {
         float *s1 = scr, *s2 = s1 + (size_t)B * 3600 * RsNet::kStem, *s3 = s2 + (size_t)B * 3600 * RsNet::kStem;
-        syn::launch_rs_stem(in, in8, in_hwc, P + n.dst_stem_w, P + n.dst_stem_scale, P + n.dst_stem_shift, s1, B, s);
+        syn::launch_rs_stem(in, in8, in_hwc, P + n.stem.dst_w, P + n.stem.dst_scale, P + n.stem.dst_shift, s1, B, s);
         mark(0, 2.0 * 27 * RsNet::kStem * 3600);
         conv3(n.stem2, s1, s2, 60);
         mark(1, 2.0 * 9 * RsNet::kStem * RsNet::kStem * 3600);
@@ -1526,7 +1547,7 @@ void rs_launch_block(const RsNet &n, const float *P, int block, bool fused, cons
     }
     if (block == 17) {
         // global mean + heads (:309-320); the SynergyNet wrapper's 62 = ori | shape | exp, the rows as packed
-        syn::launch_pool_fc_generic(in, P + n.dst_fc_w, P + n.dst_fc_b, out, aux, B, 16, RsNet::kPool, 62, 62, s);
+        syn::launch_pool_fc_generic(in, P + n.fc.dst_w, P + n.fc.dst_b, out, aux, B, 16, RsNet::kPool, 62, 62, s);
         mark(1700, 2.0 * RsNet::kPool * 62);
         return;
     }
@@ -1584,21 +1605,13 @@ void rs_block_counts(const RsNet &n, int block, size_t *n_in, size_t *n_out, siz
 }
 
 int run_resnest50(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s,
-                  std::vector<hipEvent_t> *marks = nullptr, std::vector<int> *mark_launch = nullptr, std::vector<double> *mark_flops = nullptr) {
+                  LaunchMarks *marks = nullptr) {
     const RsNet &n = rsnet();
     int rc = ensure_ws(h, B);
     if (rc) return rc;
     float *X = h->ws, *Y = X + (size_t)B * n.buf_io, *scr = Y + (size_t)B * n.buf_io;
     const float *P = h->d_backbone;
-    auto mark = [&](int code, double flops) {
-        if (!marks) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        (void)hipEventRecord(e, s);
-        marks->push_back(e);
-        mark_launch->push_back(code);
-        mark_flops->push_back(flops);
-    };
+    auto mark = [&](int code, double flops) { if (marks) (*marks)(code, flops); };
     mark(-1, 0.0);
     const bool fused = rs_fused(h);
     rs_launch_block(n, P, 0, fused, img, img8, 0, B, X, nullptr, scr, s, mark);
@@ -1633,7 +1646,7 @@ void bb_launch_block(const BbNet &n, const float *P, int block, bool fused, cons
         return;
     }
     if (block == n.last()) {
-        syn::launch_pool_fc_generic(in, P + n.dst_fc_w, P + n.dst_fc_b, out, pool, B, 16, BbNet::kPool, 62, 62, s);
+        syn::launch_pool_fc_generic(in, P + n.fc.dst_w, P + n.fc.dst_b, out, pool, B, 16, BbNet::kPool, 62, 62, s);
         mark(100 * block, 2.0 * BbNet::kPool * 62);
         return;
     }
@@ -1641,7 +1654,7 @@ void bb_launch_block(const BbNet &n, const float *P, int block, bool fused, cons
     const int code = 100 * block, H = b.hin, H2 = b.hout;
     float *t1 = scr + (size_t)B * n.buf_stem, *r = t1 + (size_t)B * n.buf_t1;
     const double f1 = 2.0 * 9 * b.cin * b.C * H2 * H2, f2 = 2.0 * 9 * b.C * b.C * H2 * H2, fd = 2.0 * b.cin * b.C * H2 * H2;
-    auto conv = [&](const BbConv &c, const BbConv *ds, const float *X, const float *res, float *Y, int hin, int stride) {
+    auto conv = [&](const ConvBn &c, const ConvBn *ds, const float *X, const float *res, float *Y, int hin, int stride) {
         const float *w = P + c.dst_w, *sc = P + c.dst_scale, *sh = P + c.dst_shift;
         if (!fused) syn::launch_bb_conv3x3(X, w, sc, sh, res, Y, B, hin, H2, c.cin, c.cout, stride, 1, s);
         else syn::launch_bb_conv3x3_lds(X, w, sc, sh, res, Y, ds ? P + ds->dst_w : nullptr, ds ? P + ds->dst_scale : nullptr,
@@ -1672,21 +1685,13 @@ void bb_block_counts(const BbNet &n, int block, size_t *n_in, size_t *n_out) {
 }
 
 int run_resnet_basic(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s,
-                     std::vector<hipEvent_t> *marks = nullptr, std::vector<int> *mark_launch = nullptr, std::vector<double> *mark_flops = nullptr) {
+                     LaunchMarks *marks = nullptr) {
     const BbNet &n = bbnet(h->arch);
     int rc = ensure_ws(h, B);
     if (rc) return rc;
     float *X = h->ws, *Y = X + (size_t)B * n.buf_io, *scr = Y + (size_t)B * n.buf_io;
     const float *P = h->d_backbone;
-    auto mark = [&](int code, double flops) {
-        if (!marks) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        (void)hipEventRecord(e, s);
-        marks->push_back(e);
-        mark_launch->push_back(code);
-        mark_flops->push_back(flops);
-    };
+    auto mark = [&](int code, double flops) { if (marks) (*marks)(code, flops); };
     mark(-1, 0.0);
     const bool fused = bb_fused(h);
     bb_launch_block(n, P, 0, fused, img, img8, B, X, nullptr, scr, s, mark);
@@ -1696,6 +1701,13 @@ int run_resnet_basic(syn_handle *h, const float *img, const uint8_t *img8, int B
     }
     bb_launch_block(n, P, n.last(), fused, X, nullptr, B, param, pool, scr, s, mark);
     HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+// what the four layer / block hooks ask of B and fused alike: the kernels index pixels (up to 3600 B) and pixel x channel quads in 32-bit integers
+int check_hook_batch(const char *who, int B, int fused) {
+    if (B < 1 || B > 65536) return fail(SYN_ERR_INVALID, "%s: B=%d, expected 1 <= B <= 65536", who, B);
+    if (fused != 0 && fused != 1) return fail(SYN_ERR_INVALID, "%s: fused=%d, expected 0 or 1", who, fused);
     return SYN_OK;
 }
 
@@ -2608,13 +2620,7 @@ int syn_load_backbone_resnet50(syn_handle *h, const float *flat, size_t n_floats
         return fail(SYN_ERR_INVALID, "syn_load_backbone_resnet50: got %zu floats, ResNet-50 has %zu", n_floats, n.flat_count);
     std::vector<float> pk;
     pack_backbone_resnet50(flat, pk);
-    DeviceGuard g(h->device);
-    if (h->d_backbone) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->d_backbone)); h->d_backbone = nullptr; }
-    HIP_TRY(hipMalloc((void **)&h->d_backbone, n.packed_count * sizeof(float)));
-    HIP_TRY(hipMemcpy(h->d_backbone, pk.data(), n.packed_count * sizeof(float), hipMemcpyHostToDevice));
-    h->arch = 1;
-    h->ri = RangeInfo{};
-    h->resnet_fp32 = 0; h->range_events = 0; h->guard_armed = 0; if (h->guard_word) { (void)hipDeviceSynchronize(); *(volatile unsigned *)h->guard_word = 0; }
+    if (int rc = install_backbone(h, 1, pk.data(), n.packed_count)) return rc;
     memcpy(h->resnet_w_unsafe, pk.data() + n.dst_range, sizeof h->resnet_w_unsafe);
     return SYN_OK;
 }
@@ -2626,39 +2632,12 @@ double syn_mobilenet1_flops_per_face(int arch) { return is_mb1(arch) ? mb1net(ar
 static void pack_backbone_mobilenet1(int arch, const float *flat, std::vector<float> &pk) {
     const Mb1Net &n = mb1net(arch);
     pk.assign(n.packed_count, 0.f);
-    // BN folding: y = conv * scale + shift, scale = gamma / sqrt(var + 1e-5), shift = beta - mean * scale
-    auto fold = [&](const float *bn, int c, float *scale, float *shift) {      // bn = weight | bias | running_mean | running_var
-        for (int i = 0; i < c; ++i) {
-            const float sc = bn[i] / sqrtf(bn[3 * c + i] + 1e-5f);
-            scale[i] = sc;
-            shift[i] = bn[c + i] - bn[2 * c + i] * sc;
-        }
-    };
-    {   // conv1.weight [c0][3][3][3] -> [ci*9 + ky*3 + kx][c0]
-        const int c0 = n.c0;
-        for (int co = 0; co < c0; ++co)
-            for (int t = 0; t < 27; ++t) pk[n.dst_stem_w + (size_t)t * c0 + co] = flat[(size_t)co * 27 + t];
-        fold(flat + (size_t)c0 * 27, c0, pk.data() + n.dst_stem_scale, pk.data() + n.dst_stem_shift);
-    }
+    pack_conv_t(flat, n.stem, pk);                            // conv1.weight [c0][3][3][3] -> [ci*9 + ky*3 + kx][c0]
     for (const Mb1Block &b : n.blocks) {
-        for (int c = 0; c < b.cin; ++c)                       // conv_dw.weight [cin][1][3][3] -> tap-major [9][cin]
-            for (int t = 0; t < 9; ++t) pk[b.dst_wd + (size_t)t * b.cin + c] = flat[b.src_dw + (size_t)c * 9 + t];
-        fold(flat + b.src_dw + (size_t)b.cin * 9, b.cin, pk.data() + b.dst_dscale, pk.data() + b.dst_dshift);
-        memcpy(pk.data() + b.dst_wp, flat + b.src_pw, sizeof(float) * (size_t)b.cout * b.cin);      // conv_sep.weight [cout][cin]: as the kernels read it
-        fold(flat + b.src_pw + (size_t)b.cout * b.cin, b.cout, pk.data() + b.dst_pscale, pk.data() + b.dst_pshift);
+        pack_conv_t(flat, b.dw, pk);                          // conv_dw.weight [cin][1][3][3] -> tap-major [9][cin]
+        pack_conv(flat, b.pw, pk);                            // conv_sep.weight [cout][cin]: as the kernels read it
     }
-    {   // heads: flat order fc_ori, fc_shape, fc_exp, fc_tex = the cat order (:132-138): rows 0..61 as they come; fc_tex is not packed
-        const float *src = flat + n.src_fc;
-        static const int hn[3] = {12, 40, 10};
-        int row = 0;
-        for (int k = 0; k < 3; ++k) {
-            memcpy(pk.data() + n.dst_fc_w + (size_t)row * n.pool, src, sizeof(float) * hn[k] * n.pool);
-            src += (size_t)hn[k] * n.pool;
-            memcpy(pk.data() + n.dst_fc_b + row, src, sizeof(float) * hn[k]);
-            src += hn[k];
-            row += hn[k];
-        }
-    }
+    pack_heads(flat, n.fc, pk);      // flat order fc_ori, fc_shape, fc_exp, fc_tex = the cat order (:132-138): rows 0..61 as they come
 }
 
 int syn_load_backbone_mobilenet1(syn_handle *h, int arch, const float *flat, size_t n_floats) {
@@ -2669,48 +2648,19 @@ int syn_load_backbone_mobilenet1(syn_handle *h, int arch, const float *flat, siz
         return fail(SYN_ERR_INVALID, "syn_load_backbone_mobilenet1: got %zu floats, %s has %zu", n_floats, arch_name(arch), n.flat_count);
     std::vector<float> pk;
     pack_backbone_mobilenet1(arch, flat, pk);
-    DeviceGuard g(h->device);
-    if (h->d_backbone) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->d_backbone)); h->d_backbone = nullptr; }
-    HIP_TRY(hipMalloc((void **)&h->d_backbone, n.packed_count * sizeof(float)));
-    HIP_TRY(hipMemcpy(h->d_backbone, pk.data(), n.packed_count * sizeof(float), hipMemcpyHostToDevice));
-    h->arch = arch;
-    h->ri = RangeInfo{};
-    h->resnet_fp32 = 0; h->range_events = 0; h->guard_armed = 0; if (h->guard_word) { (void)hipDeviceSynchronize(); *(volatile unsigned *)h->guard_word = 0; }
-    h->resnet_w_unsafe[0] = h->resnet_w_unsafe[1] = h->resnet_w_unsafe[2] = 0;
-    return SYN_OK;
+    return install_backbone(h, arch, pk.data(), pk.size());
 }
 
 // ---- GhostNet: flat = the module's state_dict order without num_batches_tracked (synergynet_amd.synergy3DMM.ghostnet_keys) ----
 size_t syn_ghostnet_flat_count(void) { return gnnet().flat_count; }
 double syn_ghostnet_flops_per_face(void) { return gnnet().flops; }
 
-static void pack_backbone_ghostnet(const float *flat, std::vector<float> &pk) {
+static void pack_backbone_ghostnet(int, const float *flat, std::vector<float> &pk) {
     const GnNet &n = gnnet();
     pk.assign(n.packed_count, 0.f);
-    // BN folding in fp32: scale = gamma / sqrt(var + 1e-5), shift = beta - mean * scale
-    auto fold = [&](const float *bn, int c, size_t scale, size_t shift) {      // bn = weight | bias | running_mean | running_var
-        for (int i = 0; i < c; ++i) {
-            const float sc = bn[i] / sqrtf(bn[3 * c + i] + 1e-5f);
-            pk[scale + i] = sc;
-            pk[shift + i] = bn[c + i] - bn[2 * c + i] * sc;
-        }
-    };
-    auto conv = [&](const GnConv &c) {                         // [cout][cin]: as the kernels read it
-        memcpy(pk.data() + c.dst_w, flat + c.src, sizeof(float) * (size_t)c.cout * c.cin);
-        fold(flat + c.src + (size_t)c.cout * c.cin, c.cout, c.dst_scale, c.dst_shift);
-    };
-    auto dwc = [&](const GnDw &d) {                            // [c][1][k][k] -> tap-major [k*k][c]
-        const int kk = d.k * d.k;
-        for (int c = 0; c < d.c; ++c)
-            for (int t = 0; t < kk; ++t) pk[d.dst_w + (size_t)t * d.c + c] = flat[d.src + (size_t)c * kk + t];
-        fold(flat + d.src + (size_t)d.c * kk, d.c, d.dst_scale, d.dst_shift);
-    };
-    {   // conv_stem.weight [16][3][3][3] -> [ci*9 + ky*3 + kx][16] (launch_mb1_stem's layout)
-        const int c0 = GnNet::kStem;
-        for (int co = 0; co < c0; ++co)
-            for (int t = 0; t < 27; ++t) pk[n.dst_stem_w + (size_t)t * c0 + co] = flat[(size_t)co * 27 + t];
-        fold(flat + (size_t)c0 * 27, c0, n.dst_stem_scale, n.dst_stem_shift);
-    }
+    auto conv = [&](const ConvBn &c) { pack_conv(flat, c, pk); };        // [cout][cin]: as the kernels read it
+    auto dwc = [&](const ConvBn &d) { pack_conv_t(flat, d, pk); };       // [c][1][k][k] -> tap-major [k*k][c]
+    pack_conv_t(flat, n.stem, pk);      // conv_stem.weight [16][3][3][3] -> [ci*9 + ky*3 + kx][16] (launch_mb1_stem's layout)
     for (const GnBlock &b : n.blocks) {
         conv(b.g1p); dwc(b.g1d);
         if (b.stride == 2) dwc(b.dw);
@@ -2728,18 +2678,7 @@ static void pack_backbone_ghostnet(const float *flat, std::vector<float> &pk) {
     conv(n.last);
     memcpy(pk.data() + n.dst_head_w, flat + n.src_head, sizeof(float) * (size_t)GnNet::kPool * GnNet::kLast);
     memcpy(pk.data() + n.dst_head_b, flat + n.src_head + (size_t)GnNet::kPool * GnNet::kLast, sizeof(float) * GnNet::kPool);
-    {   // heads: flat order classifier_ori, _shape, _exp, _texture = the cat order (:227-231): rows 0..61 as they come; _texture is not packed
-        const float *src = flat + n.src_fc;
-        static const int hn[3] = {12, 40, 10};
-        int row = 0;
-        for (int k = 0; k < 3; ++k) {
-            memcpy(pk.data() + n.dst_fc_w + (size_t)row * GnNet::kPool, src, sizeof(float) * hn[k] * GnNet::kPool);
-            src += (size_t)hn[k] * GnNet::kPool;
-            memcpy(pk.data() + n.dst_fc_b + row, src, sizeof(float) * hn[k]);
-            src += hn[k];
-            row += hn[k];
-        }
-    }
+    pack_heads(flat, n.fc, pk);      // flat order classifier_ori, _shape, _exp, _texture = the cat order (:227-231): rows 0..61 as they come
 }
 
 int syn_load_backbone_ghostnet(syn_handle *h, const float *flat, size_t n_floats) {
@@ -2747,55 +2686,24 @@ int syn_load_backbone_ghostnet(syn_handle *h, const float *flat, size_t n_floats
     const GnNet &n = gnnet();
     if (n_floats != n.flat_count) return fail(SYN_ERR_INVALID, "syn_load_backbone_ghostnet: got %zu floats, ghostnet has %zu", n_floats, n.flat_count);
     std::vector<float> pk;
-    pack_backbone_ghostnet(flat, pk);
-    DeviceGuard g(h->device);
-    if (h->d_backbone) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->d_backbone)); h->d_backbone = nullptr; }
-    HIP_TRY(hipMalloc((void **)&h->d_backbone, n.packed_count * sizeof(float)));
-    HIP_TRY(hipMemcpy(h->d_backbone, pk.data(), n.packed_count * sizeof(float), hipMemcpyHostToDevice));
-    h->arch = kArchGhost;
-    h->ri = RangeInfo{};
-    h->resnet_fp32 = 0; h->range_events = 0; h->guard_armed = 0; if (h->guard_word) { (void)hipDeviceSynchronize(); *(volatile unsigned *)h->guard_word = 0; }
-    h->resnet_w_unsafe[0] = h->resnet_w_unsafe[1] = h->resnet_w_unsafe[2] = 0;
-    return SYN_OK;
+    pack_backbone_ghostnet(kArchGhost, flat, pk);
+    return install_backbone(h, kArchGhost, pk.data(), pk.size());
 }
 
 // ---- ResNeSt-50: flat = the module's state_dict order without num_batches_tracked (synergynet_amd.synergy3DMM.resnest50_keys) ----
 size_t syn_resnest50_flat_count(void) { return rsnet().flat_count; }
 double syn_resnest50_flops_per_face(void) { return rsnet().flops; }
 
-static void pack_backbone_resnest50(const float *flat, std::vector<float> &pk) {
+static void pack_backbone_resnest50(int, const float *flat, std::vector<float> &pk) {
     const RsNet &n = rsnet();
     pk.assign(n.packed_count, 0.f);
-    // BN folding in fp32: scale = gamma / sqrt(var + 1e-5), shift = beta - mean * scale
-    auto fold = [&](const float *bn, int c, size_t scale, size_t shift) {      // bn = weight | bias | running_mean | running_var
-        for (int i = 0; i < c; ++i) {
-            const float sc = bn[i] / sqrtf(bn[3 * c + i] + 1e-5f);
-            pk[scale + i] = sc;
-            pk[shift + i] = bn[c + i] - bn[2 * c + i] * sc;
-        }
-    };
-    auto conv = [&](const RsConv &c) {                         // [cout][cin]: as the kernels read it
-        memcpy(pk.data() + c.dst_w, flat + c.src, sizeof(float) * (size_t)c.cout * c.cin);
-        fold(flat + c.src + (size_t)c.cout * c.cin, c.cout, c.dst_scale, c.dst_shift);
-    };
-    auto conv3 = [&](const RsConv3 &c) {                       // [n][cg][3][3] -> [n][tap][cg]
-        const int nn = c.groups * c.ng;
-        for (int o = 0; o < nn; ++o)
-            for (int ci = 0; ci < c.cg; ++ci)
-                for (int t = 0; t < 9; ++t) pk[c.dst_w + ((size_t)o * 9 + t) * c.cg + ci] = flat[c.src + ((size_t)o * c.cg + ci) * 9 + t];
-        fold(flat + c.src + (size_t)nn * c.cg * 9, nn, c.dst_scale, c.dst_shift);
-    };
-    {   // conv1.0.weight [32][3][3][3] -> [ci*9 + ky*3 + kx][32]
-        const int c0 = RsNet::kStem;
-        for (int co = 0; co < c0; ++co)
-            for (int t = 0; t < 27; ++t) pk[n.dst_stem_w + (size_t)t * c0 + co] = flat[(size_t)co * 27 + t];
-        fold(flat + (size_t)c0 * 27, c0, n.dst_stem_scale, n.dst_stem_shift);
-    }
-    conv3(n.stem2);
-    conv3(n.stem3);
+    auto conv = [&](const ConvBn &c) { pack_conv(flat, c, pk); };      // 1x1 [cout][cin]: as the kernels read it; 3x3 [n][cg][3][3] -> [n][tap][cg]
+    pack_conv_t(flat, n.stem, pk);                            // conv1.0.weight [32][3][3][3] -> [ci*9 + ky*3 + kx][32]
+    conv(n.stem2);
+    conv(n.stem3);
     for (const RsBlock &b : n.blocks) {
         conv(b.c1);
-        conv3(b.c2);
+        conv(b.c2);
         const int C = b.C, I = b.inter;
         const float *w1 = flat + b.src_fc, *b1 = w1 + (size_t)I * C, *bn = b1 + I, *w2 = bn + 4 * (size_t)I, *b2 = w2 + 2 * (size_t)C * I;
         for (int j = 0; j < I; ++j) {
@@ -2811,18 +2719,7 @@ static void pack_backbone_resnest50(const float *flat, std::vector<float> &pk) {
         conv(b.c3);
         if (b.down) conv(b.ds);
     }
-    {   // heads: flat order fc_ori, fc_shape, fc_exp, fc_tex; the cat (:320) is ori | shape | exp: rows 0..61 as they come; fc_tex is not packed
-        const float *src = flat + n.src_fc;
-        static const int hn[3] = {12, 40, 10};
-        int row = 0;
-        for (int k = 0; k < 3; ++k) {
-            memcpy(pk.data() + n.dst_fc_w + (size_t)row * RsNet::kPool, src, sizeof(float) * hn[k] * RsNet::kPool);
-            src += (size_t)hn[k] * RsNet::kPool;
-            memcpy(pk.data() + n.dst_fc_b + row, src, sizeof(float) * hn[k]);
-            src += hn[k];
-            row += hn[k];
-        }
-    }
+    pack_heads(flat, n.fc, pk);      // flat order fc_ori, fc_shape, fc_exp, fc_tex; the cat (:320) is ori | shape | exp: rows 0..61 as they come
 }
 
 int syn_load_backbone_resnest50(syn_handle *h, const float *flat, size_t n_floats) {
@@ -2830,16 +2727,8 @@ int syn_load_backbone_resnest50(syn_handle *h, const float *flat, size_t n_float
     const RsNet &n = rsnet();
     if (n_floats != n.flat_count) return fail(SYN_ERR_INVALID, "syn_load_backbone_resnest50: got %zu floats, resnest50 has %zu", n_floats, n.flat_count);
     std::vector<float> pk;
-    pack_backbone_resnest50(flat, pk);
-    DeviceGuard g(h->device);
-    if (h->d_backbone) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->d_backbone)); h->d_backbone = nullptr; }
-    HIP_TRY(hipMalloc((void **)&h->d_backbone, n.packed_count * sizeof(float)));
-    HIP_TRY(hipMemcpy(h->d_backbone, pk.data(), n.packed_count * sizeof(float), hipMemcpyHostToDevice));
-    h->arch = kArchResnest;
-    h->ri = RangeInfo{};
-    h->resnet_fp32 = 0; h->range_events = 0; h->guard_armed = 0; if (h->guard_word) { (void)hipDeviceSynchronize(); *(volatile unsigned *)h->guard_word = 0; }
-    h->resnet_w_unsafe[0] = h->resnet_w_unsafe[1] = h->resnet_w_unsafe[2] = 0;
-    return SYN_OK;
+    pack_backbone_resnest50(kArchResnest, flat, pk);
+    return install_backbone(h, kArchResnest, pk.data(), pk.size());
 }
 
 // ---- resnet18 / resnet34: flat = the module's state_dict order without num_batches_tracked (synergynet_amd.synergy3DMM.resnet_basic_keys) ----
@@ -2849,43 +2738,15 @@ double syn_resnet_basic_flops_per_face(int arch) { return is_bb(arch) ? bbnet(ar
 static void pack_backbone_resnet_basic(int arch, const float *flat, std::vector<float> &pk) {
     const BbNet &n = bbnet(arch);
     pk.assign(n.packed_count, 0.f);
-    // BN folding in fp32: scale = gamma / sqrt(var + 1e-5), shift = beta - mean * scale
-    auto conv = [&](const BbConv &c, bool stem) {
-        const int kk = c.k * c.k;
-        const size_t nw = (size_t)c.cout * c.cin * kk;
-        for (int o = 0; o < c.cout; ++o)
-            for (int ci = 0; ci < c.cin; ++ci)
-                for (int t = 0; t < kk; ++t) {
-                    const float v = flat[c.src + ((size_t)o * c.cin + ci) * kk + t];
-                    if (stem) pk[c.dst_w + ((size_t)ci * kk + t) * c.cout + o] = v;      // [ci*49 + ky*7 + kx][64]
-                    else pk[c.dst_w + ((size_t)o * kk + t) * c.cin + ci] = v;            // [n][tap][cin]
-                }
-        const float *bn = flat + c.src + nw;                   // weight | bias | running_mean | running_var
-        for (int i = 0; i < c.cout; ++i) {
-            const float sc = bn[i] / sqrtf(bn[3 * c.cout + i] + 1e-5f);
-            pk[c.dst_scale + i] = sc;
-            pk[c.dst_shift + i] = bn[c.cout + i] - bn[2 * c.cout + i] * sc;
-        }
-    };
-    conv(n.stem, true);
+    pack_conv_t(flat, n.stem, pk);                            // [64][3][7][7] -> [ci*49 + ky*7 + kx][64]
     for (const BbBlock &b : n.blocks) {
-        conv(b.c1, false);
-        conv(b.c2, false);
-        if (b.down) conv(b.ds, false);
+        pack_conv(flat, b.c1, pk);                            // [n][cin][3][3] -> [n][tap][cin]
+        pack_conv(flat, b.c2, pk);
+        if (b.down) pack_conv(flat, b.ds, pk);
     }
-    {   // heads: flat order fc_tex, fc_ori, fc_shape, fc_exp; the forward's cat (:246) is ori | shape | exp | tex and the adapter takes the
-        // first 62: rows 0..61 = ori | shape | exp; fc_tex is not packed
-        const float *src = flat + n.src_fc + (size_t)40 * BbNet::kPool + 40;
-        static const int hn[3] = {12, 40, 10};
-        int row = 0;
-        for (int k = 0; k < 3; ++k) {
-            memcpy(pk.data() + n.dst_fc_w + (size_t)row * BbNet::kPool, src, sizeof(float) * hn[k] * BbNet::kPool);
-            src += (size_t)hn[k] * BbNet::kPool;
-            memcpy(pk.data() + n.dst_fc_b + row, src, sizeof(float) * hn[k]);
-            src += hn[k];
-            row += hn[k];
-        }
-    }
+    // flat order fc_tex, fc_ori, fc_shape, fc_exp; the forward's cat (:246) is ori | shape | exp | tex and the adapter takes the first 62:
+    // rows 0..61 = ori | shape | exp, which n.fc.src points at; fc_tex is not packed
+    pack_heads(flat, n.fc, pk);
 }
 
 int syn_load_backbone_resnet_basic(syn_handle *h, int arch, const float *flat, size_t n_floats) {
@@ -2895,15 +2756,7 @@ int syn_load_backbone_resnet_basic(syn_handle *h, int arch, const float *flat, s
     if (n_floats != n.flat_count) return fail(SYN_ERR_INVALID, "syn_load_backbone_resnet_basic: got %zu floats, %s has %zu", n_floats, arch_name(arch), n.flat_count);
     std::vector<float> pk;
     pack_backbone_resnet_basic(arch, flat, pk);
-    DeviceGuard g(h->device);
-    if (h->d_backbone) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(h->d_backbone)); h->d_backbone = nullptr; }
-    HIP_TRY(hipMalloc((void **)&h->d_backbone, n.packed_count * sizeof(float)));
-    HIP_TRY(hipMemcpy(h->d_backbone, pk.data(), n.packed_count * sizeof(float), hipMemcpyHostToDevice));
-    h->arch = arch;
-    h->ri = RangeInfo{};
-    h->resnet_fp32 = 0; h->range_events = 0; h->guard_armed = 0; if (h->guard_word) { (void)hipDeviceSynchronize(); *(volatile unsigned *)h->guard_word = 0; }
-    h->resnet_w_unsafe[0] = h->resnet_w_unsafe[1] = h->resnet_w_unsafe[2] = 0;
-    return SYN_OK;
+    return install_backbone(h, arch, pk.data(), pk.size());
 }
 
 static void pack_basis(const float *w_shp, const float *w_exp, const float *u, const float *param_mean, const float *param_std,
@@ -2963,6 +2816,36 @@ int syn_load_basis(syn_handle *h, const float *w_shp, const float *w_exp, const 
     return SYN_OK;
 }
 
+namespace {
+const std::vector<ArchInfo> &arch_table() {
+    static const std::vector<ArchInfo> table = [] {
+        std::vector<ArchInfo> t;
+        const Net &m = net();
+        t.push_back({0, "mobilenet_v2", m.flat_count, m.packed_count, 2 * m.max_io + 2 * m.max_hidden, 1280,
+                     [](int, const float *flat, std::vector<float> &pk) { pack_backbone_mbv2(flat, pk); }});
+        const ResNet50 &r = resnet50();
+        t.push_back({1, "resnet50", r.flat_count, r.packed_count, 4 * r.buf_big + 2 * r.buf_mid, 2048,
+                     [](int, const float *flat, std::vector<float> &pk) { pack_backbone_resnet50(flat, pk); }});
+        static const char *const mb1_names[3] = {"mobilenet_1", "mobilenet_05", "mobilenet_2"};
+        for (int a = kArchMb1First; a <= kArchLast; ++a) {
+            const Mb1Net &n = mb1net(a);
+            t.push_back({a, mb1_names[a - kArchMb1First], n.flat_count, n.packed_count, n.ws_per_face(), n.pool, pack_backbone_mobilenet1});
+        }
+        const GnNet &g = gnnet();
+        t.push_back({kArchGhost, "ghostnet", g.flat_count, g.packed_count, g.ws_per_face(), GnNet::kPool, pack_backbone_ghostnet});
+        const RsNet &s = rsnet();
+        t.push_back({kArchResnest, "resnest50", s.flat_count, s.packed_count, s.ws_per_face(), RsNet::kPool, pack_backbone_resnest50});
+        for (int a : {kArchRes18, kArchRes34}) {
+            const BbNet &n = bbnet(a);
+            t.push_back({a, a == kArchRes18 ? "resnet18" : "resnet34", n.flat_count, n.packed_count, n.ws_per_face(), BbNet::kPool,
+                         pack_backbone_resnet_basic});
+        }
+        return t;
+    }();
+    return table;
+}
+}  // namespace
+
 // Device-free twins of the constant hand-off: pack the blob syn_export_constants would produce straight from host
 // arrays, and run the checks syn_import_constants makes on a host copy of a blob.  No HIP call is made: usable on a machine
 // without a GPU (a loader process, or tests/test_dist_cpu.py's gloo ranks).
@@ -2991,14 +2874,7 @@ int syn_pack_constants_host(int arch, const float *backbone_flat, size_t n_float
     const size_t need = syn_pack_constants_host_bytes(arch, has_bb, has_basis ? n_vert : 0, has_basis ? n_lmk : 0);
     if (bytes < need) return fail(SYN_ERR_INVALID, "syn_pack_constants_host: buffer %zu < %zu bytes", bytes, need);
     std::vector<float> bb, bs;
-    if (has_bb) {
-        if (is_bb(arch)) pack_backbone_resnet_basic(arch, backbone_flat, bb);
-        else if (is_rs(arch)) pack_backbone_resnest50(backbone_flat, bb);
-        else if (is_gn(arch)) pack_backbone_ghostnet(backbone_flat, bb);
-        else if (is_mb1(arch)) pack_backbone_mobilenet1(arch, backbone_flat, bb);
-        else if (arch == 1) pack_backbone_resnet50(backbone_flat, bb);
-        else pack_backbone_mbv2(backbone_flat, bb);
-    }
+    if (has_bb) arch_info(arch)->pack(arch, backbone_flat, bb);
     if (has_basis) pack_basis(w_shp, w_exp, u, param_mean, param_std, keypoints, n_lmk, n_vert, bs);
     ConstHeader hd{};
     hd.magic = kMagic; hd.version = kConstVersion;
@@ -3200,9 +3076,7 @@ int syn_import_constants(syn_handle *h, const void *dev_src, size_t bytes, void 
         h->arch = (int)hd.arch;
         if (!h->d_backbone) HIP_TRY(hipMalloc((void **)&h->d_backbone, hd.backbone_floats * sizeof(float)));
         HIP_TRY(hipMemcpyAsync(h->d_backbone, d, hd.backbone_floats * sizeof(float), hipMemcpyDeviceToDevice, s));
-        h->ri = RangeInfo{};
-        h->resnet_fp32 = 0; h->range_events = 0; h->guard_armed = 0; if (h->guard_word) { (void)hipDeviceSynchronize(); *(volatile unsigned *)h->guard_word = 0; }
-        h->resnet_w_unsafe[0] = h->resnet_w_unsafe[1] = h->resnet_w_unsafe[2] = 0;
+        reset_backbone_state(h);
         if (h->arch == 0) {          // the sender's verdict on its weights rides in the blob
             HIP_TRY(hipMemcpyAsync(&h->ri, d + net().dst_range * sizeof(float), sizeof h->ri, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
@@ -3226,30 +3100,29 @@ size_t syn_workspace_bytes(syn_handle *, int B) {
     return ((size_t)B * (ws_floats_per_face() + syn::kRecFloatsPerFace) + 1024 + syn::kRecSlack) * sizeof(float);
 }
 
+// the forward of whatever the handle runs, on fp32 NCHW crops (img) or uint8 HWC crops (img8)
+static int run_forward(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s) {
+    DeviceGuard g(h->device);
+    if (is_bb(h->arch)) return run_resnet_basic(h, img, img8, B, param, pool, s);
+    if (is_rs(h->arch)) return run_resnest50(h, img, img8, B, param, pool, s);
+    if (is_gn(h->arch)) return run_ghostnet(h, img, img8, B, param, pool, s);
+    if (is_mb1(h->arch)) return run_mobilenet1(h, img, img8, B, param, pool, s);
+    if (h->arch == 1) return run_resnet50(h, img, img8, B, param, pool, s);
+    return run_backbone(h, img, img8, B, param, pool, s);
+}
+
 int syn_backbone_forward(syn_handle *h, const float *img, int B, float *param, float *pool, void *stream) {
     if (!h || !img || !param) return fail(SYN_ERR_INVALID, "syn_backbone_forward: NULL argument");
     if (B <= 0) return fail(SYN_ERR_INVALID, "syn_backbone_forward: B=%d", B);
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_backbone_forward: backbone weights not loaded");
-    DeviceGuard g(h->device);
-    if (is_bb(h->arch)) return run_resnet_basic(h, img, nullptr, B, param, pool, (hipStream_t)stream);
-    if (is_rs(h->arch)) return run_resnest50(h, img, nullptr, B, param, pool, (hipStream_t)stream);
-    if (is_gn(h->arch)) return run_ghostnet(h, img, nullptr, B, param, pool, (hipStream_t)stream);
-    if (is_mb1(h->arch)) return run_mobilenet1(h, img, nullptr, B, param, pool, (hipStream_t)stream);
-    if (h->arch == 1) return run_resnet50(h, img, nullptr, B, param, pool, (hipStream_t)stream);
-    return run_backbone(h, img, nullptr, B, param, pool, (hipStream_t)stream);
+    return run_forward(h, img, nullptr, B, param, pool, (hipStream_t)stream);
 }
 
 int syn_backbone_forward_u8(syn_handle *h, const uint8_t *img, int B, float *param, float *pool, void *stream) {
     if (!h || !img || !param) return fail(SYN_ERR_INVALID, "syn_backbone_forward_u8: NULL argument");
     if (B <= 0) return fail(SYN_ERR_INVALID, "syn_backbone_forward_u8: B=%d", B);
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_backbone_forward_u8: backbone weights not loaded");
-    DeviceGuard g(h->device);
-    if (is_bb(h->arch)) return run_resnet_basic(h, nullptr, img, B, param, pool, (hipStream_t)stream);
-    if (is_rs(h->arch)) return run_resnest50(h, nullptr, img, B, param, pool, (hipStream_t)stream);
-    if (is_gn(h->arch)) return run_ghostnet(h, nullptr, img, B, param, pool, (hipStream_t)stream);
-    if (is_mb1(h->arch)) return run_mobilenet1(h, nullptr, img, B, param, pool, (hipStream_t)stream);
-    if (h->arch == 1) return run_resnet50(h, nullptr, img, B, param, pool, (hipStream_t)stream);
-    return run_backbone(h, nullptr, img, B, param, pool, (hipStream_t)stream);
+    return run_forward(h, nullptr, img, B, param, pool, (hipStream_t)stream);
 }
 
 int syn_backbone_profile(syn_handle *h, const uint8_t *img_hwc, int B, int max_launches, int *feature_of_launch,
@@ -3262,51 +3135,23 @@ int syn_backbone_profile(syn_handle *h, const uint8_t *img_hwc, int B, int max_l
     HIP_TRY(hipMalloc((void **)&param, (size_t)B * 62 * sizeof(float)));
     std::vector<hipEvent_t> marks;
     std::vector<int> feats;
-    if (is_gn(h->arch) || is_rs(h->arch) || is_bb(h->arch)) {           // launch codes of gn_launch_block / rs_launch_block / bb_launch_block in feature_of_launch
-        std::vector<double> fl;
-        int rc = is_bb(h->arch) ? run_resnet_basic(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats, &fl)
-               : is_rs(h->arch) ? run_resnest50(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats, &fl)
-                                : run_ghostnet(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats, &fl);
+    if (is_mb1(h->arch) || is_gn(h->arch) || is_rs(h->arch) || is_bb(h->arch)) {      // feature_of_launch = the launch codes of mb1_launch_layer / gn_ / rs_ / bb_launch_block
+        LaunchMarks lm(nullptr);
+        int rc = is_bb(h->arch) ? run_resnet_basic(h, nullptr, img_hwc, B, param, nullptr, lm.s, &lm)
+               : is_rs(h->arch) ? run_resnest50(h, nullptr, img_hwc, B, param, nullptr, lm.s, &lm)
+               : is_gn(h->arch) ? run_ghostnet(h, nullptr, img_hwc, B, param, nullptr, lm.s, &lm)
+                                : run_mobilenet1(h, nullptr, img_hwc, B, param, nullptr, lm.s, &lm);
         int count = 0;
         if (rc == SYN_OK) {
             HIP_TRY(hipDeviceSynchronize());
-            for (size_t i = 1; i < marks.size() && count < max_launches; ++i, ++count) {
+            for (size_t i = 1; i < lm.events.size() && count < max_launches; ++i, ++count) {
                 float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, marks[i - 1], marks[i]);
-                feature_of_launch[count] = feats[i];
+                (void)hipEventElapsedTime(&ms, lm.events[i - 1], lm.events[i]);
+                feature_of_launch[count] = lm.codes[i];
                 ms_of_launch[count] = ms;
-                flops_of_launch[count] = fl[i] * B;
+                flops_of_launch[count] = lm.flops[i] * B;
             }
         }
-        for (hipEvent_t e : marks) (void)hipEventDestroy(e);
-        (void)hipFree(param);
-        return rc == SYN_OK ? count : rc;
-    }
-    if (is_mb1(h->arch)) {          // launch codes of run_mobilenet1 in feature_of_launch
-        int rc = run_mobilenet1(h, nullptr, img_hwc, B, param, nullptr, nullptr, &marks, &feats);
-        int count = 0;
-        if (rc == SYN_OK) {
-            HIP_TRY(hipDeviceSynchronize());
-            const Mb1Net &n = mb1net(h->arch);
-            const bool fused = mb1_fused(h, B);
-            for (size_t i = 1; i < marks.size() && count < max_launches; ++i, ++count) {
-                float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, marks[i - 1], marks[i]);
-                const int code = feats[i];
-                double fl;
-                if (code == 0) fl = 2.0 * 27 * n.c0 * 3600;
-                else if (code == 27) fl = 2.0 * n.pool * 62 + 16.0 * n.pool;
-                else {
-                    const Mb1Block &b = n.blocks[(code - 1) / 2];
-                    const double dw = 2.0 * 9 * b.cin * b.hout * b.hout, pw = 2.0 * b.cin * b.cout * b.hout * b.hout;
-                    fl = fused ? dw + pw : ((code & 1) ? dw : pw);
-                }
-                feature_of_launch[count] = code;
-                ms_of_launch[count] = ms;
-                flops_of_launch[count] = fl * B;
-            }
-        }
-        for (hipEvent_t e : marks) (void)hipEventDestroy(e);
         (void)hipFree(param);
         return rc == SYN_OK ? count : rc;
     }
@@ -3364,9 +3209,7 @@ int syn_mobilenet1_layer(syn_handle *h, int layer, int fused, const void *in, in
     if (!is_mb1(h->arch))
         return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: this handle runs %s, expected mobilenet_1, mobilenet_05 or mobilenet_2", arch_name(h->arch));
     if (layer < 0 || layer > 14) return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: layer=%d, expected 0 (stem), 1..13 (blocks) or 14 (pool + heads)", layer);
-    if (B < 1 || B > 65536)          // the kernels index pixels (up to 3600 B) and pixel x channel quads in 32-bit integers
-        return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: B=%d, expected 1 <= B <= 65536", B);
-    if (fused != 0 && fused != 1) return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: fused=%d, expected 0 or 1", fused);
+    if (int rc = check_hook_batch("syn_mobilenet1_layer", B, fused)) return rc;
     if (in_u8 && layer != 0) return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: in_u8 is set on layer %d, expected only on layer 0 (the stem)", layer);
     const bool block = layer >= 1 && layer <= 13;
     if (aux && layer == 0) return fail(SYN_ERR_INVALID, "syn_mobilenet1_layer: aux on layer 0, expected NULL (the stem has no second output)");
@@ -3387,7 +3230,7 @@ int syn_mobilenet1_layer(syn_handle *h, int layer, int fused, const void *in, in
         second = h->ws + 2 * (size_t)B * n.buf_io;
     }
     mb1_launch_layer(n, h->d_backbone, layer, fused != 0, in_u8 ? nullptr : (const float *)in, in_u8 ? (const uint8_t *)in : nullptr, B, out,
-                     second, (hipStream_t)stream, [](int) {});
+                     second, (hipStream_t)stream, [](int, double) {});
     HIP_TRY(hipGetLastError());
     return SYN_OK;
 }
@@ -3399,8 +3242,7 @@ int syn_ghostnet_block(syn_handle *h, int block, int fused, const float *in, int
     if (!h || !in || !out) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: NULL argument (handle, in and out are required)");
     if (!is_gn(h->arch)) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: this handle runs %s, expected ghostnet", arch_name(h->arch));
     if (block < 0 || block > 17) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: block=%d, expected 0..15 (bottlenecks), 16 (ConvBnAct) or 17 (pool + conv_head + heads)", block);
-    if (B < 1 || B > 65536) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: B=%d, expected 1 <= B <= 65536", B);      // 32-bit pixel indices
-    if (fused != 0 && fused != 1) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: fused=%d, expected 0 or 1", fused);
+    if (int rc = check_hook_batch("syn_ghostnet_block", B, fused)) return rc;
     const GnNet &n = gnnet();
     size_t f_in, f_out, f_aux;
     if (block == 16) { f_in = 16 * 160; f_out = 16 * (size_t)GnNet::kLast; f_aux = 0; }
@@ -3430,8 +3272,7 @@ int syn_resnest50_block(syn_handle *h, int block, int fused, const float *in, in
     if (!h || !in || !out) return fail(SYN_ERR_INVALID, "syn_resnest50_block: NULL argument (handle, in and out are required)");
     if (!is_rs(h->arch)) return fail(SYN_ERR_INVALID, "syn_resnest50_block: this handle runs %s, expected resnest50", arch_name(h->arch));
     if (block < 0 || block > 17) return fail(SYN_ERR_INVALID, "syn_resnest50_block: block=%d, expected 0 (stem + max pool), 1..16 (bottlenecks) or 17 (pool + heads)", block);
-    if (B < 1 || B > 65536) return fail(SYN_ERR_INVALID, "syn_resnest50_block: B=%d, expected 1 <= B <= 65536", B);      // 32-bit pixel indices
-    if (fused != 0 && fused != 1) return fail(SYN_ERR_INVALID, "syn_resnest50_block: fused=%d, expected 0 or 1", fused);
+    if (int rc = check_hook_batch("syn_resnest50_block", B, fused)) return rc;
     const RsNet &n = rsnet();
     size_t f_in, f_out, f_aux;
     rs_block_counts(n, block, &f_in, &f_out, &f_aux);
@@ -3457,8 +3298,7 @@ int syn_resnet_basic_block(syn_handle *h, int block, int fused, const float *in,
     const BbNet &n = bbnet(h->arch);
     if (block < 0 || block > n.last())
         return fail(SYN_ERR_INVALID, "syn_resnet_basic_block: block=%d, expected 0 (stem + max pool), 1..%d (BasicBlocks) or %d (pool + heads)", block, n.last() - 1, n.last());
-    if (B < 1 || B > 65536) return fail(SYN_ERR_INVALID, "syn_resnet_basic_block: B=%d, expected 1 <= B <= 65536", B);      // 32-bit pixel indices
-    if (fused != 0 && fused != 1) return fail(SYN_ERR_INVALID, "syn_resnet_basic_block: fused=%d, expected 0 or 1", fused);
+    if (int rc = check_hook_batch("syn_resnet_basic_block", B, fused)) return rc;
     size_t f_in, f_out;
     bb_block_counts(n, block, &f_in, &f_out);
     if (n_in != f_in * B || n_out != f_out * B)
@@ -4479,7 +4319,7 @@ syn::SynTrunkW trunk_weights(const syn_handle *h, int which) {
 int synergy_ready(const syn_handle *h, const char *who) {
     if (h->arch != 0 && !is_gn(h->arch))          // ghostnet's pooled feature (the 1280 outputs of conv_head + ReLU) has the same width
         return fail(SYN_ERR_INVALID, "%s: the synergy refinement needs the 1280-d pooled feature of mobilenet_v2 or ghostnet; this handle runs %s (%d-d)", who,
-                    arch_name(h->arch), is_mb1(h->arch) ? mb1net(h->arch).pool : 2048);
+                    arch_name(h->arch), arch_info(h->arch)->pool);
     if (!h->d_syn) return fail(SYN_ERR_NOT_LOADED, "%s: synergy weights not loaded (syn_load_synergy)", who);
     return SYN_OK;
 }

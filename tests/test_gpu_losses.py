@@ -362,6 +362,7 @@ def test_refusals_leave_the_outputs_untouched(model, lgold, pack):
     rn = _with_synergy(SynergyNet(device='cuda:0', pack=pack, backbone_state=synth.make_resnet_basic_state('resnet18'), arch='resnet18'), lgold)
     assert losses(rn) == abi.SYN_ERR_INVALID
     assert b'1280-d' in lib.syn_last_error() and b'resnet18' in lib.syn_last_error()
+    assert b'(512-d)' in lib.syn_last_error()          # the width of the pool THIS handle has
     with pytest.raises(RuntimeError, match='1280-d'):
         rn(torch.zeros(1, 3, 120, 120), target[:1])
     # ... while the two modules on their own work with any backbone
