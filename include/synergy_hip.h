@@ -748,12 +748,14 @@ int syn_mobilenet2_span(syn_handle *h, int first, int last, const void *in, int 
  *                squeeze-and-excite (3, 4, 9, 10, 11, 13, 15) a non-NULL aux receives the gate [B,mid]
  *   block 16     blocks.9.0 (ConvBnAct): in = [B,4,4,160], out = [B,4,4,960]
  *   block 17     pool + conv_head + ReLU + heads: in = [B,4,4,960], out = [B,62], a non-NULL aux receives the pooled feature [B,1280]
+ *   block 18     conv_stem + bn1 + ReLU, the launch the forward makes before block 0: in = normalised fp32 crops NCHW [B,3,120,120],
+ *                out = [B,60,60,16]; no aux, `fused` selects nothing
  * fused = 1: the GhostModules of the block that have a fused launch use it; fused = 0: one launch per layer.  n_in / n_out / n_aux are
  * ELEMENT counts (n_aux = 0 when aux is NULL).  Refused with SYN_ERR_INVALID and a message that names what was expected, before any
  * launch, with `out` untouched: a count that differs from what the block needs, a handle whose arch is not ghostnet, block outside
- * 0..17, B < 1 or B > 65536, fused other than 0 / 1, aux on a block that has neither gate nor pool.  Asynchronous on `stream`; all
+ * 0..18, B < 1 or B > 65536, fused other than 0 / 1, aux on a block that has neither gate nor pool.  Asynchronous on `stream`; all
  * pointers are device pointers; the block's intermediates live in the handle's workspace (one stream at a time, as the forward). */
-int syn_ghostnet_block(syn_handle *h, int block, int fused, const float *in_nhwc, int B, size_t n_in,
+int syn_ghostnet_block(syn_handle *h, int block, int fused, const float *in, int B, size_t n_in,
                        float *out, size_t n_out, float *aux, size_t n_aux, void *stream);
 
 /* One block of the loaded ResNeSt-50 (arch 8) on activations the caller supplies, through exactly the launches the forward uses for that

@@ -129,6 +129,7 @@ _SIGS = {
                                        C.c_size_t, C.c_void_p]),
     'syn_mobilenet2_span': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                       C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+    # block 0..15 bottlenecks, 16 ConvBnAct, 17 pool + conv_head + heads, 18 conv_stem (in = normalised fp32 crops NCHW, no aux)
     'syn_ghostnet_block': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
     'syn_resnest50_block': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,

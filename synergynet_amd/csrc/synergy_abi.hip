@@ -1490,6 +1490,12 @@ int gn_launch_count(const GnNet &n, bool fused) {
     return c;
 }
 
+// conv_stem + bn1 + ReLU: normalised fp32 crops NCHW [B,3,120,120] (img) or uint8 HWC crops (img8) -> [B,60,60,16].  run_ghostnet and
+// block 18 of syn_ghostnet_block both launch it here.
+void gn_launch_stem(const GnNet &n, const float *P, const float *img, const uint8_t *img8, int B, float *out, hipStream_t s) {
+    syn::launch_mb1_stem(img, img8, P + n.stem.dst_w, P + n.stem.dst_scale, P + n.stem.dst_shift, out, GnNet::kStem, B, s);
+}
+
 int run_ghostnet(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s,
                  LaunchMarks *marks = nullptr) {
     const GnNet &n = gnnet();
@@ -1501,7 +1507,7 @@ int run_ghostnet(syn_handle *h, const float *img, const uint8_t *img8, int B, fl
     auto mark = [&](int code, double flops) { if (marks) (*marks)(code, flops); };
     mark(-1, 0.0);
     const bool fused = gn_fused(h);
-    syn::launch_mb1_stem(img, img8, P + n.stem.dst_w, P + n.stem.dst_scale, P + n.stem.dst_shift, X, GnNet::kStem, B, s);
+    gn_launch_stem(n, P, img, img8, B, X, s);
     mark(0, 2.0 * 27 * GnNet::kStem * 3600);
     for (int block = 0; block <= 16; ++block) {
         gn_launch_block(n, P, block, fused, X, B, Y, nullptr, w, s, mark);
@@ -3241,11 +3247,13 @@ int syn_ghostnet_block(syn_handle *h, int block, int fused, const float *in, int
                        size_t n_aux, void *stream) {
     if (!h || !in || !out) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: NULL argument (handle, in and out are required)");
     if (!is_gn(h->arch)) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: this handle runs %s, expected ghostnet", arch_name(h->arch));
-    if (block < 0 || block > 17) return fail(SYN_ERR_INVALID, "syn_ghostnet_block: block=%d, expected 0..15 (bottlenecks), 16 (ConvBnAct) or 17 (pool + conv_head + heads)", block);
+    if (block < 0 || block > 18)
+        return fail(SYN_ERR_INVALID, "syn_ghostnet_block: block=%d, expected 0..15 (bottlenecks), 16 (ConvBnAct), 17 (pool + conv_head + heads) or 18 (conv_stem)", block);
     if (int rc = check_hook_batch("syn_ghostnet_block", B, fused)) return rc;
     const GnNet &n = gnnet();
     size_t f_in, f_out, f_aux;
-    if (block == 16) { f_in = 16 * 160; f_out = 16 * (size_t)GnNet::kLast; f_aux = 0; }
+    if (block == 18) { f_in = 3 * 120 * 120; f_out = 3600 * (size_t)GnNet::kStem; f_aux = 0; }
+    else if (block == 16) { f_in = 16 * 160; f_out = 16 * (size_t)GnNet::kLast; f_aux = 0; }
     else if (block == 17) { f_in = 16 * (size_t)GnNet::kLast; f_out = 62; f_aux = GnNet::kPool; }
     else {
         const GnBlock &b = n.blocks[block];
@@ -3257,6 +3265,11 @@ int syn_ghostnet_block(syn_handle *h, int block, int fused, const float *in, int
                     f_out * B, aux ? f_aux * B : (size_t)0, n_in, n_out, n_aux);
     if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_ghostnet_block: backbone weights not loaded");
     DeviceGuard g(h->device);
+    if (block == 18) {            // the stem needs no workspace; `fused` selects nothing here
+        gn_launch_stem(n, h->d_backbone, in, nullptr, B, out, (hipStream_t)stream);
+        HIP_TRY(hipGetLastError());
+        return SYN_OK;
+    }
     int rc = ensure_ws(h, B);
     if (rc) return rc;
     const GnWs w = gn_ws(n, h->ws + 2 * (size_t)B * n.buf_io, B);

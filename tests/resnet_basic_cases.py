@@ -144,9 +144,11 @@ def resnet_basic_forward(sd, arch, x, dtype=torch.float32, details=False):
     return out.numpy(), pool.numpy()
 
 
-def block_reference(sd, arch, block, x, dtype=torch.float64, **wrong):
+def block_reference(sd, arch, block, x, dtype=torch.float64, variant=None, **wrong):
     """The hook's block (syn_resnet_basic_block) in `dtype` as numpy: block 0 on NCHW crops, the others on NHWC input; out NHWC ([B,62]
-    for the last block)."""
+    for the last block).  variant: one of VARIANTS (below), a BasicBlock with one mistake in one place."""
+    if variant is not None:
+        return variant_reference(sd, arch, block, x, variant, dtype)
     x = torch.as_tensor(np.asarray(x)).to(dtype)
     last = len(blocks(arch)) + 1
     with torch.no_grad():
@@ -156,3 +158,242 @@ def block_reference(sd, arch, block, x, dtype=torch.float64, **wrong):
         if block < last:
             return _basic_block(sd, x, blocks(arch)[block - 1], dtype, **wrong).permute(0, 2, 3, 1).contiguous().numpy()
         return _tail(sd, x, dtype)[0].numpy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# One block at a time, every element judged (tests/test_gpu_resnet_basic_blocks.py): the integer probe, its conditions, the one-place
+# mistakes the probe has to see, and the elementwise fp32 bound of a block.  Shared machinery: tests/exact_probe.py.
+# ---------------------------------------------------------------------------------------------------------------------------------
+import exact_probe as ep          # noqa: E402
+
+PROBE_SEED = 20260
+N_FACES = ep.N_FACES
+# Value sets of the probe by the block's output width.  64 and 128 channels take the sets of mobilenet1_cases; with them a 512 -> 512
+# block reaches 1.6e7 of the 2^24 = 1.68e7 an exact partial sum may have, so 256 and 512 channels (layer3, layer4) take narrower ones.
+# (inputs, conv weights, BN weights); the stem's input is the normalised uint8 crop, the tail's input the integers of the wide set.
+WIDE = ((-3, -2, -1, 0, 1, 2, 3), (-2, -1, 1, 2), (0.5, 1, 2, -1))
+NARROW = ((-1, 0, 1), (-1, 1), (0.5, 1, -1))
+
+
+def value_sets(cout):
+    return NARROW if cout >= 256 else WIDE
+
+
+def last_block(arch):
+    return len(blocks(arch)) + 1
+
+
+def integer_faces(arch, block, n=N_FACES, seed=PROBE_SEED):
+    """The n distinct faces of a block's probe.  Block 0: normalised crops [n,3,120,120] whose values are (2 x - 255) / 256 of uint8 x over
+    the full range (8 fractional bits).  BasicBlocks: integers of the block's input set, NHWC.  Last block: integers in [-3, 3], and no
+    pooled feature is 0 (a 4x4 sum that came out 0 has its first pixel moved by one)."""
+    rng = np.random.default_rng([seed, ARCH_ID[arch], block, n])
+    s = block_shapes(arch)[block]
+    if block == 0:
+        return normalize_u8(rng.integers(0, 256, size=(n, 120, 120, 3), dtype=np.uint8))
+    if block == last_block(arch):
+        x = rng.integers(-3, 4, size=(n, 4, 4, 512)).astype(np.float32)
+        dead = x.sum(axis=(1, 2)) == 0
+        x[:, 0, 0, :] += np.where(dead, np.where(x[:, 0, 0, :] < 3, 1, -1), 0).astype(np.float32)
+        return x
+    return rng.choice(np.asarray(value_sets(s['cout'])[0], np.float32), size=(n, s['hin'], s['hin'], s['cin']))
+
+
+def integer_input(arch, block, B):
+    """a probe batch: slot i holds distinct face exact_probe.batch_index(B)[i]"""
+    return np.ascontiguousarray(integer_faces(arch, block)[ep.batch_index(B)])
+
+
+_INT_STATES = {}
+
+
+def make_integer_state(arch, seed=PROBE_SEED):
+    """A state_dict on which every block of the network is exact in fp32 on integer_faces.  Per block, by its output width (value_sets):
+      64, 128 channels (stem, layer1, layer2): inputs in [-3, 3], conv weights {-2, -1, 1, 2}, BN weight {0.5, 1, 2, -1};
+      256, 512 channels (layer3, layer4):       inputs {-1, 0, 1},  conv weights {-1, 1},        BN weight {0.5, 1, -1};
+      heads: weights {-2, -1, 1, 2}, integer biases in [-8, 8].
+    running_mean 0, running_var V_STAR, integer BN biases: bn1 and bn2 (the latter on conv2 + residual) by the rule of
+    exact_probe.probe_conv_bn on the 8 distinct faces, the downsample's from [-3, 3].  Whether the sets are narrow enough is not assumed:
+    exactness_violations states the condition and tests/test_resnet_basic_cpu.py asserts it for every block."""
+    if (arch, seed) in _INT_STATES:
+        return _INT_STATES[arch, seed]
+    rng = np.random.default_rng([seed, ARCH_ID[arch]])
+    sd = {}
+    with torch.no_grad():
+        _, w, g = WIDE
+        ep.probe_conv_bn(rng, sd, 'conv1', 'bn1', (64, 3, 7, 7), torch.from_numpy(integer_faces(arch, 0)).to(ep.F64), 2, 3, 1, w, g)
+        for i, (key, cin, c, s, down) in enumerate(blocks(arch), start=1):
+            _, w, g = value_sets(c)
+            x = torch.from_numpy(integer_faces(arch, i)).to(ep.F64).permute(0, 3, 1, 2)
+            y = ep.probe_conv_bn(rng, sd, key + '.conv1', key + '.bn1', (c, cin, 3, 3), x, s, 1, 1, w, g)
+            r = ep.probe_conv_bn(rng, sd, key + '.downsample.0', key + '.downsample.1', (c, cin, 1, 1), x, 2, 0, 1, w, g, relu=False) if down else x
+            ep.probe_conv_bn(rng, sd, key + '.conv2', key + '.bn2', (c, c, 3, 3), y, 1, 1, 1, w, g, add=r)
+    for name, n in (('fc_ori', 12), ('fc_shape', 40), ('fc_exp', 10), ('fc_tex', 40)):
+        sd[name + '.weight'] = rng.choice(np.array([-2, -1, 1, 2], np.float32), size=(n, 512))
+        sd[name + '.bias'] = rng.integers(-8, 9, size=n).astype(np.float32)
+    _INT_STATES[arch, seed] = sd
+    return sd
+
+
+# ---- the mistakes a port could make, each confined to ONE place of one block ---------------------------------------------------------
+# taps_pad0 / down_odd are the two alignment mistakes of _basic_block (every pixel of a strided block).  The others:
+#   tap        conv1's centre tap of output pixel (1, 1) read one pixel to the right
+#   halo       the first output row of the second 4-row band (row 4; row 1 on a 4^2 map) takes conv1's upper tap row from the band's own
+#              top input row instead of the halo row above it
+#   last_band  conv2's output row hout - 2 (the first of the 2-row last band of 30^2) is the row above it, of the previous band
+#   down_last  the downsample's last pixel -- (14, 14) of the odd 15^2 map -- read at (2 y - 1, 2 x - 1)
+#   res_face   the residual of the next face of the batch
+VARIANTS = ('taps_pad0', 'down_odd', 'halo', 'last_band', 'down_last', 'tap', 'res_face')
+STRIDED_ONLY = ('taps_pad0', 'down_odd', 'down_last')
+
+
+def variant_block(sd, x, blk, variant, dtype=torch.float64):
+    """_basic_block on NCHW x with one of VARIANTS applied"""
+    if variant in ('taps_pad0', 'down_odd'):
+        return _basic_block(sd, x, blk, dtype, **{variant: True})
+    key, cin, c, s, down = blk
+    assert variant in VARIANTS and (down or variant not in STRIDED_ONLY)
+    w1 = _t(sd, key + '.conv1.weight', dtype)
+    y = F.conv2d(x, w1, None, s, 1)
+    if variant == 'tap':
+        y[:, :, 1, 1] += (x[:, :, s, s + 1] - x[:, :, s, s]) @ w1[:, :, 1, 1].t()
+    if variant == 'halo':
+        yb = 4 if y.shape[2] > 4 else 1
+        d = torch.zeros_like(x)
+        d[:, :, s * yb - 1] = x[:, :, s * yb] - x[:, :, s * yb - 1]
+        top = torch.zeros_like(w1)
+        top[:, :, 0] = w1[:, :, 0]
+        y[:, :, yb] += F.conv2d(d, top, None, s, 1)[:, :, yb]
+    y = torch.relu(_bn(sd, y, key + '.bn1', dtype))
+    y = F.conv2d(y, _t(sd, key + '.conv2.weight', dtype), None, 1, 1)
+    if variant == 'last_band':
+        y[:, :, -2] = y[:, :, -3].clone()
+    y = _bn(sd, y, key + '.bn2', dtype)
+    r = x
+    if down:
+        r = x[:, :, ::2, ::2].clone()
+        if variant == 'down_last':
+            r[:, :, -1, -1] = x[:, :, 2 * (r.shape[2] - 1) - 1, 2 * (r.shape[3] - 1) - 1]
+        r = _bn(sd, F.conv2d(r, _t(sd, key + '.downsample.0.weight', dtype)), key + '.downsample.1', dtype)
+    if variant == 'res_face':
+        r = torch.roll(r, -1, dims=0)
+    return torch.relu(y + r)
+
+
+def variant_reference(sd, arch, block, x, variant, dtype=torch.float64):
+    """block_reference of a BasicBlock (NHWC in and out) with one of VARIANTS applied"""
+    assert 0 < block < last_block(arch)
+    with torch.no_grad():
+        xin = torch.as_tensor(np.asarray(x)).to(dtype).permute(0, 3, 1, 2)
+        return variant_block(sd, xin, blocks(arch)[block - 1], variant, dtype).permute(0, 2, 3, 1).contiguous().numpy()
+
+
+def variants_of(arch, block):
+    """the VARIANTS that exist on a block"""
+    if not 0 < block < last_block(arch):
+        return ()
+    return tuple(v for v in VARIANTS if block_shapes(arch)[block]['down'] or v not in STRIDED_ONLY)
+
+
+# ---- the conditions under which the probe is exact ------------------------------------------------------------------------------------
+def exactness_violations(sd_ref, arch, block, x):
+    """The conditions of the probe on the float64 trace of one block (sd_ref: exact_probe.reference_state of the integer state; x: the
+    block's input as block_reference takes it); returns the list of violations, empty = all hold.  Per stage, the residual add included:
+    the output is a multiple of 2^-q; 2^q (|s| sum |a||w| + |shift| (+ |residual|)) < 2^24, so every partial sum in any order is an
+    fp32 number; the output is not constant; every ReLU map is partly clamped and has no dead channel.
+    q: 8 from the normalised pixel and 1 from BN weight 0.5 in the stem (9); 1 behind conv1 and the downsample, 2 behind conv2 and the
+    add; 4 for the mean of 16 and the heads."""
+    bad = []
+    f = ep.F64
+    x = torch.as_tensor(np.asarray(x)).to(f)
+
+    def stage(name, y, mag, q, relu):
+        if not ep.is_multiple(y, q):
+            bad.append(f'{name}: output is no multiple of 2^-{q}')
+        if not float(mag.max()) * 2.0 ** q < 2.0 ** 24:
+            bad.append(f'{name}: 2^{q} (|s| sum |a||w| + |shift| + |residual|) = {float(mag.max()) * 2.0 ** q:.4g} >= 2^24')
+        if float(y.min()) == float(y.max()):
+            bad.append(f'{name}: constant output')
+        if relu and not ep.relu_is_partly_clamped(y):
+            bad.append(f'{name}: the ReLU map is not partly clamped, or a channel is dead')
+
+    with torch.no_grad():
+        if block == 0:
+            y = torch.relu(_bn(sd_ref, F.conv2d(x, _t(sd_ref, 'conv1.weight', f), None, 2, 3), 'bn1', f))
+            stage('stem', y, ep.conv_magnitude(sd_ref, 'conv1', 'bn1', x, 2, 3, 1), 9, True)
+            p = F.max_pool2d(y, 3, 2, 1)
+            if float(p.min()) == float(p.max()) or not bool((p == 0).any()):
+                bad.append('max pool: constant, or no window is clamped throughout')
+            return bad
+        if block == last_block(arch):
+            x = x.permute(0, 3, 1, 2)
+            out, pool = _tail(sd_ref, x, f)
+            wmax = max(float(_t(sd_ref, n + '.weight', f).abs().max()) for n in HEADS62)
+            bmax = max(float(_t(sd_ref, n + '.bias', f).abs().max()) for n in HEADS62)
+            if not (ep.is_multiple(pool, 4) and ep.is_multiple(out, 4)):
+                bad.append('pool / heads: no multiple of 2^-4')
+            if not (16 * float(x.abs().amax()) * 16 < 2.0 ** 24 and 16 * (512 * float(pool.abs().max()) * wmax + bmax) < 2.0 ** 24):
+                bad.append('pool / heads: partial sums reach 2^24')
+            if bool((pool == 0).any()) or float(out.min()) == float(out.max()):
+                bad.append('pool / heads: a pooled feature is 0, or the output is constant')
+            return bad
+        key, cin, c, s, down = blocks(arch)[block - 1]
+        x = x.permute(0, 3, 1, 2)
+        y1 = torch.relu(_bn(sd_ref, F.conv2d(x, _t(sd_ref, key + '.conv1.weight', f), None, s, 1), key + '.bn1', f))
+        stage(key + ' conv1', y1, ep.conv_magnitude(sd_ref, key + '.conv1', key + '.bn1', x, s, 1, 1), 1, True)
+        r = x
+        if down:
+            r = _bn(sd_ref, F.conv2d(x, _t(sd_ref, key + '.downsample.0.weight', f), None, 2, 0), key + '.downsample.1', f)
+            stage(key + ' downsample', r, ep.conv_magnitude(sd_ref, key + '.downsample.0', key + '.downsample.1', x, 2, 0, 1), 1, False)
+        y2 = _bn(sd_ref, F.conv2d(y1, _t(sd_ref, key + '.conv2.weight', f), None, 1, 1), key + '.bn2', f)
+        out = torch.relu(y2 + r)
+        stage(key + ' conv2 + residual', out, ep.conv_magnitude(sd_ref, key + '.conv2', key + '.bn2', y1, 1, 1, 1) + r.abs(), 2, True)
+        if r.shape[0] > 1 and float((r - torch.roll(r, -1, dims=0)).abs().amax(dim=(1, 2, 3)).min()) == 0:
+            bad.append(key + ': neighbouring faces have the same residual')
+    return bad
+
+
+# ---- the fp32 bound of a block --------------------------------------------------------------------------------------------------------
+def block_bound(sd, arch, block, x):
+    """Elementwise bound of |got - block_reference(float64)| for fp32 arithmetic on the fp32 input x, in the layout of block_reference's
+    result.  The hook returns no intermediate, so the bound is carried (exact_probe): stem: the 147-term convolution, ReLU, the largest
+    bound of the pool window.  BasicBlock: conv1's bound through ReLU into conv2 (|s| sum |w| e), on a strided block the downsample's
+    own bound, the add, ReLU.  Last block: the 16-term mean, then the heads' bound on the float64 pool plus the pool's bound carried
+    through sum |W| e."""
+    f = ep.F64
+    x = torch.as_tensor(np.asarray(x)).to(f)
+    with torch.no_grad():
+        if block == 0:
+            a, e = ep.relu_pair(*ep.conv_bn_pair(sd, 'conv1', 'bn1', x, None, 2, 3, 1))
+            return ep.max_pool_pair(a, e, 3, 2, 1)[1].permute(0, 2, 3, 1).contiguous().numpy()
+        x = x.permute(0, 3, 1, 2)
+        if block == last_block(arch):
+            pool, e = ep.mean_pair(x, None)
+            return ep.heads_pair(sd, HEADS62, pool, e)[1].numpy()
+        key, cin, c, s, down = blocks(arch)[block - 1]
+        a1, e1 = ep.relu_pair(*ep.conv_bn_pair(sd, key + '.conv1', key + '.bn1', x, None, s, 1, 1))
+        a2, e2 = ep.conv_bn_pair(sd, key + '.conv2', key + '.bn2', a1, e1, 1, 1, 1)
+        r, er = ep.conv_bn_pair(sd, key + '.downsample.0', key + '.downsample.1', x, None, 2, 0, 1) if down else (x, None)
+        return ep.relu_pair(*ep.add_pair(a2, e2, r, er))[1].permute(0, 2, 3, 1).contiguous().numpy()
+
+
+# Every grid-shape branch of the LDS kernel's launcher (bb_lds_grid), each at the smallest batch that takes it: bands of one face
+# (30^2, 15^2, the 15 -> 8 convolution, and the small maps while the batch is small), whole faces without the halo once that grid has
+# 256 workgroups (8^2: one face, 4^2: two; the 8 -> 4 convolution: one), and the channels split over blockIdx.y while the grid has fewer
+# than 512 workgroups and every wave keeps a work item.  (The channels are never staged in chunks -- DESIGN 5.16 says why.)
+GRID_CASES = [
+    ('layer1.1', 1, 'bands of 4 rows + a last one of 2, no channel split (64 channels: two items per tile group)'),
+    ('layer3.0', 1, 'bands, stride 2 with the downsample, channels split in 2'),
+    ('layer3.0', 256, 'bands, stride 2 with the downsample, 512 workgroups: no split'),
+    ('layer3.1', 127, '8^2: the last batch in bands (2 per face, channels split in 2)'),
+    ('layer3.1', 128, '8^2: one whole face per workgroup, channels split in 2'),
+    ('layer3.1', 512, '8^2: one whole face, 512 workgroups: no split'),
+    ('layer4.0', 63, '8 -> 4 with the downsample: the last batch in bands of 2 rows (half a tile), channels split in 4'),
+    ('layer4.0', 64, '8 -> 4 with the downsample: one whole face, channels split in 4'),
+    ('layer4.0', 256, 'the same, 256 workgroups: split in 2'),
+    ('layer4.0', 512, 'the same, 512 workgroups: no split'),
+    ('layer4.1', 126, '4^2: the last batch with one face = one band per workgroup, channels split in 4'),
+    ('layer4.1', 127, '4^2: two faces per workgroup, the last one half full, channels split in 4'),
+    ('layer4.1', 512, '4^2: 256 workgroups of two faces, split in 2'),
+    ('layer4.1', 1023, '4^2: 512 workgroups, the last half full: no split'),
+]

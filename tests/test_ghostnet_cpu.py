@@ -170,3 +170,96 @@ def test_unknown_arch_is_refused_before_a_gpu_is_needed():
     from synergynet_amd import SynergyNet
     with pytest.raises(RuntimeError, match=r'Please choose \[.*ghostnet, mobilenet_1, mobilenet_05, mobilenet_2\]'):
         SynergyNet(arch='ghostnet_x', load_constants=False)
+
+
+# ---- the block-level probes of tests/test_gpu_ghostnet_blocks.py: their conditions, their teeth, and the bound -------------------------
+import exact_probe as ep          # noqa: E402
+
+PROBE_BATCHES = (1, 3, 5)
+
+
+def test_integer_state_is_a_ghostnet_checkpoint():
+    from synergynet_amd.synergy3DMM import flatten_backbone
+    sd = gc.make_integer_state()
+    assert flatten_backbone(sd, arch='ghostnet').size == 4054138
+    assert all(np.array_equal(v, np.rint(v)) for k, v in sd.items() if k.endswith('.bias') or k.endswith('conv.weight') or k.endswith('.0.weight'))
+    for i in range(19):
+        f = gc.integer_faces(i)
+        assert f.shape == (8,) + gc.hook_counts(i)[0] and all(not np.array_equal(f[a], f[b]) for a in range(8) for b in range(a))
+
+
+@pytest.mark.parametrize('block', range(19))
+def test_integer_probe_is_exact_and_not_vacuous(block):
+    """exactness_violations is empty on the 8 distinct faces and on every probe batch (a larger batch holds the same 8 faces): every
+    stage exact, no constant output, every ReLU map partly clamped without a dead channel, and on the SE blocks a gate of exact 0 / 1
+    that is saturated by more than 100 x the bound of its pre-activation, differs between the faces and is 25 .. 75 % open."""
+    assert not gc.exactness_violations(block, gc.integer_faces(block))
+    for B in PROBE_BATCHES:
+        bad = gc.exactness_violations(block, gc.integer_input(block, B))
+        assert not bad, (B, bad)
+    if block in gc.SE_BLOCKS:
+        print(f'block {block}: smallest (|z| - 3) / bound = {gc.SE_MARGIN[block]:.0f}')
+        assert gc.SE_MARGIN[block] > 100
+
+
+def test_staged_bottleneck_is_the_bottleneck():
+    from synergynet_amd import synth
+    sd = synth.make_ghostnet_state(gc.SEED)
+    for block in (1, 3, 5, 9, 12):
+        s = gc.block_shapes()[block]
+        x = np.random.default_rng(block).standard_normal((2, s['hin'], s['hin'], s['cin'])).astype(np.float32)
+        want, gate = gc.block_reference(sd, block, x)
+        xin = torch.from_numpy(x).double().permute(0, 3, 1, 2)
+        with torch.no_grad():
+            got, g = gc._bottleneck_staged(sd, xin, gc.BLOCKS[block], torch.float64)
+        # float64 throughout; the SE convolutions are a matrix product here and a conv2d there, which sum in different orders
+        assert gc.rel_max(got.permute(0, 2, 3, 1).numpy(), want) < 1e-13 and (gate is None or gc.rel_max(g.numpy(), gate) < 1e-13)
+        if gate is not None:                                          # the gate handed back in reproduces the block
+            assert gc.rel_max(gc.probe_reference(sd, block, x, gate=gate)[0], want) < 1e-13
+
+
+def test_every_variant_changes_the_probe():
+    """Each one-place mistake of ghostnet_cases.VARIANTS, applied to the float64 reference of the probe at B = 3, changes at least one
+    element on every block it exists on, so the equality test of the GPU file fails for a kernel that makes it.  Printed next to it:
+    the rel_max of the same mistake on the gaussian block case of test_every_block_alone, the figure the 1e-4 bar looks at."""
+    from synergynet_amd import synth
+    sd_int, sd_g = ep.reference_state(gc.make_integer_state()), synth.make_ghostnet_state(gc.SEED)
+    seen = set()
+    for block in range(16):
+        s = gc.block_shapes()[block]
+        x = gc.integer_input(block, 3)
+        right = gc.probe_reference(sd_int, block, x)[0].astype(np.float32)
+        xg = np.random.default_rng(9000 + 100 * block + 3).standard_normal(x.shape).astype(np.float32)
+        right_g = gc.probe_reference(sd_g, block, xg)[0]
+        line = []
+        for v in gc.variants_of(block):
+            n = int((gc.probe_reference(sd_int, block, x, variant=v)[0].astype(np.float32) != right).sum())
+            line.append(f'{v} {n} el, gaussian rel_max {gc.rel_max(gc.probe_reference(sd_g, block, xg, variant=v)[0], right_g):.3g}')
+            assert n > 0, (block, v)
+            seen.add(v)
+        print(f'block {block} ({s["key"]}): ' + '; '.join(line))
+    assert seen == set(gc.VARIANTS)
+    assert [b for b in range(18) if 'dw_s2_edge' in gc.variants_of(b)] == [5] and [b for b in range(18) if 'gate_face' in gc.variants_of(b)] == gc.SE_BLOCKS
+    assert 'ntail' in gc.variants_of(7) and 'kslot' in gc.variants_of(7) and gc.variants_of(16) == gc.variants_of(17) == ()
+
+
+def test_torch_fp32_stays_under_the_block_bound():
+    """torch's own fp32 CPU block against the float64 one on the gaussian checkpoint, on both inputs of the GPU test: max(err / bound) per
+    block and part has to be below 1, or the bound is wrong.  SE blocks as on the GPU: the gate under its own bound, the output against
+    the float64 block that uses the fp32 gate."""
+    from synergynet_amd import synth
+    sd = synth.make_ghostnet_state(gc.SEED)
+    rng = np.random.default_rng(79)
+    order = [gc.STEM] + list(range(18))
+    prev, worst = synth.normalize_crops(synth.make_crops(2, seed=904)), {}
+    for block in order:
+        chain = prev.astype(np.float32)
+        for x in (chain, rng.standard_normal(chain.shape).astype(np.float32)):
+            got, aux = gc.probe_reference(sd, block, x, dtype=torch.float32)
+            ref, ref_aux = gc.probe_reference(sd, block, x)
+            if x is chain:
+                prev = ref if block != 17 else None
+            for name, r in gc.judge(sd, block, x, got, aux):
+                worst[block, name] = max(worst.get((block, name), 0.0), r)
+    print('torch fp32 max(err / bound): ' + ', '.join(f'{b}:{n} {r:.3g}' for (b, n), r in worst.items()))
+    assert max(worst.values()) < 1.0 and min(worst.values()) > 0.0

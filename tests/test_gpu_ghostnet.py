@@ -1,7 +1,7 @@
 """GPU parity of the GhostNet backbone (arch = 'ghostnet'): the HIP path against the reference module's recorded outputs
 (tests/golden/ghostnet_outputs.npz) and against the torch restatement of tests/ghostnet_cases.py, which tests/test_ghostnet_cpu.py
 holds against the same recording -- never against the library itself.  Bar: rel_max < 1e-4 (TOL of tests/test_gpu_parity.py); the two
-schedules of the network, both exact fp32 and summing in the same order, agree to 1e-5."""
+schedules of the network, both exact fp32 and summing in the same order, agree bit for bit."""
 import os
 import warnings
 
@@ -139,7 +139,7 @@ def test_block_hook_refuses_wrong_sizes(model):
     lib, h = model._lib, model._h
     x = torch.zeros(80 * 64, device='cuda')
     out = torch.full((80 * 64,), 7.0, device='cuda')
-    for args in ((7, 0, 1, x.numel() - 4, out.numel(), 0), (7, 0, 1, x.numel(), out.numel() + 4, 0), (18, 0, 1, x.numel(), out.numel(), 0),
+    for args in ((7, 0, 1, x.numel() - 4, out.numel(), 0), (7, 0, 1, x.numel(), out.numel() + 4, 0), (19, 0, 1, x.numel(), out.numel(), 0),
                  (7, 2, 1, x.numel(), out.numel(), 0), (7, 0, 0, x.numel(), out.numel(), 0)):
         block, fused, B, ni, no, na = args
         assert lib.syn_ghostnet_block(h, block, fused, x.data_ptr(), B, ni, out.data_ptr(), no, None, na, None) == abi.SYN_ERR_INVALID
@@ -193,7 +193,8 @@ def test_borders_and_neighbouring_faces(model, state):
 
 @pytest.mark.parametrize('B', [5, 130])
 def test_schedules_agree(model, per_layer_model, B):
-    """The fused GhostModules (primary in LDS) against one launch per layer (primary through HBM): the same sums in the same order."""
+    """The fused GhostModules (primary in LDS) against one launch per layer (primary through HBM): the same sums in the same order, so the
+    same bits, from either ingest."""
     import torch
     from synergynet_amd import synth
     assert model._lib.syn_backbone_launch_count(model._h) == 79
@@ -205,7 +206,7 @@ def test_schedules_agree(model, per_layer_model, B):
         (a, ap), (b, bp) = run(model), run(per_layer_model)
         e_param, e_pool = rel_max(a.cpu().numpy(), b.cpu().numpy()), rel_max(ap.cpu().numpy(), bp.cpu().numpy())
         print(f'B={B} {name}: param {e_param:.3g}, pool {e_pool:.3g}, bit-identical {torch.equal(a, b) and torch.equal(ap, bp)}')
-        assert torch.isfinite(a).all() and e_param < 1e-5 and e_pool < 1e-5
+        assert torch.isfinite(a).all() and torch.equal(a, b) and torch.equal(ap, bp)
     prev = model._lib.syn_set_schedule(model._h, 0)
     try:
         assert model._lib.syn_backbone_launch_count(model._h) == 104

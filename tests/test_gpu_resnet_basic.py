@@ -173,26 +173,7 @@ def test_output_guard(models, arch, name, fused):
     assert rel_max(got, want) < TOL
 
 
-# Every grid-shape branch of the LDS kernel's launcher (bb_lds_grid), each at the smallest batch that takes it: bands of one face
-# (30^2, 15^2, the 15 -> 8 convolution, and the small maps while the batch is small), whole faces without the halo once that grid has
-# 256 workgroups (8^2: one face, 4^2: two; the 8 -> 4 convolution: one), and the channels split over blockIdx.y while the grid has fewer
-# than 512 workgroups and every wave keeps a work item.  (The channels are never staged in chunks -- DESIGN 5.16 says why.)
-GRID_CASES = [
-    ('layer1.1', 1, 'bands of 4 rows + a last one of 2, no channel split (64 channels: two items per tile group)'),
-    ('layer3.0', 1, 'bands, stride 2 with the downsample, channels split in 2'),
-    ('layer3.0', 256, 'bands, stride 2 with the downsample, 512 workgroups: no split'),
-    ('layer3.1', 127, '8^2: the last batch in bands (2 per face, channels split in 2)'),
-    ('layer3.1', 128, '8^2: one whole face per workgroup, channels split in 2'),
-    ('layer3.1', 512, '8^2: one whole face, 512 workgroups: no split'),
-    ('layer4.0', 63, '8 -> 4 with the downsample: the last batch in bands of 2 rows (half a tile), channels split in 4'),
-    ('layer4.0', 64, '8 -> 4 with the downsample: one whole face, channels split in 4'),
-    ('layer4.0', 256, 'the same, 256 workgroups: split in 2'),
-    ('layer4.0', 512, 'the same, 512 workgroups: no split'),
-    ('layer4.1', 126, '4^2: the last batch with one face = one band per workgroup, channels split in 4'),
-    ('layer4.1', 127, '4^2: two faces per workgroup, the last one half full, channels split in 4'),
-    ('layer4.1', 512, '4^2: 256 workgroups of two faces, split in 2'),
-    ('layer4.1', 1023, '4^2: 512 workgroups, the last half full: no split'),
-]
+GRID_CASES = bc.GRID_CASES          # every grid-shape branch of the LDS kernel's launcher (bb_lds_grid): tests/resnet_basic_cases.py
 
 
 @pytest.mark.parametrize('name,B,what', GRID_CASES, ids=[f'{n}-B{b}' for n, b, _ in GRID_CASES])

@@ -214,3 +214,102 @@ def test_deeper_resnets_are_refused_before_a_gpu_is_needed(arch):
     from synergynet_amd import SynergyNet
     with pytest.raises(RuntimeError, match=r'Please choose \[mobilenet_v2, resnet50, resnest50, ghostnet, mobilenet_1, mobilenet_05, mobilenet_2\], resnet18 or resnet34'):
         SynergyNet(arch=arch, load_constants=False)
+
+
+# ---- the block-level probes of tests/test_gpu_resnet_basic_blocks.py: their conditions, their teeth, and the bound ------------------------
+import exact_probe as ep          # noqa: E402
+
+ALL_BLOCKS = [(a, b) for a in bc.ARCHS for b in range(len(bc.block_shapes(a)))]
+
+
+@pytest.fixture(scope='module')
+def int_states():
+    return {a: ep.reference_state(bc.make_integer_state(a)) for a in bc.ARCHS}
+
+
+def test_probe_constants_and_batches():
+    """V_STAR makes the fp32 fold's scale gamma itself, V_STAR64 does the same for the float64 reference; a probe batch of any size is made
+    of 8 distinct faces and neighbouring slots differ."""
+    assert np.float32(ep.V_STAR) + np.float32(1e-5) == np.float32(1) and np.float64(ep.V_STAR64) + np.float64(1e-5) == 1.0
+    for B in (1, 3, 5, 127, 1023):
+        idx = ep.batch_index(B)
+        assert idx.shape == (B,) and idx.min() >= 0 and idx.max() < 8 and (B < 2 or (idx[1:] != idx[:-1]).all())
+    assert sorted(ep.batch_index(8)) == list(range(8))
+    for arch in bc.ARCHS:
+        f = bc.integer_faces(arch, 1)
+        assert all(not np.array_equal(f[i], f[j]) for i in range(8) for j in range(i))
+        crops = bc.integer_faces(arch, 0)
+        assert crops.shape == (8, 3, 120, 120) and np.array_equal(crops * 256, np.rint(crops * 256)) and crops.min() == -255 / 256 and crops.max() == 255 / 256
+
+
+@pytest.mark.parametrize('arch,block', ALL_BLOCKS)
+def test_integer_probe_is_exact_and_not_vacuous(int_states, arch, block):
+    """exactness_violations is empty on the 8 distinct faces, of which every probe batch (B = 1, 3 and the GRID_CASES) is made; so it is
+    on every batch.  The narrow value sets are in force exactly where the wide ones would not fit."""
+    bad = bc.exactness_violations(int_states[arch], arch, block, bc.integer_faces(arch, block))
+    assert not bad, bad
+    for B in (1, 3):
+        assert np.array_equal(bc.integer_input(arch, block, B), bc.integer_faces(arch, block)[ep.batch_index(B)])
+        bad = bc.exactness_violations(int_states[arch], arch, block, bc.integer_input(arch, block, B))
+        assert not bad, (B, bad)
+    sd = bc.make_integer_state(arch)
+    if 0 < block < bc.last_block(arch):
+        key, cout = bc.block_shapes(arch)[block]['key'], bc.block_shapes(arch)[block]['cout']
+        x, w, g = bc.value_sets(cout)
+        assert (cout >= 256) == (x == (-1, 0, 1))
+        assert set(np.unique(sd[key + '.conv1.weight'])) == set(w) == set(np.unique(sd[key + '.conv2.weight']))
+        assert set(np.unique(sd[key + '.bn2.weight'])) <= set(g) and set(np.unique(bc.integer_faces(arch, block))) == set(x)
+
+
+@pytest.mark.parametrize('arch', bc.ARCHS)
+def test_every_variant_changes_the_probe(int_states, arch):
+    """Each one-place mistake of resnet_basic_cases.VARIANTS, applied to the float64 reference of the probe at B = 3, changes at least one
+    element on every block it exists on -- the equality test of the GPU file fails for a kernel that makes it.  On the gaussian block
+    case of test_every_block_alone the same mistakes are printed as rel_max, the figure the 1e-4 bar looks at: a BasicBlock spreads one
+    wrong pixel over nine and every channel, so none of them hides under it at block granularity (0.05 at the least)."""
+    from synergynet_amd import synth
+    gauss = synth.make_resnet_basic_state(arch, bc.SEED)
+    for block in range(1, bc.last_block(arch)):
+        x = bc.integer_input(arch, block, 3)
+        right = bc.block_reference(int_states[arch], arch, block, x)
+        s = bc.block_shapes(arch)[block]
+        xg = np.random.default_rng(9000 + block).standard_normal((3, s['hin'], s['hin'], s['cin'])).astype(np.float32)
+        right_g = bc.block_reference(gauss, arch, block, xg)
+        assert set(bc.variants_of(arch, block)) == set(bc.VARIANTS if s['down'] else [v for v in bc.VARIANTS if v not in bc.STRIDED_ONLY])
+        line = []
+        for v in bc.variants_of(arch, block):
+            wrong = bc.block_reference(int_states[arch], arch, block, x, variant=v)
+            n = int((wrong.astype(np.float32) != right.astype(np.float32)).sum())
+            line.append(f'{v} {n} el, gaussian rel_max {bc.rel_max(bc.block_reference(gauss, arch, block, xg, variant=v), right_g):.3g}')
+            assert n > 0, (arch, block, v)
+        print(f'{arch} block {block} ({s["key"]}): ' + '; '.join(line))
+
+
+def test_old_and_new_alignment_variants_are_the_same_mistake(states):
+    x = np.random.default_rng(3).standard_normal((2, 15, 15, 128)).astype(np.float32)
+    block = 1 + [b[0] for b in bc.blocks('resnet18')].index('layer3.0')
+    for v in ('taps_pad0', 'down_odd'):
+        assert np.array_equal(bc.block_reference(states['resnet18'], 'resnet18', block, x, variant=v),
+                              bc.block_reference(states['resnet18'], 'resnet18', block, x, **{v: True}))
+
+
+@pytest.mark.parametrize('arch', bc.ARCHS)
+def test_torch_fp32_stays_under_the_block_bound(states, arch):
+    """torch's own fp32 CPU block against the float64 one on the gaussian checkpoint, both inputs of the GPU test (the previous block's
+    output on real crops, and a sign-mixed N(0,1) tensor): max(err / bound) per block has to be below 1, or the bound is wrong."""
+    from synergynet_amd import synth
+    sd = states[arch]
+    rng = np.random.default_rng(78)
+    prev = synth.normalize_crops(synth.make_crops(2, seed=902))
+    worst = []
+    for block in range(len(bc.block_shapes(arch))):
+        chain = prev.astype(np.float32)
+        ratios = []
+        for x in (chain, rng.standard_normal(chain.shape).astype(np.float32)):
+            ref, bound = bc.block_reference(sd, arch, block, x), bc.block_bound(sd, arch, block, x)
+            ratios.append(ep.bound_ratio(bc.block_reference(sd, arch, block, x, dtype=torch.float32), ref, bound))
+            if x is chain:
+                prev = ref
+        worst.append(max(ratios))
+    print(f'{arch} torch fp32 max(err / bound) per block: ' + ', '.join(f'{i}:{r:.3g}' for i, r in enumerate(worst)))
+    assert max(worst) < 1.0 and min(worst) > 0.0
