@@ -1,4 +1,5 @@
-"""What the block-level exact probes of GhostNet and of the BasicBlock ResNets share (tests/ghostnet_cases.py, tests/resnet_basic_cases.py):
+"""What the block-level exact probes of GhostNet, of the BasicBlock ResNets and of ResNeSt-50 share (tests/ghostnet_cases.py,
+tests/resnet_basic_cases.py, tests/resnest_cases.py):
 the probe batch, the builder of a probe layer, and the propagation of the elementwise fp32 bound through the stages of a block.  The
 constants and the two small helpers keep the meaning they have in tests/mobilenet1_cases.py and are imported from there.
 
@@ -36,13 +37,14 @@ def fold64(sd, bn):
 
 
 # ---- the probe-layer builder ---------------------------------------------------------------------------------------------------------
-def probe_conv_bn(rng, sd, conv, bn, shape, a, stride, pad, groups, wset, gset, relu=True, add=None):
+def probe_conv_bn(rng, sd, conv, bn, shape, a, stride, pad, groups, wset, gset, relu=True, add=None, clamp_all=False):
     """Draws one conv + BN of the probe into sd and returns its output on `a` (NCHW float64: the N_FACES distinct faces).  Weights from wset
     (no zero: a zero weight hides its term), running_mean 0, running_var V_STAR, gamma from gset (signed powers of two), integer bias.
     relu = True: ReLU follows (after `add`, a residual, where given) and the bias keeps it from hiding the probe, by the rule of
     mobilenet1_cases.make_integer_state on all the distinct faces: three channels in four get the smallest integer that lifts the whole
     channel above 0, the fourth the integer that clamps a share of 30 .. 70 % of it, raised until one element of EVERY distinct face is positive
-    (a batch of one face must not hold a dead channel either).
+    (a batch of one face must not hold a dead channel either); clamp_all = True: every channel takes the fourth's rule, which keeps the
+    outputs, and with them the partial sums of the next stage, about half as large.
     relu = False: a linear stage (a downsample), integer bias from [-3, 3]."""
     cout = shape[0]
     sd[conv + '.weight'] = rng.choice(np.asarray(wset, np.float32), size=shape)
@@ -57,19 +59,19 @@ def probe_conv_bn(rng, sd, conv, bn, shape, a, stride, pad, groups, wset, gset, 
         return pre + torch.from_numpy(bias).view(1, -1, 1, 1)
     if add is not None:
         pre = pre + add
-    bias = relu_bias(rng, pre)
+    bias = relu_bias(rng, pre, clamp_all=clamp_all)
     sd[bn + '.bias'] = bias.astype(np.float32)
     return torch.relu(pre + torch.from_numpy(bias).view(1, -1, 1, 1))
 
 
-def relu_bias(rng, pre, per_face=True):
+def relu_bias(rng, pre, per_face=True, clamp_all=False):
     """integer bias [C] for a ReLU that follows pre [B,C,H,W] (see probe_conv_bn); per_face = False for a map of one pixel, where a
     channel that is positive on every face would never be clamped: one positive face is enough there"""
     cout = pre.shape[1]
     hi = pre.amax(dim=(2, 3))
     lo, hi = pre.amin(dim=(0, 2, 3)).numpy(), (hi.amin(dim=0) if per_face else hi.amax(dim=0)).numpy()      # per_face: the face whose largest element is smallest
     bias = np.floor(-lo) + 1                                                # smallest integer with lo + bias > 0
-    fourth = rng.permutation(cout)[:cout // 4]
+    fourth = rng.permutation(cout)[:cout if clamp_all else cout // 4]
     flat = np.sort(pre.permute(1, 0, 2, 3).reshape(cout, -1).numpy()[fourth], axis=1)
     cut = flat[np.arange(fourth.size), (rng.uniform(0.3, 0.7, fourth.size) * (flat.shape[1] - 1)).astype(int)]
     bias[fourth] = np.maximum(np.floor(-cut), np.floor(-hi[fourth]) + 1)
@@ -157,11 +159,16 @@ def bias_conv_pair(sd, conv, a, e):
     """a 1x1 convolution with a bias and no BatchNorm (SE's conv_reduce / conv_expand, conv_head) on [B,C]: the conv rule with s = 1,
     (n + 8) u (sum |a||w| + |b|) + sum |w| e_in"""
     w, b = t64(sd, conv + '.weight').flatten(1), t64(sd, conv + '.bias')
-    y = a @ w.t() + b
-    bound = (w.shape[1] + 8) * U * (a.abs() @ w.abs().t() + b.abs())
+    return affine_pair(w, b, b.abs(), a, e)
+
+
+def affine_pair(w, b, b_abs, a, e):
+    """a [B,K] times w [N,K] plus b: (K + 8) u (sum |a||w| + b_abs) + sum |w| e_in; b_abs = the sum of the absolute values of the terms
+    the bias is folded from (they round before they cancel)"""
+    bound = (w.shape[1] + 8) * U * (a.abs() @ w.abs().t() + b_abs)
     if e is not None:
         bound = bound + e @ w.abs().t()
-    return y, bound
+    return a @ w.t() + b, bound
 
 
 def hard_sigmoid_pair(z, e):
@@ -174,3 +181,38 @@ def gated_pair(a, e, g):
     g = g.view(g.shape[0], -1, 1, 1)
     y = a * g
     return y, (g.abs() * e if e is not None else 0.0) + U * y.abs()
+
+
+def avg_pool_pair(a, e, k, stride, pad, ceil_mode=False, count_include_pad=True):
+    """An average pool that adds its k^2 window terms in fp32 and multiplies by a reciprocal: k^2 - 1 additions, the reciprocal (1 / 9 is
+    no fp32 number) and the product are k^2 + 1 roundings, one to spare: (k^2 + 2) u avg|a| + avg(e), both averages with the pool's own
+    divisor."""
+    pool = lambda t: F.avg_pool2d(t, k, stride, pad, ceil_mode=ceil_mode, count_include_pad=count_include_pad)
+    b = (k * k + 2) * U * pool(a.abs())
+    return pool(a), b if e is None else b + pool(e)
+
+
+EXPF_ULP = 1.0          # largest error of the device's expf in ulp, as the HIP math API documents it (1 ulp = 2 u relative)
+
+
+def softmax2_pair(z0, e0, z1, e1):
+    """The two-way softmax att0 = exp(z0 - m) / (exp(z0 - m) + exp(z1 - m)), m = max(z0, z1), and att1 alike -> (att0, bound, att1, bound).
+    att0 = sigma(z0 - z1) and d sigma / dd = att0 (1 - att0) = att0 att1, so what the inputs carry and the rounding of the one
+    subtraction that is not x - x move either output by att0 att1 (e_z0 + e_z1 + u |z0 - z1|).  The operations behind it act on the
+    value relatively: the two expf 2 EXPF_ULP u each (att0 = E0 / (E0 + E1) has the sensitivities att1 and -att1 to relative changes
+    of E0 and E1, in sum below one expf's 2 EXPF_ULP u twice over: 4 EXPF_ULP u), the addition, the division and the product one u
+    each: (4 EXPF_ULP + 3) u, one u to spare.  An exponential below the normal range may be flushed: 2^-126 absolute.  First order, as
+    every rule here; the constant comes from the count and the documented EXPF_ULP, not from a measurement."""
+    a0, a1 = torch.softmax(torch.stack([z0, z1]), dim=0)
+    slope = a0 * a1 * (e0 + e1 + U * (z0 - z1).abs())
+    rel = (4 * EXPF_ULP + 4) * U
+    return a0, slope + rel * a0 + 2.0 ** -126, a1, slope + rel * a1 + 2.0 ** -126
+
+
+def separating(rng, v, e, count):
+    """`count` draws from the quarter (at least 16) of the columns of v [8,C] that separate the distinct faces best: the widest gap between sorted
+    neighbours with 2 .. 6 faces below it, over the column's largest bound e"""
+    srt = np.sort(np.asarray(v), axis=0)
+    score = (srt[2:7] - srt[1:6]).max(axis=0) / np.maximum(np.asarray(e).max(axis=0), 1e-300)
+    best = np.argsort(score)[-max(v.shape[1] // 4, min(v.shape[1], 16)):]
+    return rng.choice(best, size=count)

@@ -337,15 +337,6 @@ def probe_reference(sd, block, x, dtype=torch.float64, variant=None, gate=None):
         return y.permute(0, 2, 3, 1).contiguous().numpy(), None if g is None else g.numpy()
 
 
-def _separating(rng, v, e, count):
-    """`count` draws from the quarter (at least 16) of the columns of v [8,C] that separate the distinct faces best: the widest gap between sorted
-    neighbours with 2 .. 6 faces below it, over the column's largest bound e"""
-    srt = np.sort(np.asarray(v), axis=0)
-    score = (srt[2:7] - srt[1:6]).max(axis=0) / np.maximum(np.asarray(e).max(axis=0), 1e-300)
-    best = np.argsort(score)[-max(v.shape[1] // 4, min(v.shape[1], 16)):]
-    return rng.choice(best, size=count)
-
-
 # ---- the probe's weights ----------------------------------------------------------------------------------------------------------------
 _INT_STATE = {}
 
@@ -358,7 +349,7 @@ def make_integer_state(seed=PROBE_SEED):
     conv_reduce has weights {-2, -1, 1, 2} and the bias of a ReLU stage, conv_expand weights {+-64, +-128}; per mid channel the 8
     pre-activations z (one per distinct face) are sorted, a wide gap that leaves 2 .. 6 faces below it is taken and the integer bias
     puts its middle at 0.  That rounding may not move z across the gap, so one weight of every conv_reduce and conv_expand filter is
-    SE_DOMINANT times the others (+-1), on an input that separates the faces well (_separating).  Every z is then far outside [-3, 3] (tests/test_ghostnet_cpu.py: |z| - 3 > 100 x the fp32 bound of z), the
+    SE_DOMINANT times the others (+-1), on an input that separates the faces well (exact_probe.separating).  Every z is then far outside [-3, 3] (tests/test_ghostnet_cpu.py: |z| - 3 > 100 x the fp32 bound of z), the
     gate is exactly 0 or 1, and a channel is open on some faces and closed on the others.
     conv_head: weights {-2, -1, 1, 2}, the bias of a ReLU stage; heads: weights {-2, -1, 1, 2}, integer biases in [-8, 8]."""
     if seed in _INT_STATE:
@@ -392,10 +383,10 @@ def make_integer_state(seed=PROBE_SEED):
                 y = cbn(key + '.conv_dw', key + '.bn_dw', (mid, 1, k, k), y, 2, k // 2, mid, False)
             if se:
                 m, em = ep.mean_pair(*_stage_bound_to(sd, i, x))
-                red = biased(key + '.se.conv_reduce', (se, mid, 1, 1), m, (-1, 1), _separating(rng, m, em, se))
+                red = biased(key + '.se.conv_reduce', (se, mid, 1, 1), m, (-1, 1), ep.separating(rng, m, em, se))
                 _, er = ep.bias_conv_pair(sd, key + '.se.conv_reduce', m, em)
                 we = rng.choice(np.asarray((-1, 1), np.float32), size=(mid, se, 1, 1))
-                we[np.arange(mid), _separating(rng, red, er, mid)] *= SE_DOMINANT
+                we[np.arange(mid), ep.separating(rng, red, er, mid)] *= SE_DOMINANT
                 sd[key + '.se.conv_expand.weight'] = we
                 sd[key + '.se.conv_expand.bias'] = np.zeros(mid, np.float32)
                 z, ez = (t.numpy() for t in ep.bias_conv_pair(sd, key + '.se.conv_expand', red, er))      # [8, mid]
