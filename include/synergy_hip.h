@@ -669,6 +669,42 @@ int syn_synergy_losses_backward_weights(syn_handle *h, const float *param /*[B 6
  * SYN_ERR_NOT_LOADED unless syn_load_synergy ran once on this handle (the buffers and offsets come from that call). */
 int syn_update_synergy_device(syn_handle *h, const float *flat_dev /*[n] device*/, size_t n, void *stream);
 
+/* ---- the loss head's forward under BatchNorm BATCH statistics: the reference in train() (main_train.py:113) ---- */
+
+/* BatchNorm channels of the two MLPs: 3649 = 2243 (forwardDirection.bn1..bn9) + 1406 (reverseDirection.bn1..bn5, bn6_1, bn6_2, bn6_3) */
+size_t syn_synergy_bn_channels(void);
+
+/* syn_synergy_losses with every BatchNorm1d of MLP_for / MLP_rev normalising by the statistics of the CURRENT batch:
+ *   y = (z - mean) rsqrt(var_biased + 1e-5) gamma + beta,  z = W x + bias,
+ * mean / var over all 68 B rows for the per-point layers (conv1..conv5 of both trunks, conv6..conv9 of MLP_for; conv6's statistics
+ * are those of the per-point half PLUS the face's per-face half) and over the B faces for the three heads of MLP_rev; the max over a
+ * face's 68 points comes after BatchNorm + ReLU.  One call is one replica of nn.DataParallel: the statistics are those of ITS faces.
+ * Outputs, loss weights, meter and the WingLoss / ParamLoss conventions are syn_synergy_losses's; the call ends in that entry's one
+ * loss launch.  W, bias, gamma, beta are the UNFOLDED tensors of the handle's flat state (syn_load_synergy / syn_update_synergy_device).
+ *   batch_stats (nullable) [2][3649]: every BatchNorm's batch mean | biased variance, BatchNorms in the FLAT layout's order
+ *   momentum in [0, 1]: running = (1 - momentum) running + momentum stat, the variance in its unbiased form n / (n - 1) (n = 68 B, or B
+ *     for the heads), written into the handle's flat state by our launch and re-folded, so that every eval() entry of this handle
+ *     (syn_refine_*, syn_landmarks_to_param, syn_synergy_losses*) sees the moved statistics from the next call on; the reference
+ *     trains with 0.1.  momentum < 0: the running statistics and every eval() entry stay untouched, bit for bit.
+ * fp32: the layer products on the exact-fp32 matrix instruction, K ascending 16 at a time; normalisation in the centred form above;
+ * the sums of z and z z in fp64 over fixed blocks of 256 rows (test knob train_rows; the heads: blocks of a sixteenth as many faces,
+ * at least 16), folded in ascending block order; no
+ * floating-point atomics: the bits are a function of the inputs, B and the block size alone, and a row's z does not depend on its
+ * position in the batch.  Stream-ordered, no host synchronisation apart from scratch growth (caveat as syn_refine_landmarks).
+ * Scratch: 593 KB per face (z of conv5 materialised: 279 KB; two layer images of 139 KB; conv2's output; the per-face vectors), i.e.
+ * 607 MB at 1024 faces; at most 4096 faces per call (2.4 GB).  It stays on the handle until syn_destroy.
+ * Refused before any launch with the outputs untouched: SYN_ERR_INVALID for B < 2 (torch: "Expected more than 1 value per channel
+ * when training"), B > 4096, NULL pointers, momentum > 1 or NaN, outputs that overlap, a backbone whose pooled feature is not 1280-d;
+ * SYN_ERR_NOT_LOADED before syn_load_synergy / syn_load_basis.  There is no backward under batch statistics yet. */
+int syn_synergy_losses_train(syn_handle *h, const float *param /*[B 62]*/, const float *target /*[B 62]*/, const float *pool /*[B 1280]*/, int B,
+                             float *scalars /*[2]*/, float *per_face /*[3][B]*/, double *meter /*nullable, as syn_synergy_losses*/,
+                             float *batch_stats /*nullable [2][3649]*/, float momentum /*0..1, negative: running statistics untouched*/,
+                             void *stream);
+
+/* The inverse of syn_update_synergy_device: the handle's flat state, with the running statistics syn_synergy_losses_train has moved,
+ * copied device to device on `stream`.  SYN_ERR_NOT_LOADED before syn_load_synergy. */
+int syn_export_synergy_flat(syn_handle *h, float *flat_dev /*[n] device*/, size_t n, void *stream);
+
 /* d_pred[e] = g slope sign(pred[e] - target[e]) / n for syn_wing_loss(pred, target): slope = omega / (epsilon + d) for d < omega and 1 for
  * d >= omega with d = |target - pred| in fp32, n = the batch-wide number of elements that took a branch (an integer count, formed on the
  * device by a first launch).  As torch differentiates the reference: d == 0 gives 0; a NaN d is not counted and receives 0, not NaN;

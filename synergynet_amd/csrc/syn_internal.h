@@ -32,7 +32,7 @@ __device__ __forceinline__ void l2_touch_done(unsigned &sink) { asm volatile("s_
 //   SYNERGY_HIP_TEST_KNOBS = "name=value,name=value,..."   (integers; 0x.. hexadecimal accepted)
 // read once per process (synergy_abi.hip); rounds 2-5 had 18 separate SYN_* variables.  Names: lb_chain, lb4_chain, small_f7, head_sliced_in,
 // head_wide_min, f16_pair56, rm_pair56, rm_pair34, rm_band2, rm_band3, stem_band, ablate_stem, recon_no_pk, recon_pk_wpg, recon_wgs, recon_prof,
-// lt_stage, lt_glds, resnet_exact_mask, wgrad_pass, wgrad_chunk.
+// lt_stage, lt_glds, resnet_exact_mask, wgrad_pass, wgrad_chunk, train_rows.
 long long test_knob(const char *name, long long dflt);
 bool test_knob_set(const char *name);
 
@@ -542,5 +542,26 @@ void launch_syn_fold_device(const float *flat, float *blob, const SynFoldTable &
 void launch_head_backward_phase(int phase, const HeadBwdArgs &a, int b0, int faces, hipStream_t s);
 // out[b][k] = sum_n G[b][n] W[n][k], W [N][K] row-major with N % 16 == 0 and K % 32 == 0: one wave per 16 faces x 32 outputs
 void launch_face_tgemm(const float *G, int ldg, const float *W, int ldw, int N, float *out, int ldo, int K, int B, hipStream_t s);
+
+// ---- the loss head's forward under BatchNorm batch statistics (loss_train_kernels.hip) ----
+constexpr int kSynBnChannels = 2243 + 1406;  // MLP_for bn1 .. bn9 | MLP_rev bn1 .. bn5, bn6_1 .. bn6_3, the FLAT layout's order
+constexpr int kTrainRows = 256;             // default rows per block of the statistics' partial sums (test knob train_rows, >= 16)
+constexpr int kTrainMaxFaces = 4096;        // the largest batch syn_synergy_losses_train accepts (2.4 GB of scratch)
+struct SynTrainArgs {
+    const float *Wt[2][5];                   // the trunks' packed RAW weights of syn_load_synergy (conv1: [64][4])
+    const float *W6p, *W6f, *W7, *W8, *W9, *Wrev;
+    float *flat;                             // the unfolded state: bias, gamma, beta are read, the running statistics written when momentum >= 0
+    const float *Lc, *pool, *param;          // crop-space landmarks of param [B,3,68]; the head's inputs
+    float *Lr, *S2;                          // out: refined landmarks [B,3,68], MLP_rev's parameters [B,62]
+    float *scratch;                          // train_scratch_floats(B) floats
+    double *part;                            // train_part_doubles(B, rows) doubles
+    float *batch_stats;                      // nullable [2][kSynBnChannels]
+    float momentum;
+    int B, rows;
+};
+size_t train_scratch_floats(int B);
+size_t train_part_doubles(int B, int rows);
+// MLP_for on Lc and MLP_rev on its result, layer by layer, every BatchNorm by the statistics of the batch
+void launch_synergy_train_head(const SynTrainArgs &a, hipStream_t s);
 
 }  // namespace syn

@@ -4673,6 +4673,7 @@ int syn_synergy_losses_backward_weights(syn_handle *h, const float *param, const
 // Replaces the handle's MLP weights from a flat state on the device: a copy into the handle's flat image, then one launch that folds
 // (fp64, one rounding, as fold_mlp) and repacks into the buffers and at the offsets syn_load_synergy set up.  Stream-ordered, no host
 // synchronisation.
+static syn::SynFoldTable synergy_fold_table(const syn_handle *h);
 int syn_update_synergy_device(syn_handle *h, const float *flat_dev, size_t n, void *stream) {
     if (!h || !flat_dev) return fail(SYN_ERR_INVALID, "syn_update_synergy_device: NULL argument");
     if (n != synergy_flat_count()) return fail(SYN_ERR_INVALID, "syn_update_synergy_device: %zu floats, expected %zu", n, synergy_flat_count());
@@ -4680,6 +4681,13 @@ int syn_update_synergy_device(syn_handle *h, const float *flat_dev, size_t n, vo
     DeviceGuard guard(h->device);
     hipStream_t s = (hipStream_t)stream;
     if (flat_dev != h->d_syn_flat) HIP_TRY(hipMemcpyAsync(h->d_syn_flat, flat_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    syn::launch_syn_fold_device(h->d_syn_flat, h->d_syn, synergy_fold_table(h), s);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
+// where the fold launch puts each layer of the flat state: the buffers and offsets syn_load_synergy set up
+static syn::SynFoldTable synergy_fold_table(const syn_handle *h) {
     const SynOffsets &o = h->syn_off;
     syn::SynFoldTable t;
     auto set = [&t](int i, size_t W, int ld, size_t sc, size_t sh) { t.L[i] = {W, 0, sc, sh, ld, 0, syn::syn_flat_layer(i).K}; };
@@ -4694,7 +4702,72 @@ int syn_update_synergy_device(syn_handle *h, const float *flat_dev, size_t n, vo
         set(i, o.Wrev + (size_t)row * 1024, 1024, o.scale_rev + row, o.shift_rev + row);
         row += syn::syn_flat_layer(i).N;
     }
-    syn::launch_syn_fold_device(h->d_syn_flat, h->d_syn, t, s);
+    return t;
+}
+
+size_t syn_synergy_bn_channels(void) { return (size_t)syn::kSynBnChannels; }
+
+// The inverse of syn_update_synergy_device: the handle's flat state (with the running statistics syn_synergy_losses_train moved) copied
+// device to device, stream-ordered.
+int syn_export_synergy_flat(syn_handle *h, float *flat_dev, size_t n, void *stream) {
+    if (!h || !flat_dev) return fail(SYN_ERR_INVALID, "syn_export_synergy_flat: NULL argument");
+    if (n != synergy_flat_count()) return fail(SYN_ERR_INVALID, "syn_export_synergy_flat: %zu floats, expected %zu", n, synergy_flat_count());
+    if (!h->d_syn || !h->d_syn_flat) return fail(SYN_ERR_NOT_LOADED, "syn_export_synergy_flat: synergy weights not loaded (syn_load_synergy)");
+    DeviceGuard guard(h->device);
+    HIP_TRY(hipMemcpyAsync(flat_dev, h->d_syn_flat, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return SYN_OK;
+}
+
+static bool bytes_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const char *x = (const char *)a, *y = (const char *)b;
+    return a && b && x < y + nb && y < x + na;
+}
+
+// syn_synergy_losses with every BatchNorm of MLP_for / MLP_rev normalising by the statistics of the batch (the reference in train();
+// kernels: loss_train_kernels.hip).  Scratch: Lc | Lgt | Lr | S2 [B,64] | the layer images (train_scratch_floats) | the
+// blocks' partial sums | the loss launch's chunk sums.
+int syn_synergy_losses_train(syn_handle *h, const float *param, const float *target, const float *pool, int B, float *scalars, float *per_face,
+                             double *meter, float *batch_stats, float momentum, void *stream) {
+    if (!h || !param || !target || !pool || !scalars || !per_face) return fail(SYN_ERR_INVALID, "syn_synergy_losses_train: NULL argument");
+    if (B < 2)
+        return fail(SYN_ERR_INVALID, "syn_synergy_losses_train: B=%d: Expected more than 1 value per channel when training, got input size [%d, 12, 1]",
+                    B, B);
+    if (B > syn::kTrainMaxFaces) return fail(SYN_ERR_INVALID, "syn_synergy_losses_train: B=%d, at most %d faces per call", B, syn::kTrainMaxFaces);
+    if (!(momentum <= 1.f)) return fail(SYN_ERR_INVALID, "syn_synergy_losses_train: momentum=%g, expected 0..1 (or negative: running statistics untouched)", (double)momentum);
+    int rc = synergy_ready(h, "syn_synergy_losses_train");
+    if (rc != SYN_OK) return rc;
+    if (!h->d_basis) return fail(SYN_ERR_NOT_LOADED, "syn_synergy_losses_train: 3DMM basis not loaded");
+    if (h->n_lmk != syn::kSynPts) return fail(SYN_ERR_INVALID, "syn_synergy_losses_train: the landmark basis has %d points, the MLPs take %d", h->n_lmk, syn::kSynPts);
+    const size_t n_sc = 2 * sizeof(float), n_pf = (size_t)3 * B * sizeof(float), n_bs = 2 * (size_t)syn::kSynBnChannels * sizeof(float), n_mt = 8 * sizeof(double);
+    if (bytes_overlap(scalars, n_sc, per_face, n_pf) || bytes_overlap(scalars, n_sc, batch_stats, n_bs) || bytes_overlap(per_face, n_pf, batch_stats, n_bs) ||
+        bytes_overlap(meter, n_mt, scalars, n_sc) || bytes_overlap(meter, n_mt, per_face, n_pf) || bytes_overlap(meter, n_mt, batch_stats, n_bs))
+        return fail(SYN_ERR_INVALID, "syn_synergy_losses_train: the outputs overlap");
+    DeviceGuard g(h->device);
+    const long long knob = syn::test_knob("train_rows", syn::kTrainRows);
+    const int rows = knob < 16 ? 16 : knob > (1 << 20) ? (1 << 20) : (int)knob;
+    const size_t groups = syn::loss_groups(B);
+    const size_t head_floats = (3 * kSwsLc + 64) * B, train_floats = syn::train_scratch_floats(B), part_doubles = syn::train_part_doubles(B, rows);
+    rc = ensure_sws(h, (head_floats + train_floats) * sizeof(float) + (part_doubles + groups * 8) * sizeof(double));
+    if (rc != SYN_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    float *Lc = h->sws, *Lgt = Lc + kSwsLc * B, *Lr = Lgt + kSwsLc * B, *prev = Lr + kSwsLc * B;
+    syn::SynTrainArgs a = {};
+    a.scratch = prev + (size_t)64 * B;
+    a.part = (double *)(a.scratch + train_floats);
+    double *partial = a.part + part_doubles;
+    const SynOffsets &o = h->syn_off;
+    const float *d = h->d_syn;
+    for (int which = 0; which < 2; ++which)
+        for (int i = 0; i < 5; ++i) a.Wt[which][i] = d + o.tW[which][i];
+    a.W6p = d + o.W6p; a.W6f = d + o.W6f; a.W7 = d + o.W7; a.W8 = d + o.W8; a.W9 = d + o.W9; a.Wrev = d + o.Wrev;
+    a.flat = h->d_syn_flat;
+    a.Lc = Lc; a.pool = pool; a.param = param; a.Lr = Lr; a.S2 = prev;
+    a.batch_stats = batch_stats; a.momentum = momentum; a.B = B; a.rows = rows;
+    syn::launch_lmk_pose(param, basis_mean(h), basis_std(h), basis_lmk(h), h->n_lmk, h->nlp, nullptr, 1, Lc, nullptr, nullptr, B, s);
+    syn::launch_lmk_pose(target, basis_mean(h), basis_std(h), basis_lmk(h), h->n_lmk, h->nlp, nullptr, 1, Lgt, nullptr, nullptr, B, s);
+    syn::launch_synergy_train_head(a, s);
+    syn::launch_synergy_losses(param, target, Lc, Lgt, Lr, prev, B, partial, loss_counter(h), scalars, per_face, meter, s);
+    if (momentum >= 0.f) syn::launch_syn_fold_device(h->d_syn_flat, h->d_syn, synergy_fold_table(h), s);      // every eval() entry sees the moved statistics
     HIP_TRY(hipGetLastError());
     return SYN_OK;
 }

@@ -633,7 +633,8 @@ class SynergyNet(nn.Module):
         abi.check(self._lib.syn_load_synergy(self._h, flat.ctypes.data_as(C.c_void_p), flat.size))
         self.has_synergy = True
         self._syn_flat = flat
-        if self._syn_params is not None:                      # the parameters follow the new state; the handle already holds it
+        self._syn_flat_stale = False
+        if self._syn_params is not None:                     # the parameters follow the new state; the handle already holds it
             with torch.no_grad():
                 for k, t in self._syn_tensors.items():
                     at, n, shape = self._syn_where[k]
@@ -653,7 +654,7 @@ class SynergyNet(nn.Module):
             for key, shape in synergy_layers():
                 n = int(np.prod(shape))
                 self._syn_where[key] = (at, n, shape)
-                t = torch.from_numpy(self._syn_flat[at:at + n].reshape(shape).copy()).to(self.device)
+                t = torch.from_numpy(self._host_flat()[at:at + n].reshape(shape).copy()).to(self.device)
                 self._syn_tensors[key] = t if 'running_' in key else nn.Parameter(t)
                 at += n
             self._syn_params = {k: t for k, t in self._syn_tensors.items() if isinstance(t, nn.Parameter)}
@@ -673,16 +674,44 @@ class SynergyNet(nn.Module):
             abi.check(self._lib.syn_update_synergy_device(self._h, flat.data_ptr(), flat.numel(), self._stream()))
         self._syn_uploaded = self._syn_versions()
 
+    def _export_synergy_flat(self):
+        """the handle's flat state as one device tensor (syn_export_synergy_flat: a copy, no arithmetic)"""
+        with torch.cuda.device(self.device):
+            flat = torch.empty((int(self._lib.syn_synergy_flat_count()),), dtype=torch.float32, device=self.device)
+            abi.check(self._lib.syn_export_synergy_flat(self._h, flat.data_ptr(), flat.numel(), self._stream()))
+        return flat
+
+    def _running_moved(self):
+        """after a call that moved the running statistics on the handle (loss_head(bn='batch')): the running_* tensors behind
+        synergy_parameters() take them over, and the host copy is marked stale"""
+        self._syn_flat_stale = True
+        if self._syn_params is not None:
+            flat = self._export_synergy_flat()
+            with torch.no_grad():
+                for k, t in self._syn_tensors.items():
+                    if 'running_' in k:
+                        at, n, shape = self._syn_where[k]
+                        t.copy_(flat[at:at + n].reshape(shape))
+            self._syn_uploaded = self._syn_versions()        # the handle already holds them: nothing stale goes up
+
+    def _host_flat(self):
+        if getattr(self, '_syn_flat_stale', False):
+            self._syn_flat = self._export_synergy_flat().cpu().numpy()
+            self._syn_flat_stale = False
+        return self._syn_flat
+
     def synergy_state_dict(self):
-        """the current flat state as {key: tensor} with the reference's key names (load_synergy_state takes it back)"""
+        """the current flat state as {key: tensor} with the reference's key names (load_synergy_state takes it back); after
+        loss_head(bn='batch') / recalibrate_synergy_bn the running statistics are the moved ones"""
         self._need_synergy()
         if self._syn_params is not None:
             return {k: t.detach().clone() for k, t in self._syn_tensors.items()}
         from .synth import synergy_layers
+        flat = self._host_flat()
         out, at = {}, 0
         for key, shape in synergy_layers():
             n = int(np.prod(shape))
-            out[key] = torch.from_numpy(self._syn_flat[at:at + n].reshape(shape).copy()).to(self.device)
+            out[key] = torch.from_numpy(flat[at:at + n].reshape(shape).copy()).to(self.device)
             at += n
         return out
 
@@ -1039,13 +1068,57 @@ class SynergyNet(nn.Module):
             raise RuntimeError('param, pool and target must hold the same number of faces (at least one)')
         return p, po, t
 
-    def loss_head(self, param, pool, target):
+    def _losses_train(self, param, pool, target, momentum=0.1, meter=None, batch_stats=None):
+        """syn_synergy_losses_train: the dict of `_losses` with every BatchNorm of the two MLPs on the statistics of this
+        batch; momentum None leaves the running statistics alone.  batch_stats: optional float32 [2, 3649] device tensor to fill."""
+        t = self._check_faces('target', target, (62,))
+        B = param.shape[0]
+        if t.shape[0] != B:
+            raise RuntimeError(f'target must be [{B},62] (one row per face of the input), got {tuple(t.shape)}')
+        if B < 2:
+            raise RuntimeError(f"bn='batch': Expected more than 1 value per channel when training, got input size [{B}, 12, 1]")
+        if momentum is not None and not 0.0 <= float(momentum) <= 1.0:
+            raise RuntimeError(f'momentum must be None (running statistics untouched) or in [0, 1], got {momentum}')
+        if meter is not None and not (isinstance(meter, torch.Tensor) and meter.dtype == torch.float64 and tuple(meter.shape) == (8,)
+                                      and meter.device == self.device and meter.is_contiguous()):
+            raise RuntimeError(f'meter must be a contiguous float64 [8] tensor on {self.device}')
+        n_bn = int(self._lib.syn_synergy_bn_channels())
+        if batch_stats is not None and not (isinstance(batch_stats, torch.Tensor) and batch_stats.dtype == torch.float32
+                                            and tuple(batch_stats.shape) == (2, n_bn) and batch_stats.device == self.device
+                                            and batch_stats.is_contiguous()):
+            raise RuntimeError(f'batch_stats must be a contiguous float32 [2,{n_bn}] tensor on {self.device}')
+        with torch.cuda.device(self.device):
+            scalars = torch.empty((2,), dtype=torch.float32, device=self.device)
+            per_face = torch.empty((3, B), dtype=torch.float32, device=self.device)
+            abi.check(self._lib.syn_synergy_losses_train(self._h, param.data_ptr(), t.data_ptr(), pool.data_ptr(), B, scalars.data_ptr(),
+                                                         per_face.data_ptr(), meter.data_ptr() if meter is not None else None,
+                                                         batch_stats.data_ptr() if batch_stats is not None else None,
+                                                         -1.0 if momentum is None else float(momentum), self._stream()))
+        if momentum is not None:
+            self._running_moved()
+        return dict(zip(LOSS_NAMES, (scalars[0], scalars[1], per_face[0], per_face[1], per_face[2])))
+
+    def _no_backward_under_batch_statistics(self, *tensors):
+        ws = self._syn_params.values() if self._syn_params is not None else ()
+        if torch.is_grad_enabled() and any(isinstance(x, torch.Tensor) and x.requires_grad for x in (*tensors, *ws)):
+            raise RuntimeError("bn='batch': there is no backward under BatchNorm batch statistics yet (forward only); call it under "
+                               "torch.no_grad() or on tensors that do not require grad -- the eval() gradients are never handed out for it")
+
+    def loss_head(self, param, pool, target, bn='running', momentum=0.1):
         """The loss head behind any backbone: whitened param [B,62], pooled feature [B,1280], whitened target [B,62] -> the reference's
         dict of the five weighted losses (keys, order and values of `forward`).  If param or pool requires grad the tensors carry a
         grad_fn whose backward is syn_synergy_losses_backward (the head in eval() form); target gets no gradient.
         If a tensor of `synergy_parameters()` requires grad, the backward is syn_synergy_losses_backward_weights and also returns
-        their gradients; parameters an optimiser changed are uploaded before the forward."""
+        their gradients; parameters an optimiser changed are uploaded before the forward.
+        bn='batch' (DESIGN 5.21): the reference in train() -- every BatchNorm of MLP_for / MLP_rev normalises by the statistics of this
+        batch (B >= 2) and the running statistics move by `momentum` (None: untouched); forward only: anything that requires grad
+        raises.  The switch is this keyword, never self.training."""
+        if bn not in ('running', 'batch'):
+            raise RuntimeError(f"bn must be 'running' or 'batch', got {bn!r}")
         p, po, t = self._head_inputs(param, pool, target)
+        if bn == 'batch':
+            self._no_backward_under_batch_statistics(p, po)
+            return self._losses_train(p, po, t, momentum)
         ws = self._syn_params
         if torch.is_grad_enabled() and ws is not None and any(w.requires_grad for w in ws.values()):
             return dict(zip(LOSS_NAMES, _LossHeadWeightsFn.apply(self, p, po, t.detach(), *ws.values())))
@@ -1058,13 +1131,34 @@ class SynergyNet(nn.Module):
         p, po, t = self._head_inputs(param, pool, target)
         return self._losses_backward(p.detach(), po.detach(), t.detach())
 
-    def forward(self, input, target, meter=None):
+    def forward(self, input, target, meter=None, bn='running', momentum=0.1):
         """reference model_building.py:141-157: [B,3,120,120] crops (whatever forward_test takes) and the whitened [B,62] target -> the
         dict of the five weighted losses, device tensors: the two landmark losses 0-d, the three parameter losses [B].  Forward only.
-        meter: a zeroed float64 [8] device tensor the batch is added to (include/synergy_hip.h syn_synergy_losses; `validate`)."""
+        meter: a zeroed float64 [8] device tensor the batch is added to (include/synergy_hip.h syn_synergy_losses; `validate`).
+        bn='batch': the two MLPs on the statistics of this batch, as `loss_head` (the backbone stays in eval() form)."""
+        if bn not in ('running', 'batch'):
+            raise RuntimeError(f"bn must be 'running' or 'batch', got {bn!r}")
         self._need_synergy()
+        if bn == 'batch':
+            self._no_backward_under_batch_statistics(input)
         param, pool = self.forward_test(self._dev_f32(input), return_pool=True)
+        if bn == 'batch':
+            return self._losses_train(param, pool, target, momentum, meter)
         return self._losses(param, pool, target, meter)
+
+    def recalibrate_synergy_bn(self, batches):
+        """Re-estimates the running statistics of MLP_for / MLP_rev for the weights as they stand (after a fine-tuning run with frozen
+        statistics, before synergy_state_dict() is saved): batch k of the iterable of (param, pool, target) runs `loss_head(bn='batch')`
+        with momentum 1 / k -- torch's momentum=None cumulative average --, so that afterwards the running statistics are the mean of
+        the batches' statistics (the variance in its unbiased form).  -> the number of batches."""
+        k = 0
+        with torch.no_grad():
+            for param, pool, target in batches:
+                k += 1
+                self.loss_head(param, pool, target, bn='batch', momentum=1.0 / k)
+        if k == 0:
+            raise RuntimeError('recalibrate_synergy_bn: no batches')
+        return k
 
     def losses_crops_u8(self, crops, target, meter=None):
         """`forward` from uint8 crops [B,120,120,3] (what forward_crops_u8 takes)"""
