@@ -10,10 +10,12 @@
 //   * the block input of the face lives in REGISTERS as pre-split B fragments (5 k32 steps x 2 pieces = 40 registers), the
 //     accumulators too: the waves walk the 30 hidden groups with no partial sums to exchange;
 //   * the WEIGHTS go through LDS: the eight waves of a workgroup (four faces) walk the groups in lockstep and share one fetch of each group's
-//     fragments + constants -- one contiguous 48 | 64 KB run of the packed blob, an eighth per wave, fetched into registers TWO groups
-//     ahead and written to the other half of a double buffer during the depthwise of the group in front (the LDS is idle there); the
-//     group's expand operands are requested from LDS while the previous group's project runs, its project fragments inside its own
-//     expand chain: no LDS phase stands between the last matrix instruction of a group and the first of the next (lb4_stage).
+//     fragments + constants -- one contiguous 48 | 64 KB run of the packed blob, an eighth per wave, loaded STRAIGHT into the other half of
+//     a double buffer (buffer loads with the lds modifier: 1 KB per wave-instruction, no staging registers, no ds_write), the expand part
+//     two groups ahead, the project part one, issued between the matrix instructions of the expand chain and published by counted
+//     s_waitcnt vmcnt in front of the two barriers of a group; the group's expand operands are requested from LDS while the previous
+//     group's project runs, its project fragments inside its own expand chain: no LDS phase stands between the last matrix instruction
+//     of a group and the first of the next (lb4_stage).
 //     (Each wave fetching its own fragments would pull 1.2 MB through L2 per face.)
 //   * TWO waves per face (B = 1024 offers four faces per CU, and a lone wave per SIMD issues vector instructions at half the
 //     rate): wave (face, t) owns hidden tile t through expand and depthwise and half of the output tiles in the project; the
@@ -34,6 +36,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) void *lds_ptr_t;
 
 namespace {
 __device__ __forceinline__ void split2q(float x0, float x1, unsigned &a, unsigned &b) {
@@ -75,6 +78,10 @@ struct Lb4Cfg {
     static constexpr int WE_DW = 2 * KE * 2 * 256, WP_DW = MT * 2 * 256, TB_DW = 2 * 256;   // a group's expand | project fragments | constants (12 x 32 floats + pad)
     static constexpr int NKB = ((WE_DW + WP_DW + TB_DW) / 256 + 7) / 8 * 8;               // 1 KB pieces per group, padded to one more round of the 8 waves (lb4_group_dwords)
     static constexpr int GRP_DW = NKB * 256;
+    // the two parts a run is loaded in (lb4_dma), in 1 KB pieces: E = expand fragments + constants + two pieces of the padding (what a group
+    // STARTS from), P = project fragments + the rest of the padding (what its expand chain asks for); per wave NE | NP pieces
+    static constexpr int WEP = WE_DW / 256, WPP = WP_DW / 256, NE = (WEP + 4) / 8, NP = NKB / 8 - NE;
+    static_assert((WEP + 4) % 8 == 0 && WEP + WPP + 4 <= NKB, "E = 24 pieces: every wave issues the same number, the vmcnt counts depend on it");
     static constexpr int XCH_DW = 4 * 2 * 64 * 4;                                         // depthwise outputs exchanged between the two waves of a face
     static constexpr int LDS_DW = 2 * GRP_DW + XCH_DW;
     static_assert(CIN % 32 == 0 && HID % 32 == 0 && COUT % 32 == 0, "k32 steps, groups, two halves of the output tiles");
@@ -90,7 +97,7 @@ struct Lb4Cfg {
 // to the next stage as pre-split fragments through the weight buffer half the last group has just left, the residual of the next block
 // stays in the accumulator's registers, and the next stage's first weight group is fetched during the last group of this one --
 // no kernel boundary (10-16 us each), no global round trip of the 4x4 activations.
-struct Lb4NoNext { static constexpr int NKB = 0; };
+struct Lb4NoNext { static constexpr int NKB = 0, NE = 0, NP = 0, GRP_DW = 0, NG = 0; };
 struct Lb4StageArgs {
     const float *X;          // block input (global): a FIRST stage's input and residual
     const unsigned *Glb;     // [NG][NKB][64][4]: We | Wp | table per group
@@ -100,20 +107,32 @@ struct Lb4StageArgs {
     int g0 = 0, g1 = 0;      // hidden groups [g0, g1) of this workgroup's slice (g1 = 0: all); slice = blockIdx.y
 };
 
-template <int N>
-__device__ __forceinline__ void lb4_fetch(u32x4 *pf, const unsigned *src /* uniform */, unsigned lane16, int wave) {
-    // (a uniform base per piece + the lane's 32-bit byte offset: one address register for all pieces instead of a 64-bit pair each)
-    const unsigned long long a = reinterpret_cast<unsigned long long>(src + wave * 256);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    const char *base = reinterpret_cast<const char *>(((unsigned long long)hi << 32) | lo);
-#pragma unroll
-    for (int i = 0; i < N; ++i) pf[i] = *(const u32x4 *)(base + i * 8192 + lane16);
+// Piece I of this wave's share of part E | P of a group run (configuration C): global -> LDS with no register in between.  rs: the stage's
+// blob; grp: byte offset of the group's run in it (uniform); half: where the run goes.  The LDS image is the run itself (lane-linear pieces).
+// The padding pieces are loaded like the others so that EVERY wave has the same number of loads in flight.
+// Nothing orders a ds_read behind such a load but the issuing wave's s_waitcnt vmcnt AND a barrier behind it (lb4_wait_vm, lb4_barrier).
+template <class C, bool PPART, int I>
+__device__ __forceinline__ void lb4_dma(__amdgpu_buffer_rsrc_t rs, unsigned grp, unsigned *half, unsigned lane16, int wave /* uniform */) {
+    const int slot = wave + 8 * I;
+    const int piece = PPART ? (slot < C::WPP ? C::WEP + slot : slot + C::WEP + 4) : (slot < C::WEP ? slot : slot + C::WPP);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(half + piece * 256), 16, lane16, grp + piece * 1024, 0, 0);
 }
-template <int N>
-__device__ __forceinline__ void lb4_park(const u32x4 *pf, unsigned *dst /* + 4 lane */, int wave) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) *(u32x4 *)&dst[(wave + 8 * i) * 256] = pf[i];
+template <class C, bool PPART, int I0, int I1>
+__device__ __forceinline__ void lb4_dma_range(__amdgpu_buffer_rsrc_t rs, unsigned grp, unsigned *half, unsigned lane16, int wave) {
+    if constexpr (I0 < I1) {
+        lb4_dma<C, PPART, I0>(rs, grp, half, lane16, wave);
+        lb4_dma_range<C, PPART, I0 + 1, I1>(rs, grp, half, lane16, wave);
+    }
 }
+template <class C>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t lb4_rsrc(const unsigned *Glb) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned *>(Glb), 0, C::NG * C::GRP_DW * 4, 0x00027000);
+}
+// all but the N youngest loads of this wave have landed (they return in order)
+template <int N>
+__device__ __forceinline__ void lb4_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// workgroup barrier that leaves the loads in flight (__syncthreads() would drain them): this wave's LDS reads and writes are done, nothing else
+__device__ __forceinline__ void lb4_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // What a group's expand chain and depthwise start from, read from LDS one group AHEAD (during the previous group's project): the accumulator's
 // start value, this wave's expand fragments, and rows 0-8 (filter taps) and 9 (BN shift) of the group's table for channels 16 t + 4 g .. + 3.
@@ -145,18 +164,25 @@ template <int N> struct Lb4Int { static constexpr int value = N; };
 // stores its raw accumulators; lb4_reduce_kernel adds the slices in fixed order, rescales, adds BN shift and residual.  A batch of 128
 // faces is then 32 x 6 workgroups of five groups each instead of 32 workgroups walking all thirty.
 //
-// The weight pipeline, per group G (two LDS halves, `pf` = one group in registers, `pre` = the next group's expand operands):
-//   top barrier          every wave is done with group G-1: its half may be rewritten
-//   expand chain         from `pre` (requested during G-1's project); behind each k32 step one output tile's project fragments are requested
-//   PARK G+1             pf -> the half G-1 has left;  FETCH G+2 -> pf (global; a whole group to land)
-//   depthwise, exchange barrier: it also publishes group G+1
+// The weight pipeline, per group G (two LDS halves; part E of a run = expand fragments + constants, part P = project fragments; `pre` = the
+// next group's expand operands in registers):
+//   top barrier          every wave is done with group G-1 and has its own reads of group G's operands back: the P part of G-1's half and the
+//                        E part of G's OWN half (read for the last time under G-1's project) may be rewritten
+//   expand chain         from `pre`; behind each k32 step one output tile's project fragments are requested from LDS and ONE piece is loaded
+//                        global -> LDS: first P of G+1 (into G-1's half), then E of G+2 (into G's half); what is left, behind the chain
+//   depthwise
+//   vmcnt(NP + NE), exchange barrier   all but this group's loads have landed: it also publishes E of G+1 (issued a group ago)
 //   PRE G+1              requested from LDS while G's project runs, into registers the project frees as it goes (PRE0 units up front,
 //                        then one per output tile from tile LAG on, the rest behind the last)
-// At the first group of a slice | FIRST stage the prologue stands in for G-1; at a stage's last group G+1 is the NEXT stage's first group,
-// which goes to half 0 (NG is even) while half 1, the hand-over buffer, is written only between its own two barriers.
-template <class C, class CN, bool FIRST, int GRPL, bool PARTIAL, int NPF, int PRE0, int LAG>
+//   vmcnt(NE)            P of G+1 has landed; the next top barrier publishes it.  E of G+2 stays in flight across it.
+// The group a stage is entered with (G = gb) finds E and P of its own run in half 0 -- from the prologue (FIRST), or loaded by the last two
+// groups of the stage in front -- and loads E of G+1 itself, in front of its chain: half 1 is the hand-over buffer between two stages, free
+// only behind this group's top barrier.  At a stage's last two groups G+1 | G+2 are the NEXT stage's first groups (NG is even: its group 0
+// goes to half 0).  Every wave issues the same number of loads per group and they return in order: the counts above hold whatever else is
+// in flight.
+template <class C, class CN, bool FIRST, int GRPL, bool PARTIAL, int PRE0, int LAG>
 __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa, const unsigned *GlbNext, int B, u32x4 (&Xr)[5][2], f32x4 (&vres)[5],
-                                          u32x4 (&pf)[NPF], Lb4Pre &pre) {
+                                          Lb4Pre &pre) {
     constexpr int KE = C::KE, MTW = C::MTW, CIN = C::CIN, COUT = C::COUT;
     constexpr bool HANDOFF = !__is_same(CN, void);
     static_assert(KE == 5 && C::NG % 2 == 0, "160 input channels; the double buffer's parity carries over to the next stage");
@@ -173,17 +199,16 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
     const unsigned l4 = lane * 4, g4 = g * 4, l16 = lane * 16;
     unsigned *Xch = smem + 2 * GRPL;
 
-    // every wave copies every eighth 1 KB piece of a group's run through registers: fetched two groups ahead, written to the other half
-    // of the double buffer during the depthwise of the group in front.  (LDS-DMA -- global_load_lds_dwordx4, no registers -- delivers
-    // ~25 GB/s per CU whoever issues it: 44 KB per group took 1.8 us, longer than the group's arithmetic.)
-    constexpr int NPW = C::NKB / 8;
+    // every wave loads every eighth 1 KB piece of a part of a group's run straight into LDS (lb4_dma).  Measured with tools/ubench/lds_dma_stream.hip
+    // (eight waves per CU, every CU, one shared 4.3 MB blob): 54 GB/s per CU with one piece in flight per wave, 110 with four, 115 with six or
+    // eight -- four times what this kernel asks for (4.3 MB per CU in ~150 us = 29 GB/s).  (Round 2 read "25 GB/s per CU" off its own pace.)
     using CNX = typename std::conditional<HANDOFF, CN, Lb4NoNext>::type;
-    constexpr int NPWN = CNX::NKB / 8;
-    static_assert(NPF >= NPW && NPF >= NPWN, "pf holds a group of this stage or of the next");
+    const __amdgpu_buffer_rsrc_t rs = lb4_rsrc<C>(Glb), rsn = lb4_rsrc<CNX>(HANDOFF ? GlbNext : Glb);
     const int gsl = PARTIAL ? (sa.g1 - sa.g0) : C::NG;   // groups per slice (all slices the same)
     const int gb = PARTIAL ? (int)blockIdx.y * gsl : 0, ge = gb + gsl;
     if (FIRST) {
-        lb4_fetch<NPW>(pf, Glb + (size_t)gb * C::GRP_DW, l16, wave);
+        lb4_dma_range<C, false, 0, C::NE>(rs, (unsigned)gb * (C::GRP_DW * 4), smem, l16, wave);
+        lb4_dma_range<C, true, 0, C::NP>(rs, (unsigned)gb * (C::GRP_DW * 4), smem, l16, wave);
         // ---- block input of this face -> pre-split B fragments in registers (x 16; both waves of the face hold it) ----
         f32x4 xv[KE][2];
 #pragma unroll
@@ -208,9 +233,8 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
     for (int i = 0; i < MTW; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float c6e = 0.f, inv_p = 0.f;
     if (FIRST) {
-        lb4_park<NPW>(pf, smem + l4, wave);
-        if (!PARTIAL || gsl >= 2) lb4_fetch<NPW>(pf, Glb + (size_t)(gb + 1) * C::GRP_DW, l16, wave);     // (a slice of ONE group: nothing further to fetch)
-        __syncthreads();                                 // group gb is in half 0: its expand operands, which every later group finds requested by the group in front
+        lb4_wait_vm<0>();
+        lb4_barrier();                                   // group gb is in half 0: its expand operands, which every later group finds requested by the group in front
 #pragma unroll
         for (int u = 0; u < kLb4PreUnits; ++u) lb4_pre_unit<C>(pre, smem, u, t, l4, g4);
     }
@@ -219,15 +243,43 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
         const float *t0 = reinterpret_cast<const float *>(Glb + C::WE_DW + C::WP_DW);
         c6e = t0[11 * 32]; inv_p = t0[11 * 32 + 1];
     }
-    // One group.  NF pieces per wave of the group after next are fetched from `fsrc`, NP pieces of the next group parked, and the
-    // next group's expand operands requested in configuration CP (void: there is no next group): compile-time, so that the loop body holds no branch.
-    auto group = [&](auto nf_, auto np_, auto cp_, int G, const unsigned *fsrc) __attribute__((always_inline)) {
-        constexpr int NF = decltype(nf_)::value, NP = decltype(np_)::value;
+    // One group.  Part P of the next group (configuration CP, blob rs1 at byte off1; void: there is no next group) and part E of the group after
+    // next (C2, rs2, off2) are loaded, and the next group's expand operands requested in configuration CP: compile-time, so that every wave
+    // issues a known number of loads.  The one uniform branch: the group a stage is entered with loads part E of its successor as well.
+    auto group = [&](auto cp_, auto c2_, int G, __amdgpu_buffer_rsrc_t rs1, unsigned off1, __amdgpu_buffer_rsrc_t rs2, unsigned off2) __attribute__((always_inline)) {
         using CP = typename decltype(cp_)::type;
-        constexpr bool HASNEXT = !__is_same(CP, void);
-        __syncthreads();                                 // every wave is done with group G-1 (and has its own reads of group G's operands back)
-        const unsigned *We = smem + ((G - gb) & 1) * GRPL, *Wp = We + C::WE_DW;
+        using C2 = typename decltype(c2_)::type;
+        constexpr bool HASNEXT = !__is_same(CP, void), HAS2 = !__is_same(C2, void);
+        using CPX = typename std::conditional<HASNEXT, CP, Lb4NoNext>::type;
+        using C2X = typename std::conditional<HAS2, C2, Lb4NoNext>::type;
+        constexpr int NP1 = CPX::NP, NE2 = C2X::NE;
+        static_assert(NP1 + NE2 <= 8, "dma_at");
+        lb4_barrier();                                   // every wave is done with group G-1 (and has its own reads of group G's operands back)
+        unsigned *Wg = smem + ((G - gb) & 1) * GRPL;       // the half of group G, whose E part is free from here on: then of group G+2
+        const unsigned *Wp = Wg + C::WE_DW;
         unsigned *Wn = smem + ((G + 1 - gb) & 1) * GRPL;   // the half of group G-1, then of group G+1
+        if constexpr (HASNEXT) {
+            if (G == gb) lb4_dma_range<CPX, false, 0, CPX::NE>(rs1, off1, Wn, l16, wave);
+        }
+        // load j of this group: P of G+1 first (needed at the next top barrier), then E of G+2 (needed at the exchange barrier behind that)
+        auto dma_j = [&](auto j_) __attribute__((always_inline)) {
+            constexpr int J = decltype(j_)::value;
+            if constexpr (J < NP1) lb4_dma<CPX, true, J>(rs1, off1, Wn, l16, wave);
+            else if constexpr (J < NP1 + NE2) lb4_dma<C2X, false, J - NP1>(rs2, off2, Wg, l16, wave);
+        };
+        auto dma_at = [&](int j) __attribute__((always_inline)) {
+            switch (j) {
+                case 0: dma_j(Lb4Int<0>{}); break;
+                case 1: dma_j(Lb4Int<1>{}); break;
+                case 2: dma_j(Lb4Int<2>{}); break;
+                case 3: dma_j(Lb4Int<3>{}); break;
+                case 4: dma_j(Lb4Int<4>{}); break;
+                case 5: dma_j(Lb4Int<5>{}); break;
+                case 6: dma_j(Lb4Int<6>{}); break;
+                case 7: dma_j(Lb4Int<7>{}); break;
+                default: break;
+            }
+        };
         // Round 5: the eight waves read 22 KB each at this point, the LDS delivers 128 bytes per cycle, and the expand chain used to wait for ALL
         // of it: ~1400 cycles per group in which nothing else ran; then only the expand fragments stood in front of the chain.  Round 7: those
         // were requested during the previous group's project, so the chain starts here, and each k32 step of it is followed by the request of one
@@ -245,13 +297,11 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int p = 0; p < 2; ++p) Ap[kc][p] = *(const u32x4 *)&Wp[((t * MTW + kc) * 2 + p) * 256 + l4];
+            dma_at(kc);                                  // (memory instructions are issued in front of the matrix instructions that cover them, one at a time)
             __builtin_amdgcn_sched_barrier(0);
         }
-        // the next group's weights: registers -> the half group G-1 has left (the top barrier above), behind the project fragments in the LDS queue;
-        // the group after next: global -> the same registers, with a whole group to land
-        if (NP) lb4_park<NP>(pf, Wn + l4, wave);
-        __builtin_amdgcn_sched_barrier(0);               // (the fetch behind the park, into the registers it has just read: not in front of it into others)
-        if (NF) lb4_fetch<NF>(pf, fsrc, l16, wave);
+#pragma unroll
+        for (int j = KE; j < NP1 + NE2; ++j) dma_at(j);
         __builtin_amdgcn_sched_barrier(0);
         // ---- ReLU6, depthwise 3x3 + BN shift + ReLU6 on the registers, split into this wave's half of the project operand ----
         u32x4 own;                                      // {piece 0 dwords hf 0, 1 | piece 1 dwords hf 0, 1}
@@ -289,7 +339,8 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
         }
         // ---- the partner's half: K slots 0-3 of a lane group are tile 0's channels, 4-7 tile 1's ----
         *(u32x4 *)&Xch[((fl * 2 + t) * 64 + lane) * 4] = own;
-        __syncthreads();                                 // the exchange; every wave's pieces of group G+1 are in LDS too
+        lb4_wait_vm<NP1 + NE2>();                        // this wave's pieces of part E of group G+1 (loaded a group ago, or in front of this chain) have landed
+        lb4_barrier();                                   // the exchange; every wave's pieces of them are in LDS too
         const u32x4 oth = *(const u32x4 *)&Xch[((fl * 2 + (1 - t)) * 64 + lane) * 4];
 #pragma unroll
         for (int i = MTW0; i < MTW; ++i)
@@ -316,12 +367,14 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
             acc[i] = mfmaq(Ap[i][0], Bd[0], acc[i]);
             if constexpr (HASNEXT) __builtin_amdgcn_sched_barrier(0);
         }
+        lb4_wait_vm<NE2>();                              // this wave's pieces of part P of group G+1 have landed: the next top barrier publishes them
     };
-    // the last two groups of the stage fetch | park the next stage's first two groups (NPWN pieces; none without a next stage)
+    // the last two groups of the stage load the next stage's first group (none without a next stage)
+    constexpr unsigned GB = C::GRP_DW * 4;
     for (int G = gb; G < ge - 2; ++G)
-        group(Lb4Int<NPW>{}, Lb4Int<NPW>{}, Lb4Tag<C>{}, G, Glb + (size_t)(G + 2) * C::GRP_DW);
-    if (!PARTIAL || gsl >= 2) group(Lb4Int<NPWN>{}, Lb4Int<NPW>{}, Lb4Tag<C>{}, ge - 2, GlbNext);
-    group(Lb4Int<NPWN>{}, Lb4Int<NPWN>{}, Lb4Tag<CN>{}, ge - 1, HANDOFF ? GlbNext + CNX::NKB * 256 : nullptr);
+        group(Lb4Tag<C>{}, Lb4Tag<C>{}, G, rs, (unsigned)(G + 1) * GB, rs, (unsigned)(G + 2) * GB);
+    if (!PARTIAL || gsl >= 2) group(Lb4Tag<C>{}, Lb4Tag<CN>{}, ge - 2, rs, (unsigned)(ge - 1) * GB, rsn, 0u);
+    group(Lb4Tag<CN>{}, Lb4Tag<void>{}, ge - 1, rsn, 0u, rsn, 0u);
     if constexpr (PARTIAL) {                             // raw accumulators of this slice -> [slice][B][16][COUT]
         if (real) {
 #pragma unroll
@@ -348,8 +401,8 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
     }
     if constexpr (HANDOFF) {
         static_assert(CN::CIN == COUT && MTW == 5, "the next block takes this block's output: five output tiles per wave");
-        unsigned *HO = smem + GRPL;                      // half 1: the last group's weights, no longer read once every wave is here
-        __syncthreads();
+        unsigned *HO = smem + GRPL;                      // half 1: the last group's weights, no longer read once every wave is here (no load is in flight: vmcnt(0) above)
+        lb4_barrier();
 #pragma unroll
         for (int i = 0; i < MTW; ++i) {
             vres[i] = vout[i];
@@ -362,28 +415,31 @@ __device__ __forceinline__ void lb4_stage(unsigned *smem, const Lb4StageArgs &sa
             *(u32x2 *)&HO[((fl * KE + kc) * 2 + 0) * 256 + lt * 4 + dw] = (u32x2){a0, a1};
             *(u32x2 *)&HO[((fl * KE + kc) * 2 + 1) * 256 + lt * 4 + dw] = (u32x2){b0, b1};
         }
-        __syncthreads();
+        lb4_barrier();
 #pragma unroll
         for (int kc = 0; kc < KE; ++kc)
 #pragma unroll
             for (int p = 0; p < 2; ++p) Xr[kc][p] = *(const u32x4 *)&HO[((fl * KE + kc) * 2 + p) * 256 + l4];
-        // (half 1 is rewritten during the next block's first group, behind that group's top barrier: every wave has these reads back by then)
+        // (half 1 is loaded into during the next block's first group, behind that group's top barrier: every wave has these reads back by then)
     }
 }
 
 // units of the next group's expand operands requested in front of the project's first matrix instruction (the rest: one per output tile)
-// (the most that compiles without a spill: the single 160-channel block takes all ten, the chain's 160-channel stages, which also hold the
-// residual and a 64 KB group in flight, four; the 320-channel stage starts behind its second output tile -- each tile frees eight registers)
+// (round 7 took the most that compiled without a spill beside the 24-32 staging registers of the weight copy: the single 160-channel block all
+// ten, the chain's 160-channel stages four; the 320-channel stage starts behind its second output tile -- each tile frees eight registers.
+// Round 8, with those registers free: the chain at 0 / 2 / 4 / 5 / 6 / 7 / 8 units up front = 131.5 / 128.3 / 127.7 / 127.8 / 127.5 / 127.8 /
+// 127.9 us, and ten +1.7 us against four on another box -- flat from two to eight, so the depths stay; two units up front for the
+// 320-channel stage spill in its sliced instantiation: docs/history.md, round 8)
 constexpr int kPre0Q15 = 10, kPre0Q15C = 4, kPre0Q17 = 0, kLagQ15 = 1, kLagQ15C = 1, kLagQ17 = 2;
 
 template <class C, bool PARTIAL = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void fused_block_lb4_kernel(Lb4StageArgs sa, int B) {
     __shared__ __attribute__((aligned(16))) unsigned smem[C::LDS_DW];
-    u32x4 Xr[5][2], pf[C::NKB / 8];
+    u32x4 Xr[5][2];
     f32x4 vres[5];
     Lb4Pre pre;
-    lb4_stage<C, void, true, C::GRP_DW, PARTIAL, C::NKB / 8, C::MTW == 5 ? kPre0Q15 : kPre0Q17, C::MTW == 5 ? kLagQ15 : kLagQ17>(smem, sa, nullptr, B, Xr, vres, pf, pre);
+    lb4_stage<C, void, true, C::GRP_DW, PARTIAL, C::MTW == 5 ? kPre0Q15 : kPre0Q17, C::MTW == 5 ? kLagQ15 : kLagQ17>(smem, sa, nullptr, B, Xr, vres, pre);
 }
 
 // y = (slice 0 + slice 1 + ... in this order) / (16 Sp) + BN shift (+ x): one thread per four channels of a pixel
@@ -418,14 +474,12 @@ struct Lb4ChainArgs { Lb4StageArgs s[3]; };
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void fused_chain_lb4_kernel(Lb4ChainArgs ca, int B) {
     __shared__ __attribute__((aligned(16))) unsigned smem[kChain4LdsDw];
-    constexpr int NPF = Q17::NKB / 8;
-    static_assert(Q17::NKB >= Q15::NKB, "pf holds a group of any stage");
-    u32x4 Xr[5][2], pf[NPF];
+    u32x4 Xr[5][2];
     f32x4 vres[5];
     Lb4Pre pre;
-    lb4_stage<Q15, Q15, true, kChain4Grp, false, NPF, kPre0Q15C, kLagQ15C>(smem, ca.s[0], ca.s[1].Glb, B, Xr, vres, pf, pre);
-    lb4_stage<Q15, Q17, false, kChain4Grp, false, NPF, kPre0Q15C, kLagQ15C>(smem, ca.s[1], ca.s[2].Glb, B, Xr, vres, pf, pre);
-    lb4_stage<Q17, void, false, kChain4Grp, false, NPF, kPre0Q17, kLagQ17>(smem, ca.s[2], nullptr, B, Xr, vres, pf, pre);
+    lb4_stage<Q15, Q15, true, kChain4Grp, false, kPre0Q15C, kLagQ15C>(smem, ca.s[0], ca.s[1].Glb, B, Xr, vres, pre);
+    lb4_stage<Q15, Q17, false, kChain4Grp, false, kPre0Q15C, kLagQ15C>(smem, ca.s[1], ca.s[2].Glb, B, Xr, vres, pre);
+    lb4_stage<Q17, void, false, kChain4Grp, false, kPre0Q17, kLagQ17>(smem, ca.s[2], nullptr, B, Xr, vres, pre);
 }
 
 template <class C>
