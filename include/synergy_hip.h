@@ -778,6 +778,39 @@ int syn_mobilenet1_layer(syn_handle *h, int layer, int fused, const void *in, in
 int syn_mobilenet2_span(syn_handle *h, int first, int last, const void *in, int in_u8, int B, size_t n_in, float *out, size_t n_out,
                         float *aux, size_t n_aux, int *launch_tags, int max_tags, void *stream);
 
+/* Blocks first .. last of the loaded resnet50 (arch 1) on activations the caller supplies -- the hook tests/test_gpu_resnet50_spans.py judges
+ * every element of every launch with.  Block 0 = stem + max-pool, 1..16 = the bottlenecks layer1.0 .. layer4.2, 17 = pool + heads.  The span
+ * runs inside the forward's own loop, entered at `first` and left behind `last`, so the launches are the ones the forward selects for this
+ * batch size under the handle's SYNERGY_HIP_FUSION, SYNERGY_HIP_RESNET_FUSE, SYNERGY_HIP_RESNET_GEMM, SYNERGY_HIP_RANGE_GUARD, weight
+ * verdict and test knobs.  All buffers are plain fp32 NHWC; inside an fp16 x2 forward the hook converts the input to the pair format and
+ * the results back (hi + lo is exact: the way out loses nothing).
+ *   first = 0      in = uint8 HWC crops [B,120,120,3] when in_u8 is set, fp32 CHW crops [B,3,120,120] otherwise
+ *   first = 1..17  in = the input of block `first`, [B,hin,hin,cin] ([B,4,4,2048] for 17)
+ *   last <= 16     out = the output of block `last`, [B,hout,hout,cout] ([B,30,30,64] for 0)
+ *   last = 17      out = [B,62], a non-NULL aux receives the pool [B,2048]
+ *   last = 1..15   the fused launch that ends block `last` (conv_c3f_kernel) also produces conv1 of block last + 1; it is not replaced, and
+ *                  a non-NULL aux receives that conv1 output [B,h,h,c1].  Where no fused launch ran (an fp32 handle, SYNERGY_HIP_RESNET_FUSE=0,
+ *                  layers 3 / 4) aux is left untouched and SYN_SPAN_AUX_WRITTEN is not set in the return value.
+ * Returns the number of launches n, with SYN_SPAN_AUX_WRITTEN or-ed in when aux (last <= 15) was written, or a negative syn_status.
+ * launch_tags[i] = 1000 x block + the code of the KERNEL VARIANT of launch i, as the launcher that chose it reports it:
+ *     1  resnet_stem_kernel (direct)        3  resnet_stem_mfma_kernel        4  resnet_stem_mfma_kernel with the max-pool epilogue
+ *     5  maxpool3x3s2_kernel               90  pool_fc_generic_kernel        60  conv_lp_kernel DUAL (conv3 + stride-2 downsample branch)
+ *    10 + MT  conv_kernel<MT,4> (exact fp32 MFMA; MT = 1, 2, 4)
+ *    20 + MT  conv_f16x2_kernel<MT,4> (64-bit addressing; MT = 1, 2)             30 + MT  conv_h2s_kernel<MT,4,2> (MT = 1, 2)
+ *    40 + 2 [MTW = 4] + [frag]  conv_lt_kernel<MTW,frag> (MTW = 2, 4)            50 + 2 [MTW = 4] + [frag]  conv_lp_kernel<MTW,frag>
+ *   100 + 10 shape + 4 [DS] + 2 [C2F] + [identity in pairs]  conv_c3f_kernel; shape 0 = <KS3 2, NT1 4> (layer 1), 1 = <2, 8> (layer 1 ->
+ *        layer 2), 2 = <4, 8> (layer 2); DS = the downsample branch in the kernel (layer1.0), C2F = conv2 in front
+ * With the range guard armed the span resets and fills the status array as the forward does; the slots of guarded tensors the span did
+ * not produce read 1 like the unguarded ones, so syn_backbone_range_status returns the maxima of the tensors the span produced.
+ * n_in / n_out / n_aux are ELEMENT counts (n_aux = 0 when aux is NULL).  Refused with SYN_ERR_INVALID and a message that names what was
+ * expected, before any launch, with `out` untouched: a count that differs from what the span needs, a handle whose arch is not resnet50,
+ * first > last or either outside 0..17, in_u8 with first != 0, aux with last = 0 or 16, B < 1 or B > 65536, max_tags below the span's
+ * per-layer launch count (2 for block 0, 3 per bottleneck, 4 with a downsample branch, 1 for block 17).  Asynchronous on `stream`; all
+ * pointers but launch_tags are device pointers; the intermediates live in the handle's workspace (one stream at a time, as the forward). */
+#define SYN_SPAN_AUX_WRITTEN 0x10000
+int syn_resnet50_span(syn_handle *h, int first, int last, const void *in, int in_u8, int B, size_t n_in, float *out, size_t n_out,
+                      float *aux, size_t n_aux, int *launch_tags, int max_tags, void *stream);
+
 /* One block of the loaded GhostNet (arch 6) on activations the caller supplies, through exactly the launches the forward uses for that
  * block (one helper derives the launch arguments for both) -- the hook tests/test_gpu_ghostnet.py judges every block with.
  *   block 0..15  bottleneck blocks.0.0 .. blocks.8.3: in = NHWC fp32 [B,hin,hin,cin], out = [B,hout,hout,cout]; on a block with

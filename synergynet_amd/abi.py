@@ -133,6 +133,8 @@ _SIGS = {
                                        C.c_size_t, C.c_void_p]),
     'syn_mobilenet2_span': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                       C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+    'syn_resnet50_span': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                    C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
     # block 0..15 bottlenecks, 16 ConvBnAct, 17 pool + conv_head + heads, 18 conv_stem (in = normalised fp32 crops NCHW, no aux)
     'syn_ghostnet_block': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
@@ -150,6 +152,7 @@ _SIGS = dict(_SIGS, syn_debug_feature=(C.c_int, [C.c_void_p, C.c_void_p, C.c_int
              syn_debug_profile_block=(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
              syn_debug_detect_raw=(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 5),
              syn_debug_poison_workspace=(C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+             syn_debug_resnet_pairs=(C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]),
              syn_debug_det_select_nms=(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]),
              syn_debug_det_preproc=(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]))

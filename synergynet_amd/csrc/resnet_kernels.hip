@@ -270,6 +270,7 @@ static void launch_conv_t(const float *in, const float *W, const float *scale, c
     const int grid = ((m_tiles + 7) / 8) * n_tiles * 8;
     if (in_pair) conv_kernel<MT, NT, true><<<grid, 256, 0, s>>>(in, W, scale, shift, residual, out, M, Hin, Hout, Cin, N, KH, KW, stride, pad, act, n_tiles, m_tiles, stat, fmt);
     else conv_kernel<MT, NT, false><<<grid, 256, 0, s>>>(in, W, scale, shift, residual, out, M, Hin, Hout, Cin, N, KH, KW, stride, pad, act, n_tiles, m_tiles, stat, fmt);
+    note_launch(kTagConv + MT);
 }
 
 // in_pair: the input is in the pair format (Cin % 32 == 0); fmt: kOutPair | kResPair.  Every ResNet-50 Cout is a multiple of 64 (required).
@@ -503,6 +504,7 @@ static void launch_conv_h2s_t(const float *in, const unsigned *W3, const float *
     const unsigned in_bytes = (unsigned)((size_t)(M / (Hout * Hout)) * Hin * Hin * Cin * 4);
     conv_h2s_kernel<MT, NT, KS><<<grid, 256, 0, s>>>(in, W3, scale, shift, residual, out, M, Hin, Hout, Cin, N, KH, KW, stride, pad,
                                                      act, n_tiles, m_tiles, stat, in_bytes, fmt);
+    note_launch(kTagH2s + MT);
 }
 
 // =====================================================================================
@@ -944,6 +946,7 @@ static void launch_conv_lt_t(const float *in, const unsigned *W3, const float *s
     if (lp) { if (frag) SYN_LT_LAUNCH(conv_lp_kernel, true); else SYN_LT_LAUNCH(conv_lp_kernel, false); }
     else { if (frag) SYN_LT_LAUNCH(conv_lt_kernel, true); else SYN_LT_LAUNCH(conv_lt_kernel, false); }
 #undef SYN_LT_LAUNCH
+    note_launch((lp ? kTagLp : kTagLt) + (MTW == 4 ? 2 : 0) + (frag ? 1 : 0));
 }
 
 // conv3 + stride-2 downsample branch of a bottleneck as ONE GEMM (conv_lp_kernel DUAL): a = T2 [B, H, H, C1] (1x1), x = the block input [B, Hin2, Hin2, Cin2] at
@@ -958,6 +961,7 @@ bool launch_conv_dual(const float *a, const float *x, const unsigned *W3d, const
     d2.in2 = x; d2.Hin2 = Hin2; d2.stride2 = stride2; d2.Cin2 = Cin2; d2.in2_bytes = (unsigned)((size_t)B * Hin2 * Hin2 * Cin2 * 4);
     conv_lp_kernel<4, false, true><<<grid, 512, 0, s>>>(a, W3d, ones, shift, nullptr, out, M, H, H, C1, N, 1, 1, 1, 0, act, n_tiles, m_tiles, stat,
                                                         (unsigned)((size_t)B * H * H * C1 * 4), fmt, d2);
+    note_launch(kTagDual);
     return true;
 }
 // the (K, N1) combinations conv_c3f_kernel is instantiated for (launch_conv_c3f)
@@ -972,6 +976,7 @@ static void launch_conv_f16x2_t(const float *in, const unsigned *W3, const float
     const int grid = ((m_tiles + 7) / 8) * n_tiles * 8;
     conv_f16x2_kernel<MT, NT><<<grid, 256, 0, s>>>(in, W3, scale, shift, residual, out, M, Hin, Hout, Cin, N, KH, KW, stride, pad,
                                                  act, n_tiles, m_tiles, stat, fmt);
+    note_launch(kTagF16x2 + MT);
 }
 
 // in: pair format; fmt: kOutPair | kResPair (the formats of out / residual).  N % 64 == 0, Cin % 64 == 0 (every ResNet-50 convolution behind the stem).
@@ -1355,6 +1360,7 @@ static void launch_c3f_t(const float *T2, const unsigned *W3, const float *scale
                          float *stat3, float *stat1, int res_pair, const C2Args *c2) {
     const int m_tiles = (M + 4 * MT * 16 - 1) / (4 * MT * 16), grid = ((m_tiles + 7) / 8) * 8;
 #define SYN_C3F_GO(RP, C2F, C2V) conv_c3f_kernel<KS3, NT1, MT, TC, false, RP, C2F><<<grid, 256, 0, s>>>(T2, W3, scale3, shift3, identity, out, W1f, s1, scale1, shift1, T1n, M, N3, m_tiles, stat3, stat1, DsArgs{}, C2V)
+    note_launch(kTagC3f + 10 * (KS3 == 4 ? 2 : NT1 == 8 ? 1 : 0) + ((KS3 == 2 || KS3 == 4) && c2 ? 2 : 0) + (res_pair ? 1 : 0));
     if constexpr (KS3 == 2 || KS3 == 4) {                        // (conv2 in front: the 64- and 128-channel bottlenecks of layers 1 / 2)
         if (c2) { if (res_pair) SYN_C3F_GO(true, true, *c2); else SYN_C3F_GO(false, true, *c2); return; }
     }
@@ -1377,6 +1383,7 @@ bool launch_conv_c3f_ds(const float *T2, const unsigned *W3, const float *scale3
     // (32-channel chunks: with 64 the second B operand spills)
     if (c2) conv_c3f_kernel<2, 4, MT, 2, true, false, true><<<grid, 256, 0, s>>>(T2, W3, scale3, shift3, nullptr, out, W1f, s1, scale1, shift1, T1n, M, N3, m_tiles, stat3, stat1, ds, *c2);
     else conv_c3f_kernel<2, 4, MT, 2, true, false><<<grid, 256, 0, s>>>(T2, W3, scale3, shift3, nullptr, out, W1f, s1, scale1, shift1, T1n, M, N3, m_tiles, stat3, stat1, ds);
+    note_launch(kTagC3f + 4 + (c2 ? 2 : 0));
     return true;
 }
 
@@ -1442,6 +1449,7 @@ void launch_resnet_stem(const float *img, const uint8_t *img8, const float *w, c
     const int npix = B * 3600;
     if (img8) resnet_stem_kernel<true><<<(npix + 15) / 16, 256, 0, s>>>(nullptr, img8, w, scale, shift, out, npix);
     else      resnet_stem_kernel<false><<<(npix + 15) / 16, 256, 0, s>>>(img, nullptr, w, scale, shift, out, npix);
+    note_launch(kTagStem);
 }
 
 // MaxPool2d(kernel 3, stride 2, padding 1) (resnet_backbone.py:172), NHWC fp32 in; padding never wins the max (-inf).  out_pair: the pooled
@@ -1483,6 +1491,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const float *__restri
 void launch_maxpool3x3s2(const float *in, float *out, int B, int Hin, int Hout, int C, hipStream_t s, float *stat, int out_pair) {
     const long total = (long)B * Hout * Hout * (C / 4);
     maxpool3x3s2_kernel<<<(int)((total + 255) / 256), 256, 0, s>>>(in, out, total, Hin, Hout, C / 4, stat, out_pair);
+    note_launch(kTagMaxpool);
 }
 
 // adaptive_avg_pool2d -> flatten -> linear heads (resnet_backbone.py:236-246): feat [B,P,C] NHWC, Wfc [n_out][C].
@@ -1557,6 +1566,7 @@ __global__ __launch_bounds__(256) void pool_fc_generic_kernel(const float *__res
 void launch_pool_fc_generic(const float *feat, const float *Wfc, const float *bias, float *param, float *pool, int B, int P,
                             int C, int n_out, int out_stride, hipStream_t s, const float *stat, int n_stat, unsigned *guard_word) {
     pool_fc_generic_kernel<<<B, 256, 0, s>>>(feat, Wfc, bias, param, pool, P, C, n_out, out_stride, stat, n_stat, guard_word);
+    note_launch(kTagPoolFc);
 }
 
 // =====================================================================================
@@ -1757,7 +1767,47 @@ bool launch_resnet_stem_mfma(const uint8_t *img8, const unsigned *As3, const flo
     const int wgs = (B + U - 1) / U;
     if (pool) resnet_stem_mfma_kernel<U, true><<<wgs < 256 ? wgs : 256, (2 * U + 1) * 64, 0, s>>>(img8, As3, s_shift, out, B, stat, out_pair);
     else resnet_stem_mfma_kernel<U><<<wgs < 256 ? wgs : 256, (2 * U + 1) * 64, 0, s>>>(img8, As3, s_shift, out, B);
+    note_launch(pool ? kTagStemMfmaPool : kTagStemMfma);
     return true;
+}
+
+// =====================================================================================
+// Test hook (syn_resnet50_span): the caller's buffers are plain fp32 NHWC, the tensors between the kernels of an fp16 x2 forward are in the
+// PAIR format (top of this file).  A thread owns the eight channels 32 b + 8 g .. + 7 of one pixel = k-group g of chunk b: the 16 bytes of
+// high halves at dword m C + 32 b + 4 g, the low halves 16 dwords further -- the arithmetic of split8 / unpair8, nothing else.
+// =====================================================================================
+thread_local LaunchSink *resnet_launch_sink = nullptr;
+
+__global__ __launch_bounds__(256) void pair_from_f32_kernel(const float *__restrict__ in, float *__restrict__ out, size_t n8, int C8) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n8) return;
+    const size_t m = idx / C8;
+    const int q = (int)(idx - m * C8), b = q >> 2, g = q & 3;
+    const float *src = in + idx * 8;
+    u32x4 pc[2];
+    split8(*(const f32x4 *)src, *(const f32x4 *)(src + 4), pc);
+    float *dst = out + m * (size_t)(8 * C8) + 32 * b + 4 * g;
+    *(u32x4 *)dst = pc[0];
+    *(u32x4 *)(dst + 16) = pc[1];
+}
+__global__ __launch_bounds__(256) void f32_from_pair_kernel(const float *__restrict__ in, float *__restrict__ out, size_t n8, int C8) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n8) return;
+    const size_t m = idx / C8;
+    const int q = (int)(idx - m * C8), b = q >> 2, g = q & 3;
+    const float *src = in + m * (size_t)(8 * C8) + 32 * b + 4 * g;
+    f32x4 v0, v1;
+    unpair8(*(const u32x4 *)src, *(const u32x4 *)(src + 16), v0, v1);
+    *(f32x4 *)(out + idx * 8) = v0;
+    *(f32x4 *)(out + idx * 8 + 4) = v1;
+}
+void launch_pair_from_f32(const float *in, float *out, size_t M, int C, hipStream_t s) {
+    const size_t n8 = M * (size_t)(C / 8);
+    pair_from_f32_kernel<<<(unsigned)((n8 + 255) / 256), 256, 0, s>>>(in, out, n8, C / 8);
+}
+void launch_f32_from_pair(const float *in, float *out, size_t M, int C, hipStream_t s) {
+    const size_t n8 = M * (size_t)(C / 8);
+    f32_from_pair_kernel<<<(unsigned)((n8 + 255) / 256), 256, 0, s>>>(in, out, n8, C / 8);
 }
 
 }  // namespace syn

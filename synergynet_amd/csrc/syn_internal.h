@@ -247,6 +247,27 @@ void launch_maxpool3x3s2(const float *in, float *out, int B, int Hin, int Hout, 
 void launch_pool_fc_generic(const float *feat, const float *Wfc, const float *bias, float *param, float *pool, int B, int P,
                             int C, int n_out, int out_stride, hipStream_t s, const float *stat = nullptr, int n_stat = 0,
                             unsigned *guard_word = nullptr /* host-mapped word: set to 1 by a forward the range guard poisoned */);
+// Test hook (syn_resnet50_span): which KERNEL VARIANT a launcher of resnet_kernels.hip chose is decided inside the launcher (M, N, the step
+// count, the 2 GiB limits, the knobs), so the launcher reports it: while resnet_launch_sink is set (by the hook, for the duration of its
+// call, on the calling thread) every launch records 1000 x sink->block + its code (include/synergy_hip.h has the table).  NULL in
+// production: one host branch per launch, nothing on the device.
+struct LaunchSink {
+    int codes[160];
+    int n = 0, block = 0;
+};
+extern thread_local LaunchSink *resnet_launch_sink;
+inline void note_launch(int code) {
+    if (LaunchSink *k = resnet_launch_sink) {
+        if (k->n < 160) k->codes[k->n] = 1000 * k->block + code;
+        ++k->n;
+    }
+}
+constexpr int kTagStem = 1, kTagStemMfma = 3, kTagStemMfmaPool = 4, kTagMaxpool = 5, kTagConv = 10 /* + MT 1 / 2 / 4 */, kTagF16x2 = 20 /* + MT */,
+              kTagH2s = 30 /* + MT */, kTagLt = 40 /* + 2 (MTW == 4) + frag */, kTagLp = 50 /* + 2 (MTW == 4) + frag */, kTagDual = 60, kTagPoolFc = 90,
+              kTagC3f = 100 /* + 10 shape (0: K 64 -> N1 64, 1: K 64 -> N1 128, 2: K 128 -> N1 128) + 4 DS + 2 C2F + (identity in pairs) */;
+// the two converters of the hook: fp32 NHWC [M][C] <-> the pair format (C % 32 == 0); hi + lo is exact, so the way out loses nothing
+void launch_pair_from_f32(const float *in, float *out, size_t M, int C, hipStream_t s);
+void launch_f32_from_pair(const float *in, float *out, size_t M, int C, hipStream_t s);
 
 // ---- MobileNetV1 variants (mobilenet1_kernels.hip): mobilenet_1 / _05 / _2, every product exact fp32 ----
 // 3x3 / 2 stem + BN + ReLU: NCHW fp32 or HWC uint8 crops -> NHWC [B,60,60,C0]; w [27][C0] (row ci*9 + ky*3 + kx), C0 = 16 | 32 | 64

@@ -1150,8 +1150,20 @@ int ensure_range(syn_handle *h) {
     return SYN_OK;
 }
 
+// Entry and exit of a span (syn_resnet50_span): block 0 = stem + max-pool, 1..16 = the bottlenecks, 17 = pool + heads.  The forward's loop is
+// entered at `first` on the caller's fp32 NHWC activations (first = 0: on the crops, as the forward) and left behind `last`; the production
+// call passes no span and issues exactly the launches it always issued.
+struct RSpan {
+    int first = 0, last = 17;
+    const float *in = nullptr;     // first >= 1: the input of block `first`, fp32 NHWC
+    float *out = nullptr;          // last <= 16: the output of block `last`, fp32 NHWC (last = 17: param / pool are the outputs)
+    float *aux = nullptr;          // last <= 15: conv1 of block last + 1 where the fused launch of block `last` produced it
+    bool aux_written = false;
+    syn::LaunchSink *sink = nullptr;
+};
+
 int run_resnet50(syn_handle *h, const float *img, const uint8_t *img8, int B, float *param, float *pool, hipStream_t s,
-                 int n_out = 62) {
+                 int n_out = 62, RSpan *sp = nullptr) {
     const ResNet50 &n = resnet50();
     int rc = ensure_ws(h, B);
     if (rc) return rc;
@@ -1185,38 +1197,77 @@ int run_resnet50(syn_handle *h, const float *img, const uint8_t *img8, int B, fl
     // test knob resnet_exact_mask = bit set of convolutions forced onto the exact kernel inside an fp16 x2 forward (tools/dbg_resnet_exact.py)
     static const unsigned long long force_exact = (unsigned long long)syn::test_knob("resnet_exact_mask", 0);
     auto unsafe_w = [&](int ci) { return ((force_exact >> ci) & 1ull) || (h->range_guard && ((h->resnet_w_unsafe[ci >> 5] >> (ci & 31)) & 1u)); };
+    // the guard slot of tensor t (0 = the max-pool output, 1 + i = the output of convs[i]), or NULL; `reported` keeps which slots a launch of
+    // this call was handed: a span neutralises the others (below)
+    unsigned long long reported = 0;
+    auto slot = [&](int t) -> float * {
+        if (!stat || !resnet_stat_used(t)) return nullptr;
+        reported |= 1ull << t;
+        return range_slot(stat, t);
+    };
     auto conv = [&](int ci, const float *in, const float *res, float *out, int act, int out_pair, int res_pair) {
         const RConv &c = n.convs[ci];
         const int fmt = (PF && out_pair ? syn::kFmtOutPair : 0) | (PF && res_pair ? syn::kFmtResPair : 0);
         if (f16 && c.dst_w3 && !unsafe_w(ci)) {
             syn::launch_conv_f16x2(in, reinterpret_cast<const unsigned *>(P + c.dst_w3), P + c.dst_scale, P + c.dst_shift, res, out, B,
                                  c.hin, c.hout, c.cin, c.cout, c.k, c.k, c.stride, c.pad, act, s,
-                                 stat && resnet_stat_used(1 + ci) ? range_slot(stat, 1 + ci) : nullptr, h->resnet_gemm, fmt);
+                                 slot(1 + ci), h->resnet_gemm, fmt);
             return;
         }
         // (a convolution whose WEIGHTS failed the fp16 criterion runs the exact kernel, but a later fp16 x2 convolution still takes its
         // output as pieces: it reports into its slot like the others -- left at 0 the slot read as "below the window" on every forward)
         syn::launch_conv(in, P + c.dst_w, P + c.dst_scale, P + c.dst_shift, res, out, B, c.hin, c.hout, c.cin, c.cout, c.k, c.k,
-                         c.stride, c.pad, act, s, stat && resnet_stat_used(1 + ci) ? range_slot(stat, 1 + ci) : nullptr, PF, fmt);
+                         c.stride, c.pad, act, s, slot(1 + ci), PF, fmt);
     };
+    // ---- span entry / exit (test hook; sp == nullptr in production) ----
+    const int first = sp ? sp->first : 0, span_last = sp ? sp->last : 17;
+    // a tensor between two blocks: [B,hw,hw,c] in the pair format inside an fp16 x2 forward (`pairs`), fp32 otherwise; the caller's side is fp32
+    auto span_copy = [&](const float *src, float *dst, size_t pixels, int c, bool pairs, bool to_pairs) {
+        if (!pairs) return hipMemcpyAsync(dst, src, pixels * c * sizeof(float), hipMemcpyDeviceToDevice, s);
+        if (to_pairs) syn::launch_pair_from_f32(src, dst, pixels, c, s); else syn::launch_f32_from_pair(src, dst, pixels, c, s);
+        return hipGetLastError();
+    };
+    // slots of guarded tensors that no launch of the span reported read as neutral (1.0, like the unguarded ones: slot 63 of the initial values)
+    auto span_neutralise = [&]() {
+        for (int t = 0; stat && sp && t < kResnetStat; ++t)
+            if (resnet_stat_used(t) && !((reported >> t) & 1ull)) {
+                const hipError_t e = hipMemcpyAsync(range_slot(stat, t), range_slot(stat + kRangeFloats, 63),
+                                                    (size_t)syn::kRangeSub * syn::kRangeStride * sizeof(float), hipMemcpyDeviceToDevice, s);
+                if (e != hipSuccess) return e;
+            }
+        return hipSuccess;
+    };
+    auto at_block = [&](int block) { if (sp && sp->sink) sp->sink->block = block; };
     const RConv &st = n.convs[0];
+    at_block(first);
     // conv1+bn1+relu (:231-233): uint8 crops on the bf16 matrix pipe (batches that give every CU a workgroup), else the direct kernel
     // (the max-pool, :234, rides in the matrix-pipe stem's epilogue: the 60x60x64 tensor never exists)
-    if (h->fusion >= 2 && img8 && B >= 128 && (h->early_rm & 16) && h->resnet_fuse &&
-        syn::launch_resnet_stem_mfma(img8, reinterpret_cast<const unsigned *>(P + st.dst_wrm), P + st.dst_wrm + 2 * 10 * 2 * 256, X, B, s, 1, stat, PF)) {
+    if (first >= 1) {           // the caller's activations are the input of block `first` (block 17 reads the last block's output: always fp32)
+        const RConv &ci = first <= 16 ? n.convs[n.blocks[first - 1].c1] : n.convs[n.blocks.back().c3];
+        const size_t pixels = first <= 16 ? (size_t)B * ci.hin * ci.hin : (size_t)B * ci.hout * ci.hout;
+        HIP_TRY(span_copy(sp->in, X, pixels, first <= 16 ? ci.cin : ci.cout, PF && first <= 16, true));
+    } else if (h->fusion >= 2 && img8 && B >= 128 && (h->early_rm & 16) && h->resnet_fuse &&
+               syn::launch_resnet_stem_mfma(img8, reinterpret_cast<const unsigned *>(P + st.dst_wrm), P + st.dst_wrm + 2 * 10 * 2 * 256, X, B, s, 1, slot(0), PF)) {
     } else {
         if (!(h->fusion >= 2 && img8 && B >= 128 && (h->early_rm & 16) &&
               syn::launch_resnet_stem_mfma(img8, reinterpret_cast<const unsigned *>(P + st.dst_wrm), P + st.dst_wrm + 2 * 10 * 2 * 256, A, B, s)))
             syn::launch_resnet_stem(img, img8, P + st.dst_w, P + st.dst_scale, P + st.dst_shift, A, B, s);
-        syn::launch_maxpool3x3s2(A, X, B, 60, 30, 64, s, stat, PF);                                      // maxpool (:234)
+        syn::launch_maxpool3x3s2(A, X, B, 60, 30, 64, s, slot(0), PF);                                      // maxpool (:234)
+    }
+    if (sp && span_last == 0) {
+        HIP_TRY(span_copy(X, sp->out, (size_t)B * 900, 64, PF, false));
+        HIP_TRY(span_neutralise());
+        HIP_TRY(hipGetLastError());
+        return SYN_OK;
     }
     // Bottleneck.forward (:114-136).  Where conv3 of a block and conv1 of the next can run as ONE launch (conv_c3f_kernel: layer 1, whose
     // convolutions are bound by memory throughput), the block output is not read back as conv1's operand and T1 already holds the next
     // block's conv1 output when its turn comes.
     bool have_t1 = false;
-    for (size_t bi = 0; bi < n.blocks.size(); ++bi) {
+    for (size_t bi = first >= 1 ? first - 1 : 0; bi < n.blocks.size(); ++bi) {
         const RBlock &b = n.blocks[bi];
         const bool last = bi + 1 == n.blocks.size();
+        at_block((int)bi + 1);
         if (!have_t1) conv(b.c1, X, nullptr, T1, 1, 1, 0);
         have_t1 = false;
         const float *identity = X;
@@ -1235,7 +1286,7 @@ int run_resnet50(syn_handle *h, const float *img, const uint8_t *img8, int B, fl
         if (c2f) {
             c2a.T1 = T1; c2a.W2 = reinterpret_cast<const unsigned *>(P + c2c.dst_w3); c2a.scale2 = P + c2c.dst_scale; c2a.shift2 = P + c2c.dst_shift;
             c2a.Hin = c2c.hin; c2a.Hout = c2c.hout; c2a.stride = c2c.stride; c2a.in_bytes = (unsigned)((size_t)B * c2c.hin * c2c.hin * c2c.cin * 4);
-            c2a.stat2 = stat && resnet_stat_used(1 + b.c2) ? range_slot(stat, 1 + b.c2) : nullptr;
+            c2a.stat2 = slot(1 + b.c2);
             c2_done = true;
         } else
             conv(b.c2, T1, nullptr, T2, 1, 1, 0);
@@ -1246,8 +1297,7 @@ int run_resnet50(syn_handle *h, const float *img, const uint8_t *img8, int B, fl
             const RConv &c3 = n.convs[b.c3], &c1n = n.convs[n.blocks[bi + 1].c1];
             {
                 const float *s1 = P + c1n.dst_w3 + (size_t)(c1n.cout / 16) * (c1n.cin / 32) * 512;      // device {S, 1/S} of the next conv1's weights
-                float *st3 = stat && resnet_stat_used(1 + b.c3) ? range_slot(stat, 1 + b.c3) : nullptr;
-                float *st1 = stat && resnet_stat_used(1 + n.blocks[bi + 1].c1) ? range_slot(stat, 1 + n.blocks[bi + 1].c1) : nullptr;
+                float *st3 = slot(1 + b.c3), *st1 = slot(1 + n.blocks[bi + 1].c1);
                 const int M = B * c3.hout * c3.hout;
                 // a stride-1 downsample branch on 64 channels (layer1.0) is evaluated inside the fused kernel: no launch, no 256-channel tensor
                 if (b.ds >= 0 && n.convs[b.ds].stride == 1 && n.convs[b.ds].dst_w3 && !unsafe_w(b.ds)) {
@@ -1273,14 +1323,29 @@ int run_resnet50(syn_handle *h, const float *img, const uint8_t *img8, int B, fl
             !unsafe_w(b.c3) && !unsafe_w(b.ds) && syn::test_knob("lt_glds", 1) >= 1 && h->resnet_gemm == 1) {
             const RConv &c3 = n.convs[b.c3], &cd = n.convs[b.ds];
             c3_done = syn::launch_conv_dual(T2, X, reinterpret_cast<const unsigned *>(P + b.dst_w3d), P + b.dst_ones, P + b.dst_shiftd, Y, B, c3.hout, c3.cin,
-                                            cd.hin, cd.stride, cd.cin, c3.cout, 1, s, stat && resnet_stat_used(1 + b.c3) ? range_slot(stat, 1 + b.c3) : nullptr,
+                                            cd.hin, cd.stride, cd.cin, c3.cout, 1, s, slot(1 + b.c3),
                                             last ? 0 : syn::kFmtOutPair);
             if (c3_done) ds_done = true;
         }
         if (!ds_done) { conv(b.ds, X, nullptr, D, 0, 0, 0); identity = D; id_pair = 0; }
         if (!have_t1 && !c3_done) conv(b.c3, T2, identity, Y, 1, last ? 0 : 1, id_pair);      // out = relu(bn3(conv3) + identity)
         float *t = X; X = Y; Y = t;
+        if (sp && span_last == (int)bi + 1) {      // leave behind block `last`: its output, and the next block's conv1 where the fused launch made it
+            const RConv &c3 = n.convs[b.c3];
+            HIP_TRY(span_copy(X, sp->out, (size_t)B * c3.hout * c3.hout, c3.cout, PF && !last, false));
+            if (have_t1 && sp->aux) {
+                const RConv &c1n = n.convs[n.blocks[bi + 1].c1];
+                HIP_TRY(span_copy(T1, sp->aux, (size_t)B * c1n.hout * c1n.hout, c1n.cout, true, false));
+                sp->aux_written = true;
+            }
+            if (!have_t1 && !last) reported &= ~(1ull << (1 + n.blocks[bi + 1].c1));      // (no fused launch: the next conv1 was not produced)
+            HIP_TRY(span_neutralise());
+            HIP_TRY(hipGetLastError());
+            return SYN_OK;
+        }
     }
+    at_block(17);
+    HIP_TRY(span_neutralise());
     // avgpool + heads; rows are packed (ori, shape, exp, tex) = the cat order (:242-246); the SynergyNet wrapper takes [:, :62]
     syn::launch_pool_fc_generic(X, P + n.dst_fc_w, P + n.dst_fc_b, param, pool, B, 16, 2048, n_out, n_out, s, stat, stat ? kResnetStat : 0,
                                 stat ? h->guard_word_dev : nullptr);
@@ -3399,6 +3464,61 @@ int syn_mobilenet2_span(syn_handle *h, int first, int last, const void *in, int 
     if (rc != SYN_OK) return rc;
     for (size_t i = 0; i < tags.size() && i < (size_t)max_tags; ++i) launch_tags[i] = tags[i];
     return (int)tags.size();
+}
+
+// Blocks first .. last of the loaded resnet50 on caller-supplied activations (include/synergy_hip.h): run_resnet50 itself, entered at `first`
+// and left behind `last`, so the launches -- and the kernel variant of each, which the launchers report through syn::resnet_launch_sink --
+// are those the forward selects for this batch under the handle's schedule.  Everything is vetted before a device is touched.
+int syn_resnet50_span(syn_handle *h, int first, int last, const void *in, int in_u8, int B, size_t n_in, float *out, size_t n_out,
+                      float *aux, size_t n_aux, int *launch_tags, int max_tags, void *stream) {
+    if (!h || !in || !out || !launch_tags)
+        return fail(SYN_ERR_INVALID, "syn_resnet50_span: NULL argument (expected handle, in, out and launch_tags)");
+    if (h->arch != 1) return fail(SYN_ERR_INVALID, "syn_resnet50_span: this handle runs %s, expected resnet50", arch_name(h->arch));
+    if (first < 0 || first > 17 || last < 0 || last > 17 || first > last)
+        return fail(SYN_ERR_INVALID, "syn_resnet50_span: first=%d last=%d, expected 0 <= first <= last <= 17", first, last);
+    if (in_u8 && first != 0) return fail(SYN_ERR_INVALID, "syn_resnet50_span: in_u8 is set with first=%d, expected only with first = 0 (the crops)", first);
+    if (aux && (last == 0 || last == 16))
+        return fail(SYN_ERR_INVALID, "syn_resnet50_span: aux with last=%d, expected NULL (no fused launch ends block 0 or 16; aux is the next conv1 for last = 1..15, the pool for last = 17)", last);
+    if (B < 1 || B > 65536)          // the kernels index pixels in 32-bit integers
+        return fail(SYN_ERR_INVALID, "syn_resnet50_span: B=%d, expected 1 <= B <= 65536", B);
+    const ResNet50 &n = resnet50();
+    size_t f_in = (size_t)3 * syn::kImg * syn::kImg, f_out = 62, f_aux = 0, need_tags = 0;
+    if (first >= 1 && first <= 16) { const RConv &c = n.convs[n.blocks[first - 1].c1]; f_in = (size_t)c.hin * c.hin * c.cin; }
+    if (first == 17) f_in = (size_t)16 * 2048;
+    if (last == 0) f_out = (size_t)900 * 64;
+    if (last >= 1 && last <= 16) { const RConv &c = n.convs[n.blocks[last - 1].c3]; f_out = (size_t)c.hout * c.hout * c.cout; }
+    if (aux && last == 17) f_aux = 2048;
+    if (aux && last >= 1 && last <= 15) { const RConv &c = n.convs[n.blocks[last].c1]; f_aux = (size_t)c.hout * c.hout * c.cout; }
+    for (int k = first; k <= last; ++k) need_tags += k == 0 ? 2 : k == 17 ? 1 : n.blocks[k - 1].ds >= 0 ? 4 : 3;      // (one launch per layer: the most any schedule issues)
+    if (n_in != f_in * B || n_out != f_out * B || n_aux != f_aux * B)
+        return fail(SYN_ERR_INVALID, "syn_resnet50_span: blocks %d..%d at B=%d expected n_in=%zu n_out=%zu n_aux=%zu, got %zu %zu %zu", first, last, B,
+                    f_in * B, f_out * B, f_aux * B, n_in, n_out, n_aux);
+    if (max_tags < 0 || (size_t)max_tags < need_tags)
+        return fail(SYN_ERR_INVALID, "syn_resnet50_span: max_tags=%d, expected >= %zu (the per-layer launch count of blocks %d..%d)", max_tags, need_tags, first, last);
+    if (!h->d_backbone) return fail(SYN_ERR_NOT_LOADED, "syn_resnet50_span: backbone weights not loaded");
+    DeviceGuard g(h->device);
+    syn::LaunchSink sink;
+    RSpan sp;
+    sp.first = first; sp.last = last; sp.sink = &sink;
+    if (first >= 1) sp.in = (const float *)in;
+    if (last <= 16) { sp.out = out; sp.aux = aux; }
+    syn::resnet_launch_sink = &sink;
+    const int rc = run_resnet50(h, (first == 0 && !in_u8) ? (const float *)in : nullptr, (first == 0 && in_u8) ? (const uint8_t *)in : nullptr, B,
+                                last == 17 ? out : nullptr, last == 17 ? aux : nullptr, (hipStream_t)stream, 62, &sp);
+    syn::resnet_launch_sink = nullptr;
+    if (rc != SYN_OK) return rc;
+    for (int i = 0; i < sink.n && i < max_tags && i < 160; ++i) launch_tags[i] = sink.codes[i];
+    return sink.n | (sp.aux_written ? SYN_SPAN_AUX_WRITTEN : 0);
+}
+
+// Test hook, not part of include/synergy_hip.h: the two converters of syn_resnet50_span alone.  to_pairs != 0: fp32 [M][C] -> the pair format,
+// else back; C % 32 == 0; device pointers, in != out.
+int syn_debug_resnet_pairs(const float *in, float *out, size_t M, int C, int to_pairs, void *stream) {
+    if (!in || !out || in == out || M == 0 || C <= 0 || C % 32) return fail(SYN_ERR_INVALID, "syn_debug_resnet_pairs: bad argument (expected in != out, M > 0, C a multiple of 32)");
+    if (to_pairs) syn::launch_pair_from_f32(in, out, M, C, (hipStream_t)stream);
+    else syn::launch_f32_from_pair(in, out, M, C, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
 }
 
 // Calibration of the range verdict on the CALLER'S crops (include/synergy_hip.h): the load-time analysis proves the overflow side, but
