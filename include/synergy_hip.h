@@ -729,6 +729,40 @@ int syn_param_loss_backward(syn_handle *h, const float *input /*[B 62]*/, const 
  * dimension <= 0 or margin < 0. */
 int syn_center_crop_u8(syn_handle *h, const uint8_t *in /*[B H W C]*/, int B, int H, int W, int C, int margin, uint8_t *out, void *stream);
 
+/* The reference's training transform (main_train.py:199-208: ColorJitter, ToTensor, CenterCrop in its train form, Normalize; utils/ddfa.py
+ * and PIL's ImageEnhance) on a uint8 set that lives on the device: output face i is face records[i].src_index of `src`, jittered, cropped,
+ * masked and normalised, bit for bit what the reference's loader produces for the same draws.  One launch, one workgroup per output face;
+ * the gather by src_index happens in the kernel.
+ *   steps      op[j] = 0 skip, 1 brightness, 2 contrast, 3 saturation with factor[j], applied in the order j = 0, 1, 2; repeats allowed.
+ *              Each is PIL's blend(degenerate, image, factor) per byte, t = fp32(d) + fp32(factor * fp32(x - d)) with the product and
+ *              the sum rounded separately: truncated for 0 <= factor <= 1, otherwise 0 for t <= 0, 255 for t >= 255, truncated between.
+ *              d = 0 (brightness); the pixel's grey L = (19595 c0 + 38470 c1 + 7471 c2 + 32768) >> 16 (saturation; channel 0 is the
+ *              first byte in memory: the reference hands BGR bytes to PIL as RGB, and so does this); floor((2 sum L + H W) / (2 H W))
+ *              over the image as it stands when the step runs (contrast; an integer sum).
+ *   crop, mask pixels outside [margin, H - margin) x [margin, W - margin) become 0; mask kind k != 0 zeroes everything outside its box too,
+ *              rows x columns: 1 [0, H/2) x [0, W/2); 2 [0, H/2) x [W/2, W); 3 [H/2, H) x [0, W/2); 4 the box of kind 1 (the reference's
+ *              rdown repeats lup); 5 all x [0, W/2); 6 all x [W/2, W); 7 [H/4, H - ceil(H/4)) x [W/4, W - ceil(W/4)).  2 margin >= min(H, W): all 0.
+ *   out_f32    [B 3 H W]: fp32(fp32(byte - mean) / std), a correctly rounded division; a zeroed pixel is (0 - mean) / std
+ *   out_u8     [B H W 3]: the jittered, cropped, masked bytes (what syn_backbone_forward_u8 ingests).  Either output may be NULL, not both.
+ * A face's output bits do not depend on B or on its position in the batch.  src and the outputs need no alignment; a face whose first
+ * byte is 16-byte aligned is read with 16-byte loads, any other with byte loads.
+ * The caller's error, but never an access outside the buffers: a record with src_index outside [0, N), an op above 3 or a mask above 7
+ * gives an all-zero face (every byte 0, every float (0 - mean) / std).
+ * No scratch, no host synchronisation, asynchronous on `stream`; src, records and the outputs are device pointers.
+ * Refused with SYN_ERR_INVALID and the outputs untouched: a NULL h, src or records; both outputs NULL; N, H, W or B <= 0; margin < 0; std
+ * 0 or not finite; mean not finite; 3 H W above SYN_TRAIN_TRANSFORM_MAX_FACE_BYTES (the face and its reduction words live in one
+ * workgroup's 160 KiB of LDS); an output that overlaps src or the other output. */
+typedef struct syn_train_record {
+    int32_t src_index;
+    float factor[3];
+    uint8_t op[3];
+    uint8_t mask;
+} syn_train_record;
+#define SYN_TRAIN_TRANSFORM_MAX_FACE_BYTES 163776          /* 160 KiB - 16 reduction words; 3 H W may not exceed it */
+int syn_train_transform_u8(syn_handle *h, const uint8_t *src /*[N H W 3]*/, int N, int H, int W, const syn_train_record *records /*[B]*/, int B,
+                           int margin, float mean, float std, float *out_f32 /*nullable [B 3 H W]*/, uint8_t *out_u8 /*nullable [B H W 3]*/,
+                           void *stream);
+
 /* ---- introspection (bench / profiling) --------------------------------------------- */
 
 /* Number of kernel launches one per-layer syn_backbone_forward issues. */

@@ -17,6 +17,7 @@ from .build import LIB
 SYN_ERR_INVALID, SYN_ERR_NOT_LOADED = -1, -3
 SYN_ERR_PARAM_LEN = -4
 SYN_DETECT_BATCH_MAX_FRAMES = 1024          # include/synergy_hip.h: syn_detect_batch refuses a larger N
+SYN_TRAIN_TRANSFORM_MAX_FACE_BYTES = 163776 # include/synergy_hip.h: syn_train_transform_u8 refuses a face of more bytes (3 H W)
 _lib = None
 
 
@@ -127,6 +128,8 @@ _SIGS = {
                                          C.c_void_p]),
     'syn_param_loss_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'syn_center_crop_u8': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'syn_train_transform_u8': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     'syn_backbone_launch_count': (C.c_int, [C.c_void_p]),
     'syn_backbone_profile': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'syn_mobilenet1_layer': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+struct syn_train_record;                    // include/synergy_hip.h
+
 namespace syn {
 
 #ifdef __HIPCC__
@@ -490,6 +492,11 @@ void launch_synergy_losses(const float *param, const float *target, const float 
                            const float *param_rev, int B, double *partial, unsigned *counter, float *scalars, float *per_face, double *meter,
                            hipStream_t s);
 void launch_center_crop_u8(const uint8_t *in, uint8_t *out, int B, int H, int W, int C, int margin, hipStream_t s);
+
+// ---- train-time augmentation (augment_kernels.hip): ColorJitter + CenterCrop(train) + Normalize, one workgroup per output face ----
+// records: B device records; either output nullable.  The caller has checked 3 H W against SYN_TRAIN_TRANSFORM_MAX_FACE_BYTES.
+hipError_t launch_train_transform(const uint8_t *src, int N, int H, int W, const syn_train_record *records, int B, int margin, float mean,
+                                  float stdv, float *out_f32, uint8_t *out_u8, hipStream_t s);
 
 // ---- backward of the two loss modules (loss_backward_kernels.hip) ----
 // count: [wing_chunks(N) + 1] 64-bit words of scratch (chunk counts, then n); g nullable (1 float: upstream gradient 1); counter as above

@@ -4902,4 +4902,24 @@ int syn_center_crop_u8(syn_handle *h, const uint8_t *in, int B, int H, int W, in
     return SYN_OK;
 }
 
+int syn_train_transform_u8(syn_handle *h, const uint8_t *src, int N, int H, int W, const syn_train_record *records, int B, int margin, float mean,
+                           float std, float *out_f32, uint8_t *out_u8, void *stream) {
+    if (!h || !src || !records) return fail(SYN_ERR_INVALID, "syn_train_transform_u8: NULL argument");
+    if (!out_f32 && !out_u8) return fail(SYN_ERR_INVALID, "syn_train_transform_u8: both outputs are NULL");
+    if (N <= 0 || H <= 0 || W <= 0 || B <= 0) return fail(SYN_ERR_INVALID, "syn_train_transform_u8: N=%d H=%d W=%d B=%d", N, H, W, B);
+    if (margin < 0) return fail(SYN_ERR_INVALID, "syn_train_transform_u8: margin=%d", margin);
+    if (!std::isfinite(std) || std == 0.f || !std::isfinite(mean)) return fail(SYN_ERR_INVALID, "syn_train_transform_u8: mean=%g std=%g", mean, std);
+    const unsigned long long face = 3ull * (unsigned long long)H * (unsigned long long)W;
+    if (face > SYN_TRAIN_TRANSFORM_MAX_FACE_BYTES)
+        return fail(SYN_ERR_INVALID, "syn_train_transform_u8: a face of %llu bytes (H=%d W=%d) does not fit one workgroup's LDS, at most %d", face, H, W,
+                    SYN_TRAIN_TRANSFORM_MAX_FACE_BYTES);
+    const size_t n_src = (size_t)N * face, n_u8 = (size_t)B * face, n_f32 = n_u8 * sizeof(float);
+    if (bytes_overlap(out_f32, n_f32, src, n_src) || bytes_overlap(out_u8, n_u8, src, n_src) || bytes_overlap(out_f32, n_f32, out_u8, n_u8))
+        return fail(SYN_ERR_INVALID, "syn_train_transform_u8: an output overlaps the source set or the other output");
+    DeviceGuard g(h->device);
+    HIP_TRY(syn::launch_train_transform(src, N, H, W, records, B, margin, mean, std, out_f32, out_u8, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
+    return SYN_OK;
+}
+
 }  // extern "C"

@@ -1160,10 +1160,15 @@ class SynergyNet(nn.Module):
             raise RuntimeError('recalibrate_synergy_bn: no batches')
         return k
 
-    def losses_crops_u8(self, crops, target, meter=None):
-        """`forward` from uint8 crops [B,120,120,3] (what forward_crops_u8 takes)"""
+    def losses_crops_u8(self, crops, target, meter=None, bn='running', momentum=0.1):
+        """`forward` from uint8 crops [B,120,120,3] (what forward_crops_u8 takes, and what augment.TrainTransform(out='u8') gives);
+        bn / momentum as `forward` has them"""
+        if bn not in ('running', 'batch'):
+            raise RuntimeError(f"bn must be 'running' or 'batch', got {bn!r}")
         self._need_synergy()
         param, pool = self.forward_crops_u8(crops, return_pool=True)
+        if bn == 'batch':
+            return self._losses_train(param, pool, target, momentum, meter)
         return self._losses(param, pool, target, meter)
 
     def validate(self, batches):
